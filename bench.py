@@ -14,9 +14,14 @@ A "step" is ONE full render of the workload -- by default BASELINE.json configs[
 800x600, 256 spp, max_bounces 30 -- through the C ABI with the scene already resident in HBM: path-tracing
 kernel + ordered resolve kernel on every rank's row strips, then (N > 1) one RCCL all-gather of the packed rows
 and the de-interleave.  The image is fixed, so scaling is STRONG.
-value = width*height*spp*K / max-over-ranks wall time of the K steps, in Msamples/s.
+value = width*height*spp*K / max-over-ranks wall time of the K steps, in Msamples/s; ms_per_step = that wall time / K.
 
-Extra objects in the JSON line:
+A plain run sets up, warms up, times the K steps and prints the line: its live figures are those of the timed region (HIP-event
+kernel times, the image checksum).  --full adds everything that takes work of its own after the timed region: the counter step
+(rays/sample, kernel registers), the roofline, cpu_baseline and one_shot.  --dump-outputs DIR writes what the last timed step
+handed its caller (the image, as float32 8-bit channel values) to DIR/image_rgb.npy.
+
+Extra objects in the JSON line with --full:
   roofline     the dominant kernel (k_render_ctr_*) against the unit that binds it, the f32 VALU issue rate:
                achieved = SQ_INSTS_VALU per step (PMC, profiles/pmc_counters.json, taken on THIS kernel -- the file
                carries a hash of the kernel sources; the line says "pmc": "committed (hash-matched)" when it is the hash of the library
@@ -128,7 +133,12 @@ def main(argv=None):
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="cornell-box-800x600x256-d30", choices=sorted(WORKLOADS))
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target wall time of the cpu_baseline sample; 0 disables it")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also take the counter step, the roofline, cpu_baseline and (N = 1) one_shot; a plain run prints the "
+                         "headline figures of the timed steps only")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the image of the last timed step to DIR/image_rgb.npy ([H, W, 3] float32 channel values 0..255)")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target wall time of the cpu_baseline sample (--full); 0 disables it")
     ap.add_argument("--pipeline", type=int, default=0,
                     help="frames in flight (own stream + workspace each): 2 lets frame k's resolve + gather overlap frame k+1's tracing. "
                          "0 = auto: 1 on one GPU (clean per-kernel timing), 2 on several")
@@ -151,7 +161,7 @@ def main(argv=None):
     ap.add_argument("--rendezvous-timeout", type=float, default=120.0,
                     help="rank path: timeout of init_process_group and of every collective (torch's default for nccl is 10 minutes, longer than a driver's whole "
                          "limit; 120 s leaves room for ranks whose first `import torch` on a fresh box pages the image in at different speeds)")
-    ap.add_argument("--no-one-shot", action="store_true", help="skip the one-shot mi355rt_render timing (N = 1) that the line carries as `one_shot`")
+    ap.add_argument("--no-one-shot", action="store_true", help="--full: skip the one-shot mi355rt_render timing (N = 1) that the line carries as `one_shot`")
     ap.add_argument("--single-process", action="store_true",
                     help="N > 1 without a launcher: one process, one context + stream per device, gather by device-to-device copies into device 0 "
                          "(what `bench.py --gpus N` falls back to when the one-rank-per-GPU launch cannot start)")
@@ -280,10 +290,14 @@ def main(argv=None):
     torch.cuda.synchronize()
     image_checksum = None if image is None else int(image.to(torch.int64).sum().item())    # identical for every N and pipeline depth (RNG keyed by absolute row)
     final_image = None if image is None else image.clone()                                  # the slot buffers are reused below
+    if args.dump_outputs and rank == 0 and final_image is not None:
+        dump_outputs(args.dump_outputs, final_image, W, H)
 
-    # one extra (untimed) step with counters for rays/sample
-    torch.cuda.synchronize()
-    st = ctx0.render(slots[0]["local"].data_ptr(), None, opt, slots[0]["stream"].cuda_stream, want_stats=True)
+    # --full: one extra (untimed) step with counters for rays/sample
+    st = None
+    if args.full:
+        torch.cuda.synchronize()
+        st = ctx0.render(slots[0]["local"].data_ptr(), None, opt, slots[0]["stream"].cuda_stream, want_stats=True)
     local_samples = n_local_rows * W * spp
     variant = ctx0.kernel_variant()
     render_ms_per_step = k_render_ms / max(args.steps, 1)    # kernel time per STEP (= per full render of this rank's rows, all workspace bands together),
@@ -294,12 +308,12 @@ def main(argv=None):
     if use_dist:
         me = dict(device_identity(torch, local_rank), rank=rank, local_rank=local_rank, pid=os.getpid(), rows=n_local_rows,
                   kernel_ms_per_step=round(render_ms_per_step, 4), resolve_ms_per_step=round(resolve_ms_per_step, 4),
-                  step_wall_ms=round(my_elapsed / max(args.steps, 1) * 1e3, 4), rays=int(st.rays))
+                  step_wall_ms=round(my_elapsed / max(args.steps, 1) * 1e3, 4), **({"rays": int(st.rays)} if st is not None else {}))
         ranks = [None] * world
         dist.all_gather_object(ranks, me)
 
     one_shot = None
-    if world == 1 and not use_dist and not args.no_one_shot:
+    if args.full and world == 1 and not use_dist and not args.no_one_shot:
         one_shot = measure_one_shot(abi, device, scene)
     tail = None
     if args.tail_parts > 1 and world == 1:
@@ -435,11 +449,48 @@ def device_identity(torch, index):
 
 def make_result(args, abi, build, rtdist, scene, plan, world, elapsed, render_ms_per_step, resolve_ms_per_step, launches_per_step,
                 local_samples, st, variant, depth_pipe, gather, launch, dist_info, tail, image_checksum, extras):
-    """The one JSON line (rank 0 / the single process).  `st` = stats of one untimed render of the caller's own rows (rays, grid);
-    render_ms_per_step / local_samples describe the same rows."""
+    """The one JSON line (rank 0 / the single process).  `st` = stats of one untimed render of the caller's own rows (rays, grid), taken
+    with --full only; render_ms_per_step / local_samples describe the same rows.  Without --full (st None) `roofline` carries the live
+    kernel times of the timed region alone, and there is no cpu_baseline or kernel object."""
     path, W, H, spp, depth, _ = WORKLOADS[args.workload]
     total_samples = W * H * spp
     value = total_samples * args.steps / elapsed / 1e6
+    timing = {"kernel_ms_per_step": round(render_ms_per_step, 4), "resolve_ms_per_step": round(resolve_ms_per_step, 4),
+              "kernel_launches_per_step": launches_per_step, "samples_per_step": local_samples}
+    if st is not None:
+        roofline, cpu_baseline, kernel = full_figures(args, abi, build, scene, world, render_ms_per_step, local_samples, st, variant, depth_pipe, timing)
+    else:
+        roofline = {"kernel": KERNEL_NAMES.get(variant, "k_render_ctr"), **timing,
+                    "note": "live HIP-event kernel times of the timed steps; bench.py --full adds the VALU / HBM roofline, cpu_baseline and one_shot"}
+    result = {
+        "metric": f"Msamples/s (pixels x spp / s) at {W}x{H}x{spp}spp; 1/2/4/8-GPU scaling",
+        "value": round(value, 3), "unit": "Msamples/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "strong",
+        "vs_baseline": None, "dtype": "f32", "data": f"synthetic (the reference's own scene file {path}; no external data)",
+        "config": {"workload": args.workload, "scene": path, "width": W, "height": H, "spp": spp, "max_bounces": depth,
+                   "rng": "ctr (pcg4d counter hash: per-path base = pcg4d(x, sample, row key); block j after ray r = pcg4d(base + (0, 0, r, j)))", "parallelism": f"row strips of {plan.strip_rows} dealt round-robin over {world} GPU(s)"
+                   + (f", {gather}" if gather else ""),
+                   "frames_in_flight": depth_pipe, "share_of_device_per_frame": getattr(args, "share_used", 1),
+                   **({"streams": args.stream_info} if getattr(args, "stream_info", None) else {})},
+        "launch": launch,
+        "full": st is not None,
+        **({"distributed": dist_info} if dist_info else {}),
+        "roofline": roofline,
+        **({"cpu_baseline": cpu_baseline} if st is not None else {}),
+        **({"tail": tail} if tail else {}),
+        **extras,
+        **({"kernel": kernel} if st is not None else {}),
+    }
+    if image_checksum is not None:
+        result["image_checksum"] = image_checksum
+    return result
+
+
+def full_figures(args, abi, build, scene, world, render_ms_per_step, local_samples, st, variant, depth_pipe, timing):
+    """--full: the roofline of the dominant kernel, cpu_baseline and the kernel object -- the figures that take work of their own
+    (the counter step `st`, the committed PMC file, the CPU oracle's timed sample)."""
+    path, W, H, spp, depth, _ = WORKLOADS[args.workload]
+    total_samples = W * H * spp
     rays_per_sample = st.rays / max(st.samples, 1)
     sc = scene.c
     rec = sum(REC_BYTES[sc.primitives[i].kind] for i in range(sc.n_primitives))
@@ -468,47 +519,39 @@ def make_result(args, abi, build, rtdist, scene, plan, world, elapsed, render_ms
         hbm = {"traffic_bytes": traffic, "achieved_GBs": round(gbs, 1), "peak_GBs": HBM_PEAK_GBS, "frac": round(gbs / HBM_PEAK_GBS, 4),
                "formula": "(2*FETCH_SIZE + WRITE_SIZE) KiB x 1024 per step; x2 = gfx950 FETCH_SIZE correction (MI355X_MICROARCH.md, HBM)"}
     bytes_per_sample = rays_per_sample * (rec + 48 + nodes_per_ray * 32 + tris_per_ray * 48) + 16.0 / spp
-    result = {
-        "metric": f"Msamples/s (pixels x spp / s) at {W}x{H}x{spp}spp; 1/2/4/8-GPU scaling",
-        "value": round(value, 3), "unit": "Msamples/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "strong",
-        "vs_baseline": None, "dtype": "f32", "data": f"synthetic (the reference's own scene file {path}; no external data)",
-        "config": {"workload": args.workload, "scene": path, "width": W, "height": H, "spp": spp, "max_bounces": depth,
-                   "rng": "ctr (pcg4d counter hash: per-path base = pcg4d(x, sample, row key); block j after ray r = pcg4d(base + (0, 0, r, j)))", "parallelism": f"row strips of {plan.strip_rows} dealt round-robin over {world} GPU(s)"
-                   + (f", {gather}" if gather else ""),
-                   "frames_in_flight": depth_pipe, "share_of_device_per_frame": getattr(args, "share_used", 1),
-                   **({"streams": args.stream_info} if getattr(args, "stream_info", None) else {})},
-        "launch": launch,
-        **({"distributed": dist_info} if dist_info else {}),
-        "roofline": {"bound": "valu", "kernel": KERNEL_NAMES.get(variant, "k_render_ctr"),
-                     "achieved": None if achieved is None else round(achieved / 1e9, 1), "peak": round(peak_inst / 1e9, 1),
-                     "unit": "G wave-instructions/s", "frac": None if frac is None else round(frac, 4), "traffic": traffic,
-                     "lane_utilisation": lane_util,
-                     "wave_insts_per_step": None if achieved is None else int(insts),
-                     "wave_insts_per_ray": None if achieved is None or st.rays == 0 else round(insts * 64.0 / st.rays, 1),   # VALU instructions a wave issues per 64 rays
-                     "useful_frac": None if frac is None or lane_util is None else round(frac * lane_util, 4),
-                     "hbm": hbm,
-                     "kernel_ms_per_step": round(render_ms_per_step, 4), "resolve_ms_per_step": round(resolve_ms_per_step, 4),
-                     "kernel_launches_per_step": launches_per_step, "samples_per_step": local_samples,
-                     "pmc": pmc_state, "kernel_hash": khash,
-                     "logical_bytes_model": {"bytes_per_sample": round(bytes_per_sample, 1), "rays_per_sample": round(rays_per_sample, 4),
-                                             "bytes_per_step": int(bytes_per_sample * local_samples),
-                                             "note": "SURVEY.md 8d algorithmic bytes; SGPR/L2 resident, never reach HBM -- a model, not an HBM fraction"},
-                     "note": "achieved = SQ_INSTS_VALU per step (PMC, profiles/pmc_counters.json, same kernel hash) / live HIP-event kernel time per step; "
-                             "peak = 1024 SIMDs x 2.4 GHz / 2 cycles per wave64 VALU instruction (nominal: a loop of nothing but independent "
-                             "v_mul_f32 / v_add_f32 reaches 0.82-0.94 of it at a sustained 2.32-2.39 GHz -- tools/microbench/clock.hip, "
-                             "profiles/r03_microbench_clock_and_issue.txt -- and v_fma / v_rcp / v_sqrt / 64-bit multiplies take more than one slot)"
-                             + (f"; {depth_pipe} frames are in flight on their own streams, each on 1/{getattr(args, 'share_used', 1)} of the resident grid: a kernel's event time includes the time it shared the chip -- "
-                                "it is NOT the time of one frame alone, and `frac` is that of rank 0's kernel while the others ran beside it" if depth_pipe > 1 else "")
-                             + ("; kernel figures are those of rank / device 0's rows" if world > 1 else "")},
-        "cpu_baseline": cpu_baseline,
-        **({"tail": tail} if tail else {}),
-        **extras,
-        "kernel": {"vgprs": st.kernel_vgprs, "grid_blocks": st.grid_blocks, "block_threads": st.block_threads, "bands": st.bands},
-    }
-    if image_checksum is not None:
-        result["image_checksum"] = image_checksum
-    return result
+    roofline = {"bound": "valu", "kernel": KERNEL_NAMES.get(variant, "k_render_ctr"),
+                "achieved": None if achieved is None else round(achieved / 1e9, 1), "peak": round(peak_inst / 1e9, 1),
+                "unit": "G wave-instructions/s", "frac": None if frac is None else round(frac, 4), "traffic": traffic,
+                "lane_utilisation": lane_util,
+                "wave_insts_per_step": None if achieved is None else int(insts),
+                "wave_insts_per_ray": None if achieved is None or st.rays == 0 else round(insts * 64.0 / st.rays, 1),   # VALU instructions a wave issues per 64 rays
+                "useful_frac": None if frac is None or lane_util is None else round(frac * lane_util, 4),
+                "hbm": hbm,
+                **timing,
+                "pmc": pmc_state, "kernel_hash": khash,
+                "logical_bytes_model": {"bytes_per_sample": round(bytes_per_sample, 1), "rays_per_sample": round(rays_per_sample, 4),
+                                        "bytes_per_step": int(bytes_per_sample * local_samples),
+                                        "note": "SURVEY.md 8d algorithmic bytes; SGPR/L2 resident, never reach HBM -- a model, not an HBM fraction"},
+                "note": "achieved = SQ_INSTS_VALU per step (PMC, profiles/pmc_counters.json, same kernel hash) / live HIP-event kernel time per step; "
+                        "peak = 1024 SIMDs x 2.4 GHz / 2 cycles per wave64 VALU instruction (nominal: a loop of nothing but independent "
+                        "v_mul_f32 / v_add_f32 reaches 0.82-0.94 of it at a sustained 2.32-2.39 GHz -- tools/microbench/clock.hip, "
+                        "profiles/r03_microbench_clock_and_issue.txt -- and v_fma / v_rcp / v_sqrt / 64-bit multiplies take more than one slot)"
+                        + (f"; {depth_pipe} frames are in flight on their own streams, each on 1/{getattr(args, 'share_used', 1)} of the resident grid: a kernel's event time includes the time it shared the chip -- "
+                           "it is NOT the time of one frame alone, and `frac` is that of rank 0's kernel while the others ran beside it" if depth_pipe > 1 else "")
+                        + ("; kernel figures are those of rank / device 0's rows" if world > 1 else "")}
+    kernel = {"vgprs": st.kernel_vgprs, "grid_blocks": st.grid_blocks, "block_threads": st.block_threads, "bands": st.bands}
+    return roofline, cpu_baseline, kernel
+
+
+def dump_outputs(out_dir, image, W, H):
+    """--dump-outputs: what the timed path handed its caller in the last timed step -- the [H, W] image, one 0x00RRGGBB word per pixel --
+    as DIR/image_rgb.npy, [H, W, 3] float32 channel values 0..255 (exact; 5.8 MB at 800x600, 24.9 MB at 1920x1080)."""
+    import numpy as np
+    packed = image.cpu().numpy()[:H].astype(np.int64)
+    assert packed.shape == (H, W), packed.shape
+    rgb = np.stack([(packed >> 16) & 255, (packed >> 8) & 255, packed & 255], axis=-1).astype(np.float32)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "image_rgb.npy"), rgb)
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -747,15 +790,18 @@ def main_single_process(args):
         per_part.append((a / max(args.steps, 1), b / max(args.steps, 1), ln / max(args.steps, 1)))
     image_checksum = int(image.to(torch.int64).sum().item())
     final_image = image.clone()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, final_image, W, H)
     sync_all()
-    stats = []
-    for d, p in enumerate(parts):
-        s = p["slots"][0]
-        with torch.cuda.device(devs[d]):
-            stats.append(s["ctx"].render(s["local"].data_ptr(), None, p["opt"], s["stream"].cuda_stream, want_stats=True))
+    stats = [None] * n
+    if args.full:                                            # one extra (untimed) step per device with counters for rays/sample
+        for d, p in enumerate(parts):
+            s = p["slots"][0]
+            with torch.cuda.device(devs[d]):
+                stats[d] = s["ctx"].render(s["local"].data_ptr(), None, p["opt"], s["stream"].cuda_stream, want_stats=True)
     variant = parts[0]["slots"][0]["ctx"].kernel_variant()
     ranks = [dict(device_identity(torch, devs[d]), part=d, pid=os.getpid(), rows=len(plan.rows[d]), kernel_ms_per_step=round(per_part[d][0], 4),
-                  resolve_ms_per_step=round(per_part[d][1], 4), rays=int(stats[d].rays)) for d in range(n)]
+                  resolve_ms_per_step=round(per_part[d][1], 4), **({"rays": int(stats[d].rays)} if stats[d] is not None else {})) for d in range(n)]
     result = make_result(args, abi, build, rtdist, scene, plan, n, elapsed, per_part[0][0], per_part[0][1], per_part[0][2],
                          len(plan.rows[0]) * W * spp, stats[0], variant, depth_pipe,
                          gather=f"{n} device-to-device copies of the packed rows into device 0" if n > 1 else "",

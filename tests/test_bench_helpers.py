@@ -86,3 +86,26 @@ def test_kernel_hash_covers_the_code_not_the_comments(tmp_path, monkeypatch):
     hdr.write_text("#define X 2\n"); h1 = build.kernel_hash()
     monkeypatch.setattr(build, "HIPCC_FLAGS", build.HIPCC_FLAGS + ["-O2"])
     assert build.kernel_hash() != h1
+
+
+def test_plain_line_carries_the_headline_and_full_figures_stay_behind_full(tmp_path):
+    """A plain run's line: the headline keys from the timed region, no counter step, cpu_baseline or kernel object (those come with --full).
+    --dump-outputs writes the packed image as exact float32 channel values."""
+    import types
+    import numpy as np
+    import torch
+    bench = importlib.import_module("bench")
+    args = bench.argparse.Namespace(workload="cornell-box-400x300x16-d4", steps=4, warmup=1, full=False, share_used=1, stream_info=None)
+    plan = types.SimpleNamespace(strip_rows=300)
+    line = bench.make_result(args, None, None, None, None, plan, 1, 0.002, 0.4, 0.01, 1.0, 400 * 300 * 16, None, 3, 1, gather="",
+                             launch="direct", dist_info=None, tail=None, image_checksum=7, extras={})
+    assert line["value"] == round(400 * 300 * 16 * 4 / 0.002 / 1e6, 3) and line["ms_per_step"] == 0.5 and line["unit"] == "Msamples/s"
+    assert line["higher_is_better"] is True and line["dtype"] == "f32" and line["metric"].startswith("Msamples/s")
+    assert line["full"] is False and "cpu_baseline" not in line and "kernel" not in line and "one_shot" not in line
+    assert line["roofline"]["kernel_ms_per_step"] == 0.4 and line["roofline"]["kernel"] == "k_render_ctr_simple" and line["image_checksum"] == 7
+    json.dumps(line)
+    packed = torch.tensor([[0x00FF0080, 0x00010203], [0, 0x00FFFFFF]], dtype=torch.int32)
+    bench.dump_outputs(str(tmp_path / "out"), packed, 2, 2)
+    rgb = np.load(tmp_path / "out" / "image_rgb.npy")
+    assert rgb.dtype == np.float32 and rgb.shape == (2, 2, 3)
+    assert rgb.tolist() == [[[255, 0, 128], [1, 2, 3]], [[0, 0, 0], [255, 255, 255]]]

@@ -9,6 +9,9 @@ import textwrap
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BENCH = os.path.join(ROOT, "bench.py")
+# The bench processes these tests start see no device, on any machine (an index that is not a device ends HIP's list): the paths under test are
+# those of a box without a GPU, where a child that reaches the GPU stops at once ("no GPU visible").
+NO_GPU = {"HIP_VISIBLE_DEVICES": "-1"}
 
 STUB = textwrap.dedent("""
     import json, os, sys
@@ -35,7 +38,7 @@ def run_parent(tmp_path, args, **env_extra):
     runner = tmp_path / "runner.py"
     runner.write_text(RUNNER)
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MI355RT_BENCH_FORCE_DIST", "MI355RT_BENCH_REHEARSE")}
-    env.update(MI355RT_BENCH_LAUNCHER=f"{sys.executable} {stub}", STUB_OUT=str(tmp_path / "stub.json"), PARENT_OUT=str(tmp_path / "parent.json"), **env_extra)
+    env.update(NO_GPU, MI355RT_BENCH_LAUNCHER=f"{sys.executable} {stub}", STUB_OUT=str(tmp_path / "stub.json"), PARENT_OUT=str(tmp_path / "parent.json"), **env_extra)
     out = subprocess.run([sys.executable, str(runner), BENCH, *args], env=env, cwd=ROOT, capture_output=True, text=True, timeout=300)
     seen = json.load(open(tmp_path / "stub.json")) if (tmp_path / "stub.json").exists() else None
     parent = json.load(open(tmp_path / "parent.json"))
@@ -173,7 +176,7 @@ def test_under_a_launcher_nothing_is_launched(tmp_path):
     # Without a GPU the rank stops at "no GPU visible"; the stub must not have been started.
     stub_out = tmp_path / "stub.json"
     env = dict(os.environ, RANK="0", LOCAL_RANK="0", WORLD_SIZE="2", MASTER_ADDR="127.0.0.1", MASTER_PORT="29599",
-               MI355RT_BENCH_LAUNCHER=f"{sys.executable} -c pass", STUB_OUT=str(stub_out))
+               MI355RT_BENCH_LAUNCHER=f"{sys.executable} -c pass", STUB_OUT=str(stub_out), **NO_GPU)
     out = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--cpu-seconds", "0"], env=env, cwd=ROOT, capture_output=True, text=True, timeout=300)
     assert out.returncode != 0 and "no GPU visible" in out.stderr and not stub_out.exists()
 

@@ -103,3 +103,25 @@ def test_bench_single_process_mode_and_the_fallback_into_it(tmp_path, native, ab
     assert out.returncode == 0 and line, out.stderr[-2000:]
     assert line["launch"].startswith("fallback: one process drives 2 devices") and "ended with code 9" in line["launch"]
     assert line["image_checksum"] == want and "device-to-device copies" in line["config"]["parallelism"]
+
+
+def test_bench_plain_run_dumps_the_image_of_its_last_step_and_full_adds_the_rest(tmp_path, native, abi):
+    """`bench.py --gpus 1` as typed: the headline line without the figures that take work of their own, and --dump-outputs DIR holding the image
+    the timed path computed -- the one-GPU render, channel for channel.  --full brings the counter step, the roofline and one_shot back."""
+    import os
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    args = ["--gpus", "1", "--steps", "3", "--warmup", "1", "--workload", "cornell-box-400x300x16-d4"]
+    out, line = _run_bench(args + ["--dump-outputs", str(tmp_path / "dump")])
+    assert out.returncode == 0 and line, out.stderr[-2000:]
+    assert line["full"] is False and line["steps"] == 3 and line["ms_per_step"] > 0 and line["value"] > 0
+    assert "cpu_baseline" not in line and "one_shot" not in line and "kernel" not in line and line["roofline"]["kernel_ms_per_step"] > 0
+    rgb = np.load(tmp_path / "dump" / "image_rgb.npy")
+    host, device = native
+    sc = host.LoadedScene(os.path.join(root, "data/scenes/tungsten/cornell-box/scene.json"), 400, 300, 16, 4)
+    packed = device.render(sc, sc.camera, sc.settings, abi.Options.make())[0].astype(np.int64)
+    want = np.stack([(packed >> 16) & 255, (packed >> 8) & 255, packed & 255], axis=-1).astype(np.float32)
+    assert rgb.dtype == np.float32 and np.array_equal(rgb, want)
+    assert int(packed.sum()) == line["image_checksum"]
+    out, line = _run_bench(args + ["--full", "--cpu-seconds", "0"])
+    assert out.returncode == 0 and line, out.stderr[-2000:]
+    assert line["full"] is True and line["roofline"]["bound"] == "valu" and line["kernel"]["vgprs"] > 0 and "first_call_ms" in line["one_shot"]

@@ -5,7 +5,7 @@
 set -u
 OUT=${1:-gpurun_out/pmc}; WL=${2:-cornell-box-800x600x256-d30}
 mkdir -p "$OUT"; export TMPDIR=/tmp
-CMD="python3 bench.py --steps 2 --warmup 1 --cpu-seconds 0 --workload $WL"
+CMD="python3 bench.py --full --steps 2 --warmup 1 --cpu-seconds 0 --workload $WL"
 i=0
 for grp in "FETCH_SIZE" "WRITE_SIZE" "SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_SMEM SQ_INSTS_LDS" \
            "SQ_ACTIVE_INST_VALU SQ_THREAD_CYCLES_VALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES" \
