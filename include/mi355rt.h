@@ -34,8 +34,9 @@
 extern "C" {
 #endif
 
-#define MI355RT_ABI_VERSION 4u   /* 2: mi355rt_scene.textures, MI355RT_MAT_TEXTURE; 3: mi355rt_context_check exported, quads must carry a (near-)unit normal;
-                                    4: mi355rt_context_set_share exported; MI355RT_RNG_CTR draws from pcg4d (other numbers than versions 1-3, same distribution) */
+#define MI355RT_ABI_VERSION 5u   /* 2: mi355rt_scene.textures, MI355RT_MAT_TEXTURE; 3: mi355rt_context_check exported, quads must carry a (near-)unit normal;
+                                    4: mi355rt_context_set_share exported; MI355RT_RNG_CTR draws from pcg4d (other numbers than versions 1-3, same distribution);
+                                    5: mi355rt_multi_context_* exported.  No struct changed in 5: options.abi_version 4 is still accepted. */
 
 /* ---- error codes ------------------------------------------------------------------------- */
 #define MI355RT_OK               0
@@ -281,6 +282,36 @@ int  mi355rt_render_multi(const mi355rt_scene* scene, const mi355rt_camera* came
                           const mi355rt_settings* settings, const mi355rt_options* options_or_null,
                           const int* hip_devices, uint32_t n_devices,
                           uint32_t* out_packed_rgb, float* out_linear_rgb_or_null, mi355rt_stats* stats_or_null);
+
+/* ---- resident multi-device form: one process, several GPUs, scene and buffers kept across calls ----------------------------
+ * What mi355rt_render_multi does in one call, split into a context that stays: every entry of `hip_devices` is one PART with its own
+ * mi355rt_context, a non-blocking stream, a staging buffer for its rows and a done-event; hip_devices[0] is the DESTINATION device, on
+ * which both outputs live.  A device may be listed more than once (each entry is still its own part: how a one-GPU machine tests this).
+ * Strips of options.strip_rows rows (0 -> 4) are dealt round-robin over the parts; options.n_parts / part must be left 0 (or n_parts 1);
+ * row_begin / row_end select a window (the outputs then hold only those rows); rng_mode, seed, flags and workspace_bytes pass through to
+ * every part.  The image is bit-identical, packed and linear, to mi355rt_context_render of the same window on one device.
+ * Every entry point leaves the calling thread's current HIP device as it found it.                                                  */
+typedef struct mi355rt_multi_context mi355rt_multi_context;
+
+int  mi355rt_multi_context_create(const int* hip_devices, uint32_t n_devices, mi355rt_multi_context** out);
+/* Waits for every render enqueued on the context, then frees it.  Peer access enabled by create stays enabled (process-wide state). */
+void mi355rt_multi_context_destroy(mi355rt_multi_context* m);
+/* BLOCKING: uploads the scene to every part at once (one host thread per part; a part whose thread cannot be started is uploaded on the
+ * calling thread).  May be called again to change scene, camera or settings.                                                         */
+int  mi355rt_multi_context_set_scene(mi355rt_multi_context* m, const mi355rt_scene* scene,
+                                     const mi355rt_camera* camera, const mi355rt_settings* settings);
+/* Outputs are DEVICE pointers on hip_devices[0]; `hip_stream` is a hipStream_t of hip_devices[0] or NULL (its default stream).  Every part
+ * renders its strips on its own stream after the work already enqueued on `hip_stream`; the strips come back with one peer copy per part and
+ * output (copy engines, no CU slots) and one k_gather_strips launch puts every row in its place, all on `hip_stream`, which therefore orders
+ * the result.  With stats == NULL the call only enqueues.  With stats it waits, and fills: render / resolve kernel ms = the largest over the
+ * parts (HIP events of each part's own timeline), samples / rays / rows_rendered / bands = sums, total_ms = host wall time from entry to the
+ * end of the assembly (devices share no event timeline); grid_blocks, block_threads, kernel_vgprs, kernel_sgprs are 0.               */
+int  mi355rt_multi_context_render(mi355rt_multi_context* m, const mi355rt_options* options_or_null,
+                                  void* d_out_packed_rgb, void* d_out_linear_rgb_or_null,
+                                  void* hip_stream, mi355rt_stats* stats_or_null);
+/* Waits for every render enqueued so far and returns the first pending watchdog failure of a part (mi355rt_context_check), once, with
+ * the device named.  Every other multi-context call that finds such a failure pending returns it the same way.                      */
+int  mi355rt_multi_context_check(mi355rt_multi_context* m);
 
 /* One-shot progressive render with HOST buffers: mi355rt_render in chunks of `chunk_spp` samples.  After
  * every chunk `on_chunk_or_null(user, samples_done, samples_total, out_packed_rgb)` sees the image so far

@@ -1,6 +1,6 @@
 """Build recipes for the native libraries (in-tree, gfx950 only).
 
-  libmi355rt.so       hipcc: HIP kernels + the device half of the C ABI (csrc/device)
+  libmi355rt.so       hipcc: HIP kernels + the device half of the C ABI (csrc/device; rt_multi.cpp: the multi-device context)
   libmi355rt_host.so  g++:   CPU-side producers -- scene loader, mesh readers, BVH build, PNG (csrc/host)
   rt_render           g++:   CLI that stands in for the Rust `main` (csrc/tools)
 
@@ -32,7 +32,7 @@ HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off"
                "-Wno-unused-command-line-argument"]
 CXX_FLAGS = ["-O2", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-fPIC", "-Wall", "-pthread"]
 
-DEVICE_SRCS = [os.path.join(CSRC, "device", "rt_kernels.hip"), os.path.join(CSRC, "device", "rt_api.cpp")]
+DEVICE_SRCS = [os.path.join(CSRC, "device", "rt_kernels.hip"), os.path.join(CSRC, "device", "rt_api.cpp"), os.path.join(CSRC, "device", "rt_multi.cpp")]
 DEVICE_HEADERS = sorted(os.path.join(CSRC, "device", f) for f in os.listdir(os.path.join(CSRC, "device")) if f.endswith(".h"))
 DEVICE_DEPS = DEVICE_SRCS + DEVICE_HEADERS + [os.path.join(ROOT, "include", "mi355rt.h")]
 

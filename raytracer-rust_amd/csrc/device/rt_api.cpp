@@ -21,36 +21,24 @@
 
 #include "../../../include/mi355rt.h"
 #include "rt_device.h"
+#include "rt_host.h"
 
 using namespace mi355rt;
 
 namespace {
-
 thread_local std::string g_err;
+}  // namespace
+
+namespace mi355rt {
+
 int fail(int code, const std::string& msg) { g_err = msg; return code; }
 int fail_noexcept(int code, const char* msg) noexcept { try { g_err.assign(msg); } catch (...) { g_err.clear(); } return code; }
-// The exception barrier of every extern "C" entry point below (mi355rt.h: "nothing aborts, nothing throws across the ABI"; the caller may
-// be a Rust frame -- src/renderer.rs:67 is called from src/main.rs:57 -- into which a C++ exception must not unwind):
-// std::bad_alloc / std::length_error -> MI355RT_ERR_OOM, anything else -> MI355RT_ERR_HIP with what() in mi355rt_last_error().
-template <class F> int guard(F&& f) noexcept {
-    try { return f(); }
-    catch (const std::bad_alloc&) { return fail_noexcept(MI355RT_ERR_OOM, "host allocation failed (std::bad_alloc)"); }
-    catch (const std::length_error&) { return fail_noexcept(MI355RT_ERR_OOM, "host allocation failed (std::length_error)"); }
-    catch (const std::exception& e) {
-        try { return fail(MI355RT_ERR_HIP, std::string("unexpected C++ exception: ") + e.what()); } catch (...) { return fail_noexcept(MI355RT_ERR_HIP, "unexpected C++ exception"); }
-    }
-    catch (...) { return fail_noexcept(MI355RT_ERR_HIP, "unexpected C++ exception"); }
-}
-#define HIP_TRY(expr)                                                                              \
-    do { hipError_t e_ = (expr); if (e_ != hipSuccess) return fail(e_ == hipErrorOutOfMemory ? MI355RT_ERR_OOM : MI355RT_ERR_HIP, \
-         std::string(#expr) + ": " + hipGetErrorString(e_)); } while (0)
 
-struct RowSel { std::vector<uint32_t> rows; };
-
+// Options of ABI version 4 are accepted as well: version 5 added entry points (mi355rt_multi_context_*), no struct changed.
 int select_rows(const mi355rt_settings& st, const mi355rt_options* o, RowSel& sel) {
     uint32_t rb = 0, re = st.height, strip = 1, parts = 1, part = 0;
     if (o) {
-        if (o->abi_version != MI355RT_ABI_VERSION) return fail(MI355RT_ERR_INVALID, "options.abi_version mismatch");
+        if (o->abi_version != MI355RT_ABI_VERSION && o->abi_version != 4u) return fail(MI355RT_ERR_INVALID, "options.abi_version mismatch");
         rb = o->row_begin; re = o->row_end ? o->row_end : st.height;
         strip = o->strip_rows ? o->strip_rows : 1; parts = o->n_parts ? o->n_parts : 1; part = o->part;
         if (o->rng_mode != MI355RT_RNG_CTR && o->rng_mode != MI355RT_RNG_REF) return fail(MI355RT_ERR_INVALID, "options.rng_mode");
@@ -60,6 +48,19 @@ int select_rows(const mi355rt_settings& st, const mi355rt_options* o, RowSel& se
     for (uint32_t y = rb; y < re; ++y) if ((y / strip) % parts == part) sel.rows.push_back(y);
     return MI355RT_OK;
 }
+
+int check_settings(const mi355rt_settings* st) {
+    if (!st) return fail(MI355RT_ERR_INVALID, "settings is null");
+    if (st->width == 0 || st->height == 0 || st->samples_per_pixel == 0) return fail(MI355RT_ERR_INVALID, "width/height/spp must be > 0");
+    if ((uint64_t)st->width * st->height >= (1ull << 31)) return fail(MI355RT_ERR_INVALID, "image too large");
+    if (st->width >= (1u << 24) || st->height >= (1u << 24)) return fail(MI355RT_ERR_INVALID, "width/height must be < 2^24 (x as f32 is exact, renderer.rs:96)");
+    if (st->samples_per_pixel >= (1u << 30)) return fail(MI355RT_ERR_INVALID, "samples_per_pixel too large");
+    return MI355RT_OK;
+}
+
+}  // namespace mi355rt
+
+namespace {
 
 // The three row tables of one selection, n entries each: [0, n) natural = absolute y of local output row j; [n, 2n) processing = absolute y
 // of the row processed jp-th; [2n, 3n) out_row = the local output row that processing row jp is.  `cost` (per absolute image row, may be
@@ -84,15 +85,6 @@ void row_tables(const std::vector<uint32_t>& rows, const std::vector<float>& cos
     }
 }
 
-int check_settings(const mi355rt_settings* st) {
-    if (!st) return fail(MI355RT_ERR_INVALID, "settings is null");
-    if (st->width == 0 || st->height == 0 || st->samples_per_pixel == 0) return fail(MI355RT_ERR_INVALID, "width/height/spp must be > 0");
-    if ((uint64_t)st->width * st->height >= (1ull << 31)) return fail(MI355RT_ERR_INVALID, "image too large");
-    if (st->width >= (1u << 24) || st->height >= (1u << 24)) return fail(MI355RT_ERR_INVALID, "width/height must be < 2^24 (x as f32 is exact, renderer.rs:96)");
-    if (st->samples_per_pixel >= (1u << 30)) return fail(MI355RT_ERR_INVALID, "samples_per_pixel too large");
-    return MI355RT_OK;
-}
-
 // q = n / d for every n < 2^31 as umulhi(n, mul) >> shift (mul == 0 encodes d == 1).  s = ceil(log2 d),
 // mul = ceil(2^(31+s) / d) < 2^32, shift = s - 1.
 void magic_div(uint32_t d, uint32_t& mul, uint32_t& shift) {
@@ -101,19 +93,6 @@ void magic_div(uint32_t d, uint32_t& mul, uint32_t& shift) {
     const unsigned __int128 num = (unsigned __int128)1 << (31 + s);
     mul = (uint32_t)((num + d - 1) / d); shift = s - 1;
 }
-
-template <class T> struct DevBuf {
-    T* p = nullptr; size_t n = 0;
-    int ensure(size_t count) {
-        if (count <= n && p) return MI355RT_OK;
-        if (p) { (void)hipFree(p); p = nullptr; n = 0; }
-        if (count == 0) count = 1;
-        HIP_TRY(hipMalloc((void**)&p, count * sizeof(T)));
-        n = count;
-        return MI355RT_OK;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; n = 0; }
-};
 
 }  // namespace
 

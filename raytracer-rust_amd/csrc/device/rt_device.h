@@ -188,9 +188,21 @@ struct DebugHitOut { float p[3], n[3], t, material, front_face, hit, pad[2]; }; 
 int launch_debug_scatter(const DevMat* mats, const DevTexture* textures, const DebugScatterIn* in, DebugScatterOut* out, uint32_t n, void* stream);
 int launch_debug_hit(const DevPrim* prims, uint32_t n_prims, const DevNode* nodes, const DevTri* tris, const DebugHitIn* in, DebugHitOut* out, uint32_t n, void* stream);
 
+// The exchange of mi355rt_multi_context_render (rt_multi.cpp): every part's rows lie back to back in one staging area of the destination
+// device; output row r of each image is staging row src_row[r].  Both planes are copied as 32-bit words (the linear floats bit for bit).
+struct GatherParams {
+    const uint32_t* src_row;     // n_rows entries
+    const uint32_t* src_packed;  // staging, `width` words per row
+    uint32_t* dst_packed;        // output, `width` words per row
+    const uint32_t* src_linear;  // staging, 3 * `width` words per row; null together with dst_linear: no linear plane
+    uint32_t* dst_linear;
+    uint32_t n_rows, width;
+};
+
 // launchers (rt_kernels.hip); `stream` is a hipStream_t
 int launch_render_ctr(const RenderParams& p, uint32_t variant, uint32_t grid_blocks, void* stream);
 int launch_resolve(const ResolveParams& p, void* stream);
+int launch_gather_strips(const GatherParams& p, void* stream);
 int launch_render_ref(const RefParams& p, void* stream);
 int query_render_ctr_occupancy(uint32_t variant, int* blocks_per_cu, int* vgprs, int* sgprs);
 bool render_ctr_variant_built(uint32_t variant);   // false for the retired mesh kernels in the product library (they live in the tests' -DMI355RT_REFS build)

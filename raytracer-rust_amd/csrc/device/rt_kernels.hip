@@ -22,6 +22,7 @@
 //                  1/spp (:103), sqrt-gamma, clamp, pack 0x00RRGGBB (:112-120, color.rs:87-93).
 //   k_render_ref   validation mode: one lane per image row replays the reference's sequential
 //                  StdRng::seed_from_u64(y) stream (renderer.rs:91) and folds radiance tail-first.
+//   k_gather_strips  the multi-device exchange: de-interleaves the parts' strips into the image (rt_multi.cpp).
 //
 // Files (one translation unit; this file includes the rest): rt_math.h (vec3.rs helpers), rt_rng.h (pcg4d / Philox, ChaCha12 replay),
 // rt_intersect.h (hit tests, BVH walk, finish_hit), rt_materials.h (scatter, camera, miss colour), here: the work cursor,
@@ -593,6 +594,34 @@ __global__ void __launch_bounds__(64) k_render_ref(const RefParams P) {
 }
 
 // ===================================================================================================
+// k_gather_strips -- the exchange of mi355rt_multi_context_render (rt_multi.cpp): the parts' rows arrive (peer copies) back to back in
+// one staging area of the destination device, and output row r of the packed (width words) and linear (3 * width words) images is
+// staging row src_row[r].  A pure copy of a few MB: a workgroup takes one row at a time (grid-stride over rows), so the row, its table
+// entry (a scalar load) and the alignment test are uniform; a row whose source and destination both start on 16 bytes moves as dwordx4
+// (cdna_hip_programming Guideline 13) plus a tail of < 4 words, any other row (width not a multiple of 4) as dwords.
+// ===================================================================================================
+DI void gather_row(const uint32_t* __restrict__ src, uint32_t* __restrict__ dst, uint32_t n) {
+    if (((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15u) == 0u) {
+        const uint32_t nq = n >> 2;
+        const uint4* __restrict__ s4 = reinterpret_cast<const uint4*>(src);
+        uint4* __restrict__ d4 = reinterpret_cast<uint4*>(dst);
+        for (uint32_t i = threadIdx.x; i < nq; i += blockDim.x) d4[i] = s4[i];
+        const uint32_t t = (nq << 2) + threadIdx.x;
+        if (t < n) dst[t] = src[t];                                   // (threadIdx.x < 4 <= blockDim.x)
+    } else {
+        for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) dst[i] = src[i];
+    }
+}
+__global__ void __launch_bounds__(256) k_gather_strips(const GatherParams P) {
+    const __attribute__((address_space(4))) uint32_t* table = (const __attribute__((address_space(4))) uint32_t*)P.src_row;   // uniform reads -> s_load
+    for (uint32_t r = blockIdx.x; r < P.n_rows; r += gridDim.x) {
+        const size_t s = table[r];
+        gather_row(P.src_packed + s * P.width, P.dst_packed + (size_t)r * P.width, P.width);
+        if (P.dst_linear) gather_row(P.src_linear + s * 3u * P.width, P.dst_linear + (size_t)r * 3u * P.width, 3u * P.width);
+    }
+}
+
+// ===================================================================================================
 // Diagnostic kernels: one Material::scatter / one HittableList::hit per lane through the device functions above
 // (tests/test_kat_functions.py compares them with independent numpy float32 known answers).
 // ===================================================================================================
@@ -672,6 +701,12 @@ bool render_ctr_variant_built(uint32_t variant) {
 int launch_resolve(const ResolveParams& p, void* stream) {
     const uint32_t blocks = (p.band_pixels + 15u) / 16u;         // 4 waves x 4 pixels per block
     hipLaunchKernelGGL(k_resolve, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p);
+    return (int)hipGetLastError();
+}
+int launch_gather_strips(const GatherParams& p, void* stream) {
+    if (p.n_rows == 0) return 0;
+    const uint32_t blocks = p.n_rows < 2048u ? p.n_rows : 2048u;   // one row per workgroup at a time; more rows are strided over
+    hipLaunchKernelGGL(k_gather_strips, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p);
     return (int)hipGetLastError();
 }
 int launch_render_ref(const RefParams& p, void* stream) {

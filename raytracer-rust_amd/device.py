@@ -13,7 +13,9 @@ from . import abi, build
 
 EXPORTS = ["mi355rt_render", "mi355rt_render_multi", "mi355rt_render_progressive", "mi355rt_context_create", "mi355rt_context_destroy", "mi355rt_context_set_scene",
            "mi355rt_rows_selected", "mi355rt_context_render", "mi355rt_context_render_progressive", "mi355rt_context_set_timing", "mi355rt_context_read_timing",
-           "mi355rt_context_check", "mi355rt_context_set_share", "mi355rt_last_error", "mi355rt_abi_version"]
+           "mi355rt_context_check", "mi355rt_context_set_share", "mi355rt_last_error", "mi355rt_abi_version",
+           "mi355rt_multi_context_create", "mi355rt_multi_context_destroy", "mi355rt_multi_context_set_scene", "mi355rt_multi_context_render",
+           "mi355rt_multi_context_check"]
 
 _lib = None
 _extra = {}
@@ -74,6 +76,18 @@ def _bind(so):
         L.mi355rt_context_check.argtypes = [C.c_void_p]
         L.mi355rt_context_set_share.restype = C.c_int
         L.mi355rt_context_set_share.argtypes = [C.c_void_p, C.c_uint32]
+        L.mi355rt_multi_context_create.restype = C.c_int
+        L.mi355rt_multi_context_create.argtypes = [C.POINTER(C.c_int), C.c_uint32, C.POINTER(C.c_void_p)]
+        L.mi355rt_multi_context_destroy.restype = None
+        L.mi355rt_multi_context_destroy.argtypes = [C.c_void_p]
+        L.mi355rt_multi_context_set_scene.restype = C.c_int
+        L.mi355rt_multi_context_set_scene.argtypes = [C.c_void_p, C.POINTER(abi.Scene), C.POINTER(abi.Camera), C.POINTER(abi.Settings)]
+        L.mi355rt_multi_context_render.restype = C.c_int
+        L.mi355rt_multi_context_render.argtypes = [C.c_void_p, C.POINTER(abi.Options), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(abi.Stats)]
+        L.mi355rt_multi_context_check.restype = C.c_int
+        L.mi355rt_multi_context_check.argtypes = [C.c_void_p]
+        L.mi355rt_debug_multi_part_ms.restype = C.c_int
+        L.mi355rt_debug_multi_part_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_uint32, C.POINTER(C.c_uint32)]
         L.mi355rt_debug_set_knob.restype = C.c_int
         L.mi355rt_debug_set_knob.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
         L.mi355rt_debug_has_variant.restype = C.c_int
@@ -263,6 +277,77 @@ class Context:
     def close(self):
         if self._h:
             self._L.mi355rt_context_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class MultiContext:
+    """mi355rt_multi_context_*: one process drives the listed HIP devices (a device may repeat; every entry is one part with its own
+    context and stream) and keeps scene, staging buffers and row table across calls.  Outputs live on devices[0]."""
+
+    def __init__(self, devices, library=None):
+        self._L = library or lib()
+        self._h = C.c_void_p()
+        self.devices = [int(d) for d in devices]
+        devs = (C.c_int * max(len(self.devices), 1))(*self.devices)
+        _check(self._L.mi355rt_multi_context_create(devs, len(self.devices), C.byref(self._h)), "mi355rt_multi_context_create", self._L)
+        self.settings = None
+
+    def set_scene(self, scene, camera, settings):
+        sc = getattr(scene, "c", scene)
+        _check(self._L.mi355rt_multi_context_set_scene(self._h, C.byref(sc), C.byref(camera), C.byref(settings)),
+               "mi355rt_multi_context_set_scene", self._L)
+        self.settings = abi.Settings(settings.width, settings.height, settings.samples_per_pixel, settings.max_depth)
+
+    def rows_selected(self, options=None):
+        """Rows the outputs hold: the window of `options` (the strips are dealt over the parts, all of them land in the output)."""
+        if self.settings is None:
+            raise RuntimeError("MultiContext has no scene (set_scene)")
+        window = None
+        if options is not None:
+            window = abi.Options.make(row_begin=options.row_begin, row_end=options.row_end)
+        n = C.c_uint32()
+        _check(self._L.mi355rt_rows_selected(C.byref(self.settings), C.byref(window) if window is not None else None, C.byref(n)),
+               "mi355rt_rows_selected", self._L)
+        return n.value
+
+    def render(self, out_packed, out_linear=None, options=None, stream=None, want_stats=False):
+        """out_packed: uint32/int32 device tensor on devices[0] with >= rows * width elements; out_linear: float32 tensor with
+        >= rows * width * 3 elements, or None; stream: a torch stream of devices[0] (or a raw hipStream_t), None = its default stream.
+        Without want_stats the call only enqueues (the stream orders the result); with it, it waits and returns abi.Stats."""
+        if self.settings is not None:
+            need = self.rows_selected(options) * self.settings.width
+            for t, k, name in ((out_packed, 1, "out_packed"), (out_linear, 3, "out_linear")):
+                if t is not None and t.numel() < need * k:
+                    raise ValueError(f"{name} holds {t.numel()} elements, the selected rows need {need * k}")
+        stats = abi.Stats() if want_stats else None
+        s = getattr(stream, "cuda_stream", stream)
+        _check(self._L.mi355rt_multi_context_render(self._h, C.byref(options) if options is not None else None,
+                                                    C.c_void_p(out_packed.data_ptr()) if out_packed is not None else None,
+                                                    C.c_void_p(out_linear.data_ptr()) if out_linear is not None else None,
+                                                    C.c_void_p(s) if s else None, C.byref(stats) if want_stats else None),
+               "mi355rt_multi_context_render", self._L)
+        return stats
+
+    def check(self):
+        """mi355rt_multi_context_check: waits for every render enqueued so far and raises if a part left its strips incomplete."""
+        _check(self._L.mi355rt_multi_context_check(self._h), "mi355rt_multi_context_check", self._L)
+
+    def part_kernel_ms(self):
+        """Diagnostic: render + resolve kernel ms of every part in the last render given want_stats."""
+        n = C.c_uint32()
+        out = (C.c_double * max(len(self.devices), 1))()
+        _check(self._L.mi355rt_debug_multi_part_ms(self._h, out, len(out), C.byref(n)), "mi355rt_debug_multi_part_ms", self._L)
+        return list(out)[:n.value]
+
+    def close(self):
+        if self._h:
+            self._L.mi355rt_multi_context_destroy(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):
