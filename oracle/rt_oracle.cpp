@@ -24,8 +24,9 @@
 //   REF: one ChaCha12 stream per image row, consumed sequentially by every pixel and sample of the
 //        row (renderer.rs:91-101).  Radiance folded tail-first exactly like the recursion.
 //   CTR: the GPU-native mode.  Same algorithm, but every draw is a pure function of
-//        (row y + seed; x, sample, ray index, block) through Philox4x32-10, and the path
-//        throughput is accumulated front-to-back.  Draw slots:
+//        (row y + seed; x, sample, ray index, block) through the counter generator the product
+//        ships (pcg4d; see ctr_block below), and the path throughput is accumulated
+//        front-to-back.  Draw slots:
 //          camera jitter   : ray 0, block 0, words 0 (u) and 1 (v)
 //          scatter after ray r (r = 0 is the camera ray): ray r+1,
 //              random::<f32>() number k of the event (k = 0,1) -> block 0, word k

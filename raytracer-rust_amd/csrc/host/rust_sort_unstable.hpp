@@ -15,8 +15,8 @@
 //   the ancestor pivot partitions by <=; partition = swap pivot to front, cyclic Lomuto over the rest, swap pivot to num_lt;
 //   heapsort when the limit runs out.
 // Evidence that the restatement is the reference's sort: with it the oracle's replay of the reference stream matches the
-// reference's own committed render docs/semesterbild.png with NO pixel further than 20/255 and 77.7 % of the pixels exact (79.4 % with the f32 quaternion of xform.hpp)
-// (std::stable_sort: 0.15 % of the pixels > 20 -- whole letter faces -- and 60.5 % exact); tests/test_oracle_golden.py.
+// reference's own committed render docs/semesterbild.png bit for bit, all 480 000 pixels, and so does the HIP path's (std::stable_sort
+// instead: whole letter faces differ); tests/test_oracle_golden.py, tests/test_gpu_fullsize.py.
 #pragma once
 #include <cstddef>
 #include <cstdint>

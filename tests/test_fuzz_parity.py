@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 
 from fuzz_scenes import random_scene
+from parity import assert_parity
 
 
 def _kinds_present(sc):
@@ -47,9 +48,9 @@ def test_hip_matches_oracle_on_fuzz_scenes_with_rough_conductors(seed, native, o
     opt = abi.Options.make()
     gp, gl, stats = device.render(sc, sc.camera, st, opt)
     op, ol, cnt = oracle_mod.render(sc, sc.camera, st, opt)
-    l2 = np.sqrt(((gl.astype(np.float64) - ol) ** 2).sum(-1))
-    assert (l2 <= 1e-3).mean() >= 0.995 and (gp == op).mean() >= 0.99
-    assert abs(stats.rays - cnt.rays) <= 0.001 * cnt.rays
+    # measured: equal ray counts on all three scenes (profiles/fullsize_parity.txt); 1e-6, the full-size bound, allows no difference
+    # below 1 M rays -- these scenes trace 25 k ... 103 k
+    assert_parity(gp, gl, op, ol, exact=False, gpu_rays=stats.rays, oracle_rays=cnt.rays, ray_rel=1e-6)
 
 
 @pytest.mark.gpu

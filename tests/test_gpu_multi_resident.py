@@ -156,3 +156,18 @@ def test_multi_context_argument_checks(native, abi):
         m.check()
     finally:
         m.close()
+
+
+def test_eight_parts_at_the_headline_frame(native, abi):
+    """The frame the bench times (cornell 800x600x256 d30) on 8 parts with the default strips: rows of 800 packed and 2400 linear words
+    take k_gather_strips' dwordx4 path from 8 staging areas, and the image must be the one-device image bit for bit, with its rays."""
+    host, device = native
+    sc = _scene(host, "cornell", 800, 600, spp=256, depth=30)
+    m = device.MultiContext([0] * 8)
+    try:
+        m.set_scene(sc, sc.camera, sc.settings)
+        st = _render_and_compare(m, device, abi, sc, {"strip_rows": 0})             # 0: the default strips of 4 rows
+        assert st.samples == 800 * 600 * 256 and st.rows_rendered == 600
+        m.check()
+    finally:
+        m.close()

@@ -1,15 +1,16 @@
 """GPU parity: HIP path (through the C ABI) vs the CPU oracle on identical inputs, same RNG mode.
 
-Tolerances (restated in DESIGN.md):
+Tolerances (restated in DESIGN.md section 5; tests/parity.py asserts them):
   * scenes whose path uses only + - * / sqrt (cornell, teapot): linear RGB must be BIT-IDENTICAL;
   * scenes with RoughConductor (logf/atanf/sinf/cosf: device libm differs from glibc by ulps, which can
-    flip a branch for isolated samples): per-pixel L2 <= 1e-3 on >= 99.5 % of pixels and >= 99 % of
-    8-bit pixels identical.
+    flip a branch for isolated samples): at most ceil(1e-4 N) of the N pixels with per-pixel L2 > 1e-3,
+    at most ceil(1e-3 N) 8-bit pixels that differ, image means within 2e-3.
 """
 import numpy as np
 import pytest
 
 from conftest import load_for_both
+from parity import assert_parity
 
 pytestmark = pytest.mark.gpu
 
@@ -23,16 +24,7 @@ CASES = [  # name, W, H, spp, depth, exact
 
 
 def _compare(gl, ol, gp, op, exact):
-    assert gl.shape == ol.shape
-    if exact:
-        assert np.array_equal(gl.view(np.uint32), ol.view(np.uint32)), \
-            f"linear not bit-identical: max|d|={np.abs(gl - ol).max()}, differing px={(np.abs(gl - ol).max(-1) > 0).sum()}"
-        assert np.array_equal(gp, op)
-    else:
-        l2 = np.sqrt(((gl.astype(np.float64) - ol) ** 2).sum(-1))
-        assert (l2 <= 1e-3).mean() >= 0.995, f"L2 outliers: {(l2 > 1e-3).mean():.4f}, max {l2.max()}"
-        assert (gp == op).mean() >= 0.99
-        assert abs(gl.mean() - ol.mean()) <= 2e-3 * max(ol.mean(), 1e-6)
+    assert_parity(gp, gl, op, ol, exact=exact)
 
 
 @pytest.mark.parametrize("name,W,H,spp,depth,exact", CASES)
@@ -259,8 +251,7 @@ def test_texture_material_scene_matches_the_oracle(native, oracle_mod, abi):
     st = abi.Settings(96, 72, 16, 6)
     gp, gl, gs = device.render(sc, cam, st, abi.Options.make())
     op, ol, cnt = oracle_mod.render(sc, cam, st, abi.Options.make())
-    d = np.sqrt(((gl.astype(np.float64) - ol) ** 2).sum(-1))
-    assert (d <= 1e-3).mean() >= 0.995 and (gp == op).mean() >= 0.99 and gs.rays == cnt.rays
+    assert_parity(gp, gl, op, ol, exact=False, gpu_rays=gs.rays, oracle_rays=cnt.rays)
     # refused: a texture index beyond the table
     mats[1].texture = 5
     with pytest.raises(device.RenderError):
