@@ -36,7 +36,9 @@ extern "C" {
 
 #define MI355RT_ABI_VERSION 5u   /* 2: mi355rt_scene.textures, MI355RT_MAT_TEXTURE; 3: mi355rt_context_check exported, quads must carry a (near-)unit normal;
                                     4: mi355rt_context_set_share exported; MI355RT_RNG_CTR draws from pcg4d (other numbers than versions 1-3, same distribution);
-                                    5: mi355rt_multi_context_* exported.  No struct changed in 5: options.abi_version 4 is still accepted. */
+                                    5: mi355rt_multi_context_* exported.  No struct changed in 5: options.abi_version 4 is still accepted.
+                                    Added within version 5 (no struct changed, the number stays): mi355rt_multi_context_render_progressive and
+                                    mi355rt_render_progressive_multi -- a caller that needs them probes for the symbols (dlsym), not the number. */
 
 /* ---- error codes ------------------------------------------------------------------------- */
 #define MI355RT_OK               0
@@ -313,6 +315,36 @@ int  mi355rt_multi_context_render(mi355rt_multi_context* m, const mi355rt_option
  * the device named.  Every other multi-context call that finds such a failure pending returns it the same way.                      */
 int  mi355rt_multi_context_check(mi355rt_multi_context* m);
 
+/* Progressive rendering on the resident multi-device context (added within ABI version 5: probe for the symbol): what
+ * mi355rt_context_render_progressive is on one device.  Samples [sample_begin, sample_end) of every selected pixel are traced and added,
+ * in sample order, to running sums; the outputs (DEVICE pointers on hip_devices[0], the selected rows, as in mi355rt_multi_context_render)
+ * hold the image of the first `sample_end` samples, packed, and linear when asked for.  Bit-identical to mi355rt_context_render_progressive
+ * fed the same chunks on one device, and so to mi355rt_context_render at samples_per_pixel = the sum (settings.samples_per_pixel is not
+ * consulted).
+ *   - Where the sums live: every PART owns them -- a float4 per pixel of its own strips, on its own device, allocated on first use and only
+ *     grown.  They never cross a device link between chunks, and they are separate from the workspaces: a plain
+ *     mi355rt_multi_context_render between two chunks leaves the sequence intact.
+ *   - A SEQUENCE starts with sample_begin == 0.  sample_begin > 0 continues it and must equal the sample_end of the last progressive call on
+ *     this context, with the same row selection (row_begin, row_end, strip_rows), rng_mode, seed and flags; any other call returns
+ *     MI355RT_ERR_INVALID saying why.  A call refused by these checks or by its argument checks changes nothing.
+ *   - What ends a sequence (the only valid next call then starts at 0): mi355rt_multi_context_set_scene; a progressive call that fails after
+ *     its checks, a pending part watchdog failure that it reports included; a mi355rt_multi_context_check that reports a failure; a
+ *     mi355rt_multi_context_render that returns MI355RT_ERR_HIP (the failure it reports may be an earlier chunk's).
+ *   - d_accum_or_null (on hip_devices[0]; WRITTEN, never read): when given, it receives the gathered sums of the selected rows in the layout
+ *     of mi355rt_context_render_progressive's d_accum (4 floats per pixel, row-major), bit-identical to what that call leaves there after the
+ *     same chunks -- to checkpoint them or to hand them to a single-device context.
+ *   - Stream protocol: that of mi355rt_multi_context_render.  Every part runs mi355rt_context_render_progressive on its own stream into its
+ *     own sums; the sums, when asked for, go peer-to-peer straight from every part's sums to a staging area on hip_devices[0] (one more peer
+ *     copy per part) and one k_gather_accum launch puts their rows in place.  Without stats the call only enqueues; with stats it waits once
+ *     and fills the fields of mi355rt_multi_context_render (samples = rows * width * (sample_end - sample_begin)).
+ *   - MI355RT_RNG_CTR only (MI355RT_RNG_REF -> MI355RT_ERR_INVALID); options.n_parts / part must be left 0.  Every entry point leaves the
+ *     calling thread's current HIP device as it found it.                                                                                */
+int  mi355rt_multi_context_render_progressive(mi355rt_multi_context* m, const mi355rt_options* options_or_null,
+                                              uint32_t sample_begin, uint32_t sample_end,
+                                              void* d_accum_or_null,
+                                              void* d_out_packed_rgb, void* d_out_linear_rgb_or_null,
+                                              void* hip_stream, mi355rt_stats* stats_or_null);
+
 /* One-shot progressive render with HOST buffers: mi355rt_render in chunks of `chunk_spp` samples.  After
  * every chunk `on_chunk_or_null(user, samples_done, samples_total, out_packed_rgb)` sees the image so far
  * (what the reference's preview window, src/main.rs:60-75, would show); a non-zero return stops early and
@@ -322,6 +354,16 @@ int  mi355rt_render_progressive(const mi355rt_scene* scene, const mi355rt_camera
                                 const mi355rt_settings* settings, const mi355rt_options* options_or_null,
                                 uint32_t chunk_spp, mi355rt_progress_fn on_chunk_or_null, void* user,
                                 uint32_t* out_packed_rgb, float* out_linear_rgb_or_null, mi355rt_stats* stats_or_null);
+/* Its multi-device twin (added within ABI version 5: probe for the symbol), built on mi355rt_multi_context_render_progressive: strips dealt
+ * over `hip_devices` as in mi355rt_render_multi (options.n_parts / part left 0), chunks of `chunk_spp` samples, the last one possibly
+ * shorter.  After every chunk the packed image comes back to out_packed_rgb and on_chunk_or_null sees it; a non-zero return stops early
+ * and leaves the image of `samples_done` samples in the outputs.  The final image equals mi355rt_render's and mi355rt_render_multi's.
+ * stats: kernel ms summed over the chunks, samples / rays summed, rows_rendered of one chunk.                                          */
+int  mi355rt_render_progressive_multi(const mi355rt_scene* scene, const mi355rt_camera* camera,
+                                      const mi355rt_settings* settings, const mi355rt_options* options_or_null,
+                                      const int* hip_devices, uint32_t n_devices,
+                                      uint32_t chunk_spp, mi355rt_progress_fn on_chunk_or_null, void* user,
+                                      uint32_t* out_packed_rgb, float* out_linear_rgb_or_null, mi355rt_stats* stats_or_null);
 
 /* Kernel timing without extra synchronisation: while enabled, every mi355rt_context_render call that
  * passes stats == NULL records HIP events around its kernels on the caller's stream.  After the

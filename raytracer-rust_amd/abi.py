@@ -82,6 +82,10 @@ class Stats(C.Structure):
                 ("grid_blocks", u32), ("block_threads", u32), ("kernel_vgprs", u32), ("kernel_sgprs", u32)]
 
 
+# mi355rt_progress_fn: int (*)(void* user, uint32_t samples_done, uint32_t samples_total, const uint32_t* packed_rgb)
+ProgressFn = C.CFUNCTYPE(C.c_int, C.c_void_p, u32, u32, C.POINTER(u32))
+
+
 class LoadOverrides(C.Structure):
     _fields_ = [("width", u32), ("height", u32), ("samples_per_pixel", u32), ("max_depth", u32),
                 ("skip_unknown_primitives", u32), ("wo3_four_index_stride", u32)]

@@ -199,10 +199,21 @@ struct GatherParams {
     uint32_t n_rows, width;
 };
 
+// The sums of mi355rt_multi_context_render_progressive (rt_multi.cpp): every part's running sums (a float4 per pixel of its rows) arrive
+// back to back in one staging area of the destination device, in the order of GatherParams' staging; output row r of the caller's sums is
+// staging row src_row[r] (the same table).  Rows are 16 * width bytes, so both sides start every row on 16 bytes.
+struct GatherAccumParams {
+    const uint32_t* src_row;     // n_rows entries
+    const uint32_t* src;         // staging, 4 * `width` words per row (the floats moved as 16-byte words, bit for bit)
+    uint32_t* dst;               // the caller's sums, 4 * `width` words per row
+    uint32_t n_rows, width;
+};
+
 // launchers (rt_kernels.hip); `stream` is a hipStream_t
 int launch_render_ctr(const RenderParams& p, uint32_t variant, uint32_t grid_blocks, void* stream);
 int launch_resolve(const ResolveParams& p, void* stream);
 int launch_gather_strips(const GatherParams& p, void* stream);
+int launch_gather_accum(const GatherAccumParams& p, void* stream);
 int launch_render_ref(const RefParams& p, void* stream);
 int query_render_ctr_occupancy(uint32_t variant, int* blocks_per_cu, int* vgprs, int* sgprs);
 bool render_ctr_variant_built(uint32_t variant);   // false for the retired mesh kernels in the product library (they live in the tests' -DMI355RT_REFS build)

@@ -23,6 +23,7 @@
 //   k_render_ref   validation mode: one lane per image row replays the reference's sequential
 //                  StdRng::seed_from_u64(y) stream (renderer.rs:91) and folds radiance tail-first.
 //   k_gather_strips  the multi-device exchange: de-interleaves the parts' strips into the image (rt_multi.cpp).
+//   k_gather_accum   the same for the parts' running sums of a progressive multi-device render (rt_multi.cpp).
 //
 // Files (one translation unit; this file includes the rest): rt_math.h (vec3.rs helpers), rt_rng.h (pcg4d / Philox, ChaCha12 replay),
 // rt_intersect.h (hit tests, BVH walk, finish_hit), rt_materials.h (scatter, camera, miss colour), here: the work cursor,
@@ -621,6 +622,22 @@ __global__ void __launch_bounds__(256) k_gather_strips(const GatherParams P) {
     }
 }
 
+// k_gather_accum -- the running sums of mi355rt_multi_context_render_progressive (rt_multi.cpp), assembled like the images above: every
+// part's float4 sums arrive (peer copies) back to back in a staging area of the destination device, and output row r is staging row
+// src_row[r] (k_gather_strips' table).  A row is `width` float4 = 16 * width bytes, so every row of either side starts on 16 bytes (both
+// buffers are 16-byte aligned, the caller's as in mi355rt_context_render_progressive): dwordx4 loads and stores only, no tail.  A workgroup
+// takes one row at a time (grid-stride), the table entry is a uniform scalar load.
+__global__ void __launch_bounds__(256) k_gather_accum(const GatherAccumParams P) {
+    const __attribute__((address_space(4))) uint32_t* table = (const __attribute__((address_space(4))) uint32_t*)P.src_row;   // uniform reads -> s_load
+    const uint4* __restrict__ src = reinterpret_cast<const uint4*>(P.src);
+    uint4* __restrict__ dst = reinterpret_cast<uint4*>(P.dst);
+    for (uint32_t r = blockIdx.x; r < P.n_rows; r += gridDim.x) {
+        const uint4* __restrict__ s4 = src + (size_t)table[r] * P.width;
+        uint4* __restrict__ d4 = dst + (size_t)r * P.width;
+        for (uint32_t i = threadIdx.x; i < P.width; i += blockDim.x) d4[i] = s4[i];
+    }
+}
+
 // ===================================================================================================
 // Diagnostic kernels: one Material::scatter / one HittableList::hit per lane through the device functions above
 // (tests/test_kat_functions.py compares them with independent numpy float32 known answers).
@@ -707,6 +724,12 @@ int launch_gather_strips(const GatherParams& p, void* stream) {
     if (p.n_rows == 0) return 0;
     const uint32_t blocks = p.n_rows < 2048u ? p.n_rows : 2048u;   // one row per workgroup at a time; more rows are strided over
     hipLaunchKernelGGL(k_gather_strips, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p);
+    return (int)hipGetLastError();
+}
+int launch_gather_accum(const GatherAccumParams& p, void* stream) {
+    if (p.n_rows == 0) return 0;
+    const uint32_t blocks = p.n_rows < 2048u ? p.n_rows : 2048u;   // as launch_gather_strips
+    hipLaunchKernelGGL(k_gather_accum, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p);
     return (int)hipGetLastError();
 }
 int launch_render_ref(const RefParams& p, void* stream) {

@@ -15,7 +15,7 @@ EXPORTS = ["mi355rt_render", "mi355rt_render_multi", "mi355rt_render_progressive
            "mi355rt_rows_selected", "mi355rt_context_render", "mi355rt_context_render_progressive", "mi355rt_context_set_timing", "mi355rt_context_read_timing",
            "mi355rt_context_check", "mi355rt_context_set_share", "mi355rt_last_error", "mi355rt_abi_version",
            "mi355rt_multi_context_create", "mi355rt_multi_context_destroy", "mi355rt_multi_context_set_scene", "mi355rt_multi_context_render",
-           "mi355rt_multi_context_check"]
+           "mi355rt_multi_context_check", "mi355rt_multi_context_render_progressive", "mi355rt_render_progressive_multi"]
 
 _lib = None
 _extra = {}
@@ -86,6 +86,13 @@ def _bind(so):
         L.mi355rt_multi_context_render.argtypes = [C.c_void_p, C.POINTER(abi.Options), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(abi.Stats)]
         L.mi355rt_multi_context_check.restype = C.c_int
         L.mi355rt_multi_context_check.argtypes = [C.c_void_p]
+        L.mi355rt_multi_context_render_progressive.restype = C.c_int
+        L.mi355rt_multi_context_render_progressive.argtypes = [C.c_void_p, C.POINTER(abi.Options), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                                               C.c_void_p, C.c_void_p, C.POINTER(abi.Stats)]
+        L.mi355rt_render_progressive_multi.restype = C.c_int
+        L.mi355rt_render_progressive_multi.argtypes = [C.POINTER(abi.Scene), C.POINTER(abi.Camera), C.POINTER(abi.Settings), C.POINTER(abi.Options),
+                                                       C.POINTER(C.c_int), C.c_uint32, C.c_uint32, abi.ProgressFn, C.c_void_p,
+                                                       C.c_void_p, C.c_void_p, C.POINTER(abi.Stats)]
         L.mi355rt_debug_multi_part_ms.restype = C.c_int
         L.mi355rt_debug_multi_part_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_uint32, C.POINTER(C.c_uint32)]
         L.mi355rt_debug_set_knob.restype = C.c_int
@@ -149,6 +156,37 @@ def render_multi(scene, camera, settings, devices, options=None, want_linear=Tru
     _check(L.mi355rt_render_multi(C.byref(sc), C.byref(camera), C.byref(settings), C.byref(options) if options is not None else None,
                                   devs, len(devices), packed.ctypes.data, linear.ctypes.data if want_linear else None, C.byref(stats)),
            "mi355rt_render_multi", L)
+    return packed, linear, stats
+
+
+def render_progressive_multi(scene, camera, settings, devices, chunk_spp, on_chunk=None, options=None, want_linear=True, library=None):
+    """mi355rt_render_progressive_multi: mi355rt_render_multi in chunks of `chunk_spp` samples (the last one may be shorter).  After every
+    chunk `on_chunk(samples_done, samples_total, packed)` sees the image so far (packed: uint32 [rows, W], a view of the result buffer that
+    the next chunk overwrites -- copy it to keep it); a truthy return stops early and leaves the image of `samples_done` samples.
+    Same returns as render_multi()."""
+    sc = getattr(scene, "c", scene)
+    rows = len(abi.rows_selected(settings.height, options)) if options is not None else settings.height
+    packed = np.zeros((rows, settings.width), np.uint32)
+    linear = np.zeros((rows, settings.width, 3), np.float32) if want_linear else None
+    stats = abi.Stats()
+    devs = (C.c_int * max(len(devices), 1))(*devices)
+    raised = []
+
+    def _cb(user, done, total, _ptr):
+        try:
+            return 1 if on_chunk(int(done), int(total), packed) else 0
+        except BaseException as e:                                         # never unwind through the C frames: stop, re-raise below
+            raised.append(e)
+            return 1
+
+    cb = abi.ProgressFn(_cb) if on_chunk is not None else abi.ProgressFn()
+    L = library or lib()
+    rc = L.mi355rt_render_progressive_multi(C.byref(sc), C.byref(camera), C.byref(settings), C.byref(options) if options is not None else None,
+                                            devs, len(devices), int(chunk_spp), cb, None, packed.ctypes.data,
+                                            linear.ctypes.data if want_linear else None, C.byref(stats))
+    if raised:
+        raise raised[0]
+    _check(rc, "mi355rt_render_progressive_multi", L)
     return packed, linear, stats
 
 
@@ -332,6 +370,30 @@ class MultiContext:
                                                     C.c_void_p(out_linear.data_ptr()) if out_linear is not None else None,
                                                     C.c_void_p(s) if s else None, C.byref(stats) if want_stats else None),
                "mi355rt_multi_context_render", self._L)
+        return stats
+
+    def render_progressive(self, sample_begin, sample_end, out_packed, out_linear=None, accum=None, options=None, stream=None, want_stats=False):
+        """mi355rt_multi_context_render_progressive: samples [sample_begin, sample_end) added to every part's running sums (kept on the
+        parts); the outputs then hold the image of the first sample_end samples.  sample_begin 0 starts a sequence, anything else must
+        continue the last chunk with the same rows, rng_mode, seed and flags.  Tensors as in render(); accum: float32 device tensor on
+        devices[0] with >= rows * width * 4 elements that receives the gathered sums (the layout of Context.render_progressive's d_accum),
+        or None."""
+        if self.settings is not None:
+            need = self.rows_selected(options) * self.settings.width
+            for t, k, name in ((out_packed, 1, "out_packed"), (out_linear, 3, "out_linear"), (accum, 4, "accum")):
+                if t is not None and t.numel() < need * k:
+                    raise ValueError(f"{name} holds {t.numel()} elements, the selected rows need {need * k}")
+            if accum is not None and accum.data_ptr() % 16:
+                raise ValueError("accum must start on 16 bytes (float4 per pixel)")
+        stats = abi.Stats() if want_stats else None
+        s = getattr(stream, "cuda_stream", stream)
+        _check(self._L.mi355rt_multi_context_render_progressive(self._h, C.byref(options) if options is not None else None,
+                                                                int(sample_begin), int(sample_end),
+                                                                C.c_void_p(accum.data_ptr()) if accum is not None else None,
+                                                                C.c_void_p(out_packed.data_ptr()) if out_packed is not None else None,
+                                                                C.c_void_p(out_linear.data_ptr()) if out_linear is not None else None,
+                                                                C.c_void_p(s) if s else None, C.byref(stats) if want_stats else None),
+               "mi355rt_multi_context_render_progressive", self._L)
         return stats
 
     def check(self):
