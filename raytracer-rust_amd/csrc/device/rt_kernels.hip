@@ -16,7 +16,8 @@
 //                  rt_rng.h) addressed by (image row key; x, sample, ray index, block): every draw is a pure function of
 //                  the path, so any schedule / tiling / GPU count produces bit-identical radiance.
 //                  Round 5: a wave keeps the camera rays of its next 64 samples IN STOCK (RayStock, LDS) and the mesh-free kernels
-//                  are instantiated per material set AND per primitive-kind set (k_render_ctr_simple_qc).
+//                  are instantiated per material set AND per primitive-kind set (k_render_ctr_simple_qc).  k_render_ctr_simple_qc
+//                  stocks the camera rays' first hits instead (HitStock), walked in refill passes of the loop.
 //                  Output: three floats of radiance per path into the HBM workspace.
 //   k_resolve      per pixel, sums its spp radiance values IN SAMPLE ORDER (renderer.rs:100), scales by
 //                  1/spp (:103), sqrt-gamma, clamp, pack 0x00RRGGBB (:112-120, color.rs:87-93).
@@ -140,6 +141,25 @@ struct WorkCursorT {
         }
         return got;
     }
+    // The same for a kernel that keeps camera-ray FIRST HITS in stock (HitStock below): a ring of up to 64 ready entries, [ring_head, +ring_count) mod 64.
+    // The refill pass walks the camera rays of the next samples of the run and appends the paths that go on; the deal hands out entries only.
+    uint32_t ring_head = 0, ring_count = 0;
+    // Wave-uniform: how many camera rays the refill pass walks now -- 0 while the ring holds LOW entries or more, or when no work is left.
+    template <uint32_t LOW>
+    DI uint32_t refill_size(const RenderParams& P, uint32_t lane) {
+        if (ring_count >= LOW) return 0u;
+        claim(P, lane);                                      // (no atomic while the run lasts)
+        return min(64u - ring_count, end - next);
+    }
+    // Lanes with want == true get the ring slot of an entry (returns true); the others / surplus stay idle.
+    DI bool deal_ring(bool want, uint32_t& slot) {
+        const uint64_t idle = __ballot(want);
+        const uint32_t take = min((uint32_t)__popcll(idle), ring_count);
+        const uint32_t rank = mbcnt64(idle);
+        slot = (ring_head + rank) & 63u;
+        ring_head = (ring_head + take) & 63u; ring_count -= take;
+        return want && rank < take;
+    }
 };
 typedef WorkCursorT<BATCH_MIN, BATCH_MAX> WorkCursor;                    // lockstep kernels (and the reference build's mesh kernels)
 typedef WorkCursorT<RUN_WAVEFRONT_MIN, RUN_WAVEFRONT> WorkCursorWf;          // wavefront kernel: fixed, aligned runs (rt_device.h)
@@ -198,6 +218,63 @@ struct RayStock {
         else start_path(P, sidx, ps.rng, ps.px, ps.py);                                          // (the Philox builds address by (key, x, s): nothing to keep)
     }
 };
+// Camera-ray FIRST HITS in stock (k_render_ctr_simple_qc).  With RayStock a freshly dealt lane still spends one whole iteration on the camera ray: the
+// second half of the iteration in which it is dealt (generator, cooperative unit-ball rounds, normalisations: about half of an iteration) only copies
+// the stocked direction, and scatters the first hit one iteration later -- 11 of 61 live lanes, in 94 % of the iterations, do no shading work.
+// Here the camera rays go through the loop's one walk site in a REFILL PASS of their own (render_ctr_lockstep): when the ring is empty, the wave
+// parks its paths' rays in LDS, walks the camera rays of the next (up to 64 - ring_count) samples of its run with all lanes (coherent rays from one
+// origin), finishes right there the paths whose camera ray misses or hits an emitter / a Null material, and appends the others as ready-to-scatter
+// entries.  A lane that is dealt an entry scatters its first hit in the same iteration, as a continuing lane at ray 0.  Every value of an entry is the
+// one the loop computed for that sample before (same functions, same order), so radiance and ray counts are the same bits.
+// An entry is 64 bytes (four ds_read_b128): {h.p, sample index}, {h.n, mat_ff}, q0, the generator key at ray 0 (pcg4d: its four words; Philox: the
+// key, x and s -- the ray word is 0).  The parking area holds ro and rd of the 64 lanes (24 bytes each) during a refill pass.
+struct HitStock {
+    float4* e;                                                 // [64][4] this wave's ring of entries
+    float4* park_a; float2* park_b;                            // [64] each: {ro, rd.x}, {rd.y, rd.z}
+    // Before the walk: the camera ray of sample `sidx` into (ro, rd) -- what RayStock::refill and the loop's shared tail computed -- and its key
+    // into the entry at `slot` (the entry's other words are written after the walk).
+    DI void camera(const RenderParams& P, uint32_t sidx, uint32_t slot, f3& ro, f3& rd) const {
+        RngCtr rng; uint32_t px, py;
+        start_path(P, sidx, rng, px, py);
+        rng.template load_block0<true>();                                                   // ray 0, block 0: the jitter (words 0 / 1)
+        const float un = (float)px + rng.jitter_u(), vn = (float)py + rng.jitter_v();
+        const float u = div_by_rn(un, P.width_f, P.inv_width_rn);                           // renderer.rs:96
+        const float v = div_by_rn(vn, P.height_f, P.inv_height_rn);                         // renderer.rs:97
+        ro = mk(P.cam.position[0], P.cam.position[1], P.cam.position[2]);
+        rd = ray_direction<true>(camera_raw(P.cam, u, v));                                   // renderer.rs:99
+        e[4u * slot + 3u] = make_float4(__uint_as_float(rng.w[0]), __uint_as_float(rng.w[1]), __uint_as_float(rng.w[2]), __uint_as_float(rng.w[3]));
+    }
+    // After the walk (lanes with cam == true walked sample first + lane from `tail` + lane): finish the paths that end at their camera ray, exactly as
+    // shade_and_regenerate classifies a path at ray 0 (throughput 1), and append the others to the ring in sample order.  Returns how many were appended.
+    DI uint32_t append(const RenderParams& P, uint32_t lane, uint32_t first, uint32_t tail, bool cam, bool hit, const Hit& h, f3 rd) const {
+        struct Rad { float x, y, z; };
+        bool keep = false;
+        if (cam) {
+            f3 term = mk(0.f, 0.f, 0.f); bool fin = false;
+            if (!hit) { term = miss_colour(P.sky, P.sky_w, P.sky_h, P.miss, rd); fin = true; }      // renderer.rs:38-63
+            else {
+                const uint32_t kind = __float_as_uint(h.q0.x);
+                if (kind == MI355RT_MAT_EMISSIVE) { term = mk(h.q0.y, h.q0.z, h.q0.w); fin = true; }
+                else if (kind == MI355RT_MAT_NULL) fin = true;
+            }
+            if (fin) { const f3 L = mk(1.f, 1.f, 1.f) * term; reinterpret_cast<Rad*>(P.radiance)[first + lane] = Rad{L.x, L.y, L.z}; }
+            keep = !fin;
+        }
+        const uint64_t km = __ballot(keep);
+        if (keep) {
+            const float4 key = e[4u * ((tail + lane) & 63u) + 3u];                          // (every lane reads before any lane writes: one wave, in order)
+            float4* d = e + 4u * ((tail + mbcnt64(km)) & 63u);
+            d[0] = make_float4(h.p.x, h.p.y, h.p.z, __uint_as_float(first + lane));
+            d[1] = make_float4(h.n.x, h.n.y, h.n.z, __uint_as_float(h.mat_ff));
+            d[2] = h.q0;
+            d[3] = key;
+        }
+        return (uint32_t)__popcll(km);
+    }
+};
+#ifndef MI355RT_PREHIT_LOW
+#define MI355RT_PREHIT_LOW 1                                   // refill when fewer entries are left: only when the ring is empty (cornell, against the parent: 1 -3.8 %, 4 -1.9 %, 8 -1.6 %, 16 -1.0 %, 32 +5 %; a partial refill walks fewer camera rays for the same cost)
+#endif
 struct NoStock {};
 
 // random_in_unit_sphere (vec3.rs:54-61) for the whole wave at once, counter mode.  Try 0 comes from the event's
@@ -280,7 +357,9 @@ template <uint32_t MATS, bool DEFAULTS = true, bool WIDE = !DEFAULTS, bool DROP_
 DI bool shade_and_regenerate(const RenderParams& P, WC& wc, uint32_t lane, bool& live, bool can_take, bool hit, const Hit& h,
                              PathState& ps, uint32_t& n_paths, uint32_t& n_rays, Prof& prof, const STOCK& stock = STOCK()) {
     constexpr bool STOCKED = std::is_same<STOCK, RayStock>::value;                           // camera rays come out of the wave's stock (lockstep kernels)
-    static_assert(!STOCKED || (!DEFAULTS && !REKEY), "the stock serves the lockstep form");
+    constexpr bool PREHIT = std::is_same<STOCK, HitStock>::value;                            // ... or their first hits (k_render_ctr_simple_qc)
+    static_assert(!(STOCKED || PREHIT) || (!DEFAULTS && !REKEY), "the stock serves the lockstep form");
+    static_assert(!PREHIT || (MATS & ~MATS_LAMBERT) == 0u, "an entry holds no incoming direction: the Lambert bounce does not read it");
     struct Rad { float x, y, z; };                                                        // 12 bytes per path: global_store_dwordx3
     Rad* __restrict__ radiance = reinterpret_cast<Rad*>(P.radiance);
     float4 q0;                                                                            // first 16 bytes of the hit material; read by lanes that loaded it
@@ -300,6 +379,21 @@ DI bool shade_and_regenerate(const RenderParams& P, WC& wc, uint32_t lane, bool&
     prof.mark(2);
     bool fresh = false;
     f3 stocked_raw = mk(0.f, 0.f, 1.f);
+    Hit hs;                                                                                // PREHIT: the hit a lane scatters (a dealt lane's comes from the ring)
+    if constexpr (PREHIT) {
+        hs = h;
+        uint32_t slot;
+        if (wc.deal_ring(can_take && !live, slot)) {                                       // a continuing path at ray 0 from here on
+            const float4* e = stock.e + 4u * slot;
+            const float4 e0 = e[0], e1 = e[1], e2 = e[2], e3 = e[3];
+            hs.p = mk(e0.x, e0.y, e0.z); ps.sidx = __float_as_uint(e0.w);
+            hs.n = mk(e1.x, e1.y, e1.z); hs.mat_ff = __float_as_uint(e1.w);
+            q0 = e2;
+            ps.rng.w[0] = __float_as_uint(e3.x); ps.rng.w[1] = __float_as_uint(e3.y); ps.rng.w[2] = __float_as_uint(e3.z); ps.rng.w[3] = __float_as_uint(e3.w);
+            if constexpr (RngCtr::NW == 5) ps.rng.w[4] = 0u;                                  // (Philox: the ray word)
+            ps.thr = mk(1.f, 1.f, 1.f); ps.ray_index = 0; live = true;
+        }
+    } else
     if constexpr (STOCKED) {
         if (wc.deal_stocked(P, can_take && !live, lane, ps.sidx, [&](uint32_t first, uint32_t count) { stock.template refill<FASTN>(P, first, count, lane); },
                             [&](uint32_t sidx) { stock.take(P, sidx, stocked_raw, ps); })) { fresh = true; live = true; ++n_paths; }
@@ -367,16 +461,16 @@ DI bool shade_and_regenerate(const RenderParams& P, WC& wc, uint32_t lane, bool&
                 n_thr = mk(1.f, 1.f, 1.f); n_ri = 0;
                 if (P.max_depth == 0u) { radiance[ps.sidx] = Rad{0.f, 0.f, 0.f}; live = false; }   // depth == 0 -> BLACK
             } else {
-                scattered = scatter_pre<MATS, WIDE, FASTN, /* TERMINAL_DONE */ true>(P.mats, P.textures, q0, h, ps.rd, ps.rng, side, raw, atten, emitted, ball_use, fuzz);
+                scattered = scatter_pre<MATS, WIDE, FASTN, /* TERMINAL_DONE */ true>(P.mats, P.textures, q0, PREHIT ? hs : h, ps.rd, ps.rng, side, raw, atten, emitted, ball_use, fuzz);
             }
         }
         prof.mark(5);
         prof.classes(live && !fresh, live && fresh, __float_as_uint(q0.x));
         const f3 ball = unit_ball_cooperative<WIDE, TRY1>(scattered && ball_use != BALL_NONE, ps.rng, lane, blk1);   // whole wave, uniform control flow
         if (live && !fresh) {
-            if (scattered) scattered = ball_finish<FASTN>(ball_use, h, ball, fuzz, raw);     // (a fuzzed metal reflection may still be absorbed)
+            if (scattered) scattered = ball_finish<FASTN>(ball_use, PREHIT ? hs : h, ball, fuzz, raw);     // (a fuzzed metal reflection may still be absorbed)
             if (scattered) {
-                n_thr = ps.thr * atten; n_ro = scatter_origin(h, side); n_ri = ps.ray_index + 1u;
+                n_thr = ps.thr * atten; n_ro = scatter_origin(PREHIT ? hs : h, side); n_ri = ps.ray_index + 1u;
                 if (n_ri == P.max_depth) {                                                   // next level has depth == 0 (renderer.rs:20-22)
                     const f3 L = n_thr * mk(0.f, 0.f, 0.f);
                     radiance[ps.sidx] = Rad{L.x, L.y, L.z}; live = false;
@@ -413,7 +507,8 @@ DI bool shade_and_regenerate(const RenderParams& P, WC& wc, uint32_t lane, bool&
 // The lockstep kernels' forms (each measured against its alternative; docs/kernels/lockstep_round3.md): the candidate carries the cube's object-space hit
 // point (also in the general kernel: pays at 80 VGPRs); the short reciprocal / square root / division of rt_math.h; in the Lambert-only kernel ONE try of the
 // unit-ball draw in the lane itself before the cooperative rounds (0 tries: +1.9 %, 2 tries: +-0 with pcg4d, +23 % with Philox: profiles/r05/ab_counter_generator.txt).
-template <bool HAS_MESH, uint32_t MATS, uint32_t KINDS = PRIMS_ALL>
+// PREHIT: the wave stocks its camera rays' first hits (HitStock), walked in refill passes through the loop's one walk site.
+template <bool HAS_MESH, uint32_t MATS, uint32_t KINDS = PRIMS_ALL, bool PREHIT = false>
 DI void render_ctr_lockstep(const RenderParams& P) {
     constexpr bool SIMPLE = (MATS & ~MATS_LAMBERT) == 0u;
     // The mesh-free kernels are compiled for lists that hold something and for paths that may take a step: the host sends an empty list or max_depth == 0 to
@@ -424,9 +519,17 @@ DI void render_ctr_lockstep(const RenderParams& P) {
     cprim_t prims = (cprim_t)(P.prims);
     const uint32_t lane = threadIdx.x & 63u;
     WorkCursor wc; wc.init();
+    std::conditional_t<PREHIT, HitStock, RayStock> stock;
+    if constexpr (PREHIT) {                                                                    // HitStock: 64 entries of 64 B + 1.5 KB of parked rays per wave
+        __shared__ __attribute__((aligned(16))) float4 s_ring[4u * BLOCK_THREADS];             // (22 KB per workgroup: 7 workgroups fit in 160 KB)
+        __shared__ __attribute__((aligned(16))) float4 s_park_a[BLOCK_THREADS];
+        __shared__ __attribute__((aligned(16))) float2 s_park_b[BLOCK_THREADS];
+        stock.e = s_ring + 4u * (threadIdx.x & ~63u); stock.park_a = s_park_a + (threadIdx.x & ~63u); stock.park_b = s_park_b + (threadIdx.x & ~63u);
+    } else {
     __shared__ __attribute__((aligned(16))) float4 s_stock_dir[BLOCK_THREADS];                // RayStock: 64 entries per wave
     __shared__ __attribute__((aligned(16))) uint4 s_stock_key[BLOCK_THREADS];
-    RayStock stock; stock.dir = s_stock_dir + (threadIdx.x & ~63u); stock.key = s_stock_key + (threadIdx.x & ~63u);
+    stock.dir = s_stock_dir + (threadIdx.x & ~63u); stock.key = s_stock_key + (threadIdx.x & ~63u);
+    }
     PathState ps; ps.ro = mk(0, 0, 0); ps.rd = mk(0, 0, 1); ps.thr = mk(1, 1, 1); ps.sidx = 0; ps.ray_index = 0; ps.px = ps.py = 0;
     ps.rng.clear();
     bool live = false;
@@ -446,8 +549,28 @@ DI void render_ctr_lockstep(const RenderParams& P) {
         // (Round 5, after the scalar diet: all four schemes -- 1/0, none, inverted, 3/0 -- are within 0.2 % of each other; the list walk no longer waits.
         //  profiles/r05/ab_scalar_diet.txt r05_q13.)
         __builtin_amdgcn_s_setprio(1);
-        if (live) hit = hit_scene<HAS_MESH, true, KINDS>(prims, P.n_prims, P.nodes, P.tris, ps.ro, ps.rd, h);     // renderer.rs:24
+        uint32_t n_cam = 0u;                               // PREHIT: camera rays walked in this iteration (a refill pass; wave-uniform)
+        if constexpr (PREHIT) {
+            n_cam = wc.template refill_size<MI355RT_PREHIT_LOW>(P, lane);
+            if (n_cam != 0u) {                             // park the paths' rays; lane i takes the camera ray of sample next + i
+                stock.park_a[lane] = make_float4(ps.ro.x, ps.ro.y, ps.ro.z, ps.rd.x); stock.park_b[lane] = make_float2(ps.rd.y, ps.rd.z);
+                if (lane < n_cam) stock.camera(P, wc.next + lane, (wc.ring_head + wc.ring_count + lane) & 63u, ps.ro, ps.rd);
+            }
+        }
+        if (n_cam != 0u ? lane < n_cam : live) hit = hit_scene<HAS_MESH, true, KINDS>(prims, P.n_prims, P.nodes, P.tris, ps.ro, ps.rd, h);     // renderer.rs:24
         prof.mark(1);
+        if constexpr (PREHIT) {
+            if (n_cam != 0u) {                             // finish or stock the camera paths, take the parked rays back, and walk them next
+                const bool cam = lane < n_cam;
+                if (cam) { ++n_paths; ++n_rays; }
+                wc.ring_count += stock.append(P, lane, wc.next, wc.ring_head + wc.ring_count, cam, hit, h, ps.rd);
+                wc.next += n_cam;
+                const float4 a = stock.park_a[lane]; const float2 b = stock.park_b[lane];
+                ps.ro = mk(a.x, a.y, a.z); ps.rd = mk(a.w, b.x, b.y);
+                prof.mark(2);
+                continue;
+            }
+        }
         if (!shade_and_regenerate<MATS, false, true, true, !HAS_MESH, /* FASTN */ true, /* TRY1 */ SIMPLE ? 1 : 0>(P, wc, lane, live, true, hit, h, ps, n_paths, n_rays, prof, stock)) break;
         prof.mark(4);
 #ifdef MI355RT_STAMPS
@@ -481,8 +604,9 @@ DI void render_ctr_lockstep(const RenderParams& P) {
 //   k_render_ctr_mesh       lockstep with the per-lane BVH walk inlined             (diagnostic knob; the two degenerate renders: an empty list, max_depth 0)
 __global__ void __launch_bounds__(BLOCK_THREADS) MI355RT_OCC_LS k_render_ctr_nomesh(const RenderParams P) { render_ctr_lockstep<false, MATS_ALL>(P); }
 __global__ void __launch_bounds__(BLOCK_THREADS) MI355RT_OCC_SIMPLE k_render_ctr_simple(const RenderParams P) { render_ctr_lockstep<false, MATS_LAMBERT>(P); }
-// ... and the Lambert-only kernel for lists of quads and cubes (round 5: cornell -1.1 %, profiles/r05/ab_scalar_diet.txt r05_q16)
-__global__ void __launch_bounds__(BLOCK_THREADS) MI355RT_OCC_SIMPLE k_render_ctr_simple_qc(const RenderParams P) { render_ctr_lockstep<false, MATS_LAMBERT, PRIMS_QUAD_CUBE>(P); }
+// ... and the Lambert-only kernel for lists of quads and cubes (round 5: cornell -1.1 %, profiles/r05/ab_scalar_diet.txt r05_q16), with its camera rays'
+// first hits in stock (HitStock: cornell -3.7 %, profiles/ab_stocked_first_hits.txt)
+__global__ void __launch_bounds__(BLOCK_THREADS) MI355RT_OCC_SIMPLE k_render_ctr_simple_qc(const RenderParams P) { render_ctr_lockstep<false, MATS_LAMBERT, PRIMS_QUAD_CUBE, /* PREHIT */ true>(P); }
 __global__ void __launch_bounds__(BLOCK_THREADS) MI355RT_OCC_SIMPLE k_render_ctr_nospec(const RenderParams P) { render_ctr_lockstep<false, MATS_NO_SPECULAR>(P); }
 __global__ void __launch_bounds__(BLOCK_THREADS) __attribute__((amdgpu_waves_per_eu(6, 6))) k_render_ctr_mesh(const RenderParams P) { render_ctr_lockstep<true, MATS_ALL>(P); }
 
