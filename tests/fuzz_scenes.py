@@ -5,7 +5,18 @@ import ctypes as C
 import numpy as np
 
 
-def random_scene(abi, host, seed, exact_only, n_prims=14, mesh_tris=60, only_kinds=None, lambert_only=False, identity_meshes=False, no_metal=False):
+def random_scene(abi, host, seed, exact_only, n_prims=14, mesh_tris=60, only_kinds=None, lambert_only=False, identity_meshes=False, no_metal=False,
+                 no_specular=False, textures=False, sky=False, coincident=False, big_mesh_tris=0, every_material=False):
+    """The options after no_metal are off by default, and then the scene of a seed is the one earlier versions made:
+      no_specular    no metal and no dielectric (what the no-specular lockstep / mesh-free wavefront kernels accept);
+      textures       two small RGBA8 textures whose neighbouring texels differ, and texture materials (h_offset != 0) over them;
+      sky            an HDR sky map (float32 [8, 16, 3]) instead of the flat miss colour;
+      coincident     every third primitive and the first of each kind repeated with another material right behind itself, and once more at
+                     the end of the list
+                     (equal t: the list order decides); meshes also repeat some of their triangles with the opposite winding;
+      big_mesh_tris  > 0: one more mesh of that many small triangles (its tree passes LDS_NODE_CAP and WF_SHALLOW_NODES);
+      every_material the first primitives take the material kinds in turn, so that every material of the list is hit-able.
+    They draw from a generator of their own, so the draws of the options before them stay what they were."""
     from oracle import scene_loader as L
     rng = np.random.default_rng(seed)
     F = np.float32
@@ -27,10 +38,24 @@ def random_scene(abi, host, seed, exact_only, n_prims=14, mesh_tris=60, only_kin
         kinds = [mat(abi.MAT_LAMBERT_SOLID, col()), mat(abi.MAT_EMISSIVE, tuple(rng.uniform(1, 6, 3))), mat(abi.MAT_NULL), mat(abi.MAT_LAMBERT_SOLID, col())]
     if no_metal:                                                     # the wavefront kernels' pruned instantiations: no MI355RT_MAT_METAL in the list
         kinds = [k for k in kinds if mats[k].kind != abi.MAT_METAL]
+    if no_specular:
+        kinds = [k for k in kinds if mats[k].kind not in (abi.MAT_METAL, abi.MAT_DIELECTRIC)]
     if not exact_only:
         cu = ((0.2, 1.09, 1.42), (3.91, 2.57, 2.30))
         kinds += [mat(abi.MAT_ROUGH_GGX, col(), p0=rng.uniform(0.02, 0.5), eta=cu[0], k=cu[1]),
                   mat(abi.MAT_ROUGH_BECKMANN, col(), p0=rng.uniform(0.02, 0.5), eta=cu[0], k=cu[1])]
+
+    rng2 = np.random.default_rng([seed, 0x5eed])
+    tex_arrays = []
+    if textures:
+        for h, w in ((4, 8), (6, 5)):
+            img = rng2.integers(0, 256, (h, w, 4), dtype=np.uint8)
+            img[..., 0] = (np.arange(w)[None, :] * 37 + np.arange(h)[:, None] * 91) % 256           # neighbouring texels always differ
+            tex_arrays.append(np.ascontiguousarray(img))
+        for t in range(len(tex_arrays)):
+            k = mat(abi.MAT_TEXTURE, tuple(rng2.uniform(0.1, 0.95, 3)), p0=float(rng2.uniform(0.1, 0.9)))
+            mats[k].texture = t
+            kinds.append(k)
 
     def matrix():
         q = L.quat_from_euler_yxz_deg(F(rng.uniform(-180, 180)), F(rng.uniform(-180, 180)), F(rng.uniform(-180, 180)))
@@ -41,9 +66,14 @@ def random_scene(abi, host, seed, exact_only, n_prims=14, mesh_tris=60, only_kin
         order = [only_kinds[i % len(only_kinds)] for i in range(n_prims)]
     else:
         order = [abi.PRIM_SPHERE, abi.PRIM_PLANE, abi.PRIM_QUAD, abi.PRIM_CUBE, abi.PRIM_MESH] + list(rng.integers(0, 5, n_prims - 5))
+    if big_mesh_tris > 0:
+        order = list(order) + [abi.PRIM_MESH]
     n_tri = 0
-    for kind in order:
+    for pi, kind in enumerate(order):
+        big = big_mesh_tris > 0 and pi == len(order) - 1
         p = abi.Primitive(); p.kind = int(kind); p.material = int(kinds[rng.integers(0, len(kinds))])
+        if every_material and pi < len(kinds):
+            p.material = int(kinds[pi])
         if kind == abi.PRIM_SPHERE:
             p.data[0:4] = [float(F(v)) for v in rng.uniform(-3, 3, 3)] + [float(F(rng.uniform(0.3, 1.2)))]
         elif kind == abi.PRIM_PLANE:
@@ -58,20 +88,47 @@ def random_scene(abi, host, seed, exact_only, n_prims=14, mesh_tris=60, only_kin
             if identity_meshes:                                        # untransformed meshes (OBJ data in world space): what k_render_ctr_wf_nometal_ident is picked for
                 ident = [1.0 if (k % 5) == 0 else 0.0 for k in range(16)]
                 p.data[0:16] = ident; p.data[16:32] = ident
-            nt = mesh_tris if mesh_tris > 0 else int(rng.integers(1, 4))          # mesh_tris <= 0: tiny meshes of 1..3 triangles
-            v = rng.uniform(-1, 1, size=(nt, 3, 3)).astype(F)
-            v[: nt // 4, :, 2] = F(0.25)                                   # a coplanar patch: zero-thickness leaf boxes (App. B-1)
+            if big:                                                          # small triangles scattered through the unit box: a deep tree
+                nt = big_mesh_tris
+                v = (rng2.uniform(-1, 1, size=(nt, 1, 3)) + rng2.uniform(-0.06, 0.06, size=(nt, 3, 3))).astype(F)
+            else:
+                nt = mesh_tris if mesh_tris > 0 else int(rng.integers(1, 4))          # mesh_tris <= 0: tiny meshes of 1..3 triangles
+                v = rng.uniform(-1, 1, size=(nt, 3, 3)).astype(F)
+                v[: nt // 4, :, 2] = F(0.25)                                   # a coplanar patch: zero-thickness leaf boxes (App. B-1)
+            if coincident:                                                   # repeated triangles: copies of the first fifth at the end of the mesh,
+                v = np.concatenate([v, v[: max(1, nt // 5)][:, [0, 2, 1]]], axis=0)   # wound the other way (other t arithmetic: the winner shows)
+                nt = len(v)
             idx = np.arange(nt * 3).reshape(nt, 3)
             tris = L._triangles_from_indexed(v.reshape(-1, 3), idx)
             mesh = abi.Mesh(); mesh.first_triangle, mesh.triangle_count = n_tri, len(tris)
             n_tri += len(tris); tri_chunks.append(tris); meshes.append(mesh); p.mesh = len(meshes) - 1
         prims.append(p)
+    if coincident:                                                       # equal t, other material: next to itself and once more at the end
+        reps = []
+        firsts = {int(q.kind): i for i, q in reversed(list(enumerate(prims)))}     # ... and the first primitive of every kind
+        for i in sorted(set(range(0, len(prims), 3)) | set(firsts.values())):
+            q = abi.Primitive(); C.pointer(q)[0] = prims[i]
+            q.material = int(kinds[(kinds.index(prims[i].material) + 1) % len(kinds)])
+            reps.append((i, q))
+        tail = []
+        for i, q in reversed(reps):
+            r = abi.Primitive(); C.pointer(r)[0] = q
+            r.material = int(kinds[(kinds.index(q.material) + 1) % len(kinds)])
+            prims.insert(i + 1, q)
+            tail.append(r)
+        prims.extend(tail)
 
     sc = L.LoadedScene()
+    if sky:
+        sc.sky = (rng2.uniform(0.05, 1.0, (8, 16, 3)) * rng2.choice([1.0, 4.0], (8, 16, 1))).astype(F)
     sc.materials, sc.primitives, sc.meshes = mats, prims, meshes
     sc.triangles = np.concatenate(tri_chunks, axis=0) if tri_chunks else np.zeros((0, 12), F)
     sc.finalize()
     sc.c.miss_color[:] = [float(F(v)) for v in rng.uniform(0.2, 0.8, 3)]
+    if tex_arrays:
+        sc._tex_arrays = tex_arrays
+        sc._textures = (abi.Texture * len(tex_arrays))(*[abi.Texture(a.ctypes.data_as(C.POINTER(C.c_uint8)), a.shape[1], a.shape[0]) for a in tex_arrays])
+        sc.c.textures, sc.c.n_textures = sc._textures, len(tex_arrays)
     sc._keep = host.attach_bvh(sc)
     sc.camera = L.camera_new((0.0, 1.0, 9.0), (0.0, 0.0, 0.0), (0.0, 1.0, 0.0), F(50.0), F(4.0 / 3.0))
     return sc

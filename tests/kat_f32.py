@@ -324,3 +324,182 @@ def scatter_texture(albedo, rgba, h_offset, rd, p, n, draws):     # tungsten/par
     o, d = lambert_dir(n, p, draws.unit_ball())
     tex, _ = texture_value(rgba, h_offset, n)
     return True, o, d, albedo * tex
+
+
+# ---- objects/plane.rs:26-56 ------------------------------------------------------------------------------------------
+def hit_plane(p1, normal, ro, rd, t_min, t_max):
+    """`normal` is the stored (already normalised, Plane::new) normal."""
+    denom = dot(normal, rd)
+    if abs(denom) < EPS:
+        return None
+    with np.errstate(all="ignore"):
+        t = f32(dot(normal, p1 - ro) / denom)
+    if t <= t_min or t >= t_max:
+        return None
+    p = ro + rd * t                                          # Ray::at
+    n, front = set_face(rd, normal)
+    return t, p, n, front
+
+
+# ---- glam Mat4 (column-major 16 floats) * Vec4: ((x_axis * x + y_axis * y) + z_axis * z) + w_axis * w, each product and sum rounded ----
+def mat4_vec4(m, x, y, z, w):
+    m = np.asarray(m, np.float32)
+    with np.errstate(all="ignore"):
+        acc = m[0:4] * f32(x)
+        acc = acc + m[4:8] * f32(y)
+        acc = acc + m[8:12] * f32(z)
+        acc = acc + m[12:16] * f32(w)
+    return acc[:3].astype(np.float32)
+
+
+def mat4_transpose(m):
+    return np.asarray(m, np.float32).reshape(4, 4).T.reshape(16).copy()
+
+
+def signum(x):                                   # f32::signum: NaN stays NaN, +-0 give +-1
+    return f32(np.nan) if np.isnan(x) else f32(np.copysign(f32(1.0), x))
+
+
+def normalize_or_zero(v):                        # glam Vec3::normalize_or_zero
+    with np.errstate(all="ignore"):
+        rcp = f32(f32(1.0) / f32(np.sqrt(dot(v, v))))
+    if np.isfinite(rcp) and rcp > 0:
+        return v * rcp
+    return V(0, 0, 0)
+
+
+# ---- objects/cube.rs:59-158 --------------------------------------------------------------------------------------------
+def hit_cube(o2w, w2o, ro, rd, t_min, t_max):
+    ro_o = mat4_vec4(w2o, ro[0], ro[1], ro[2], 1.0)
+    rd_o = mat4_vec4(w2o, rd[0], rd[1], rd[2], 0.0)
+    with np.errstate(all="ignore"):
+        inv = V(1, 1, 1) / rd_o
+        t1 = (V(-0.5, -0.5, -0.5) - ro_o) * inv
+        t2 = (V(0.5, 0.5, 0.5) - ro_o) * inv
+    te, tx = np.fmin(t1, t2), np.fmax(t1, t2)                 # glam min / max: f32::min / max, a NaN operand is ignored
+    t_enter = np.fmax(te[0], np.fmax(te[1], te[2]))
+    t_exit = np.fmin(tx[0], np.fmin(tx[1], tx[2]))
+    if t_exit < t_enter or t_exit <= 0:
+        return None
+    t_hit = t_enter if t_enter > 0 else t_exit
+    if t_hit >= t_max or t_hit <= t_min or t_hit < EPS:
+        return None
+    with np.errstate(all="ignore"):
+        po = ro_o + rd_o * t_hit
+    ap = np.abs(po)
+    tol = f32(1e-4)
+    n_o = V(0, 0, 0)
+    if abs(f32(ap[0] - f32(0.5))) < tol:
+        n_o[0] = signum(po[0])
+    elif abs(f32(ap[1] - f32(0.5))) < tol:
+        n_o[1] = signum(po[1])
+    elif abs(f32(ap[2] - f32(0.5))) < tol:
+        n_o[2] = signum(po[2])
+    elif ap[0] > ap[1] and ap[0] > ap[2]:
+        n_o[0] = signum(po[0])
+    elif ap[1] > ap[2]:
+        n_o[1] = signum(po[1])
+    else:
+        n_o[2] = signum(po[2])
+    n_o = normalize_or_zero(n_o)
+    pw = mat4_vec4(o2w, po[0], po[1], po[2], 1.0)
+    nw = normalized(mat4_vec4(mat4_transpose(w2o), n_o[0], n_o[1], n_o[2], 0.0))
+    with np.errstate(all="ignore"):
+        if dot(pw - ro, rd) < 0:
+            return None
+        t_world = dot(pw - ro, rd)
+    if t_world < t_min or t_world > t_max:
+        return None
+    n, front = set_face(rd, nw)
+    return t_world, pw, n, front
+
+
+# ---- acceleration/aabb.rs:27-45, acceleration/bvh.rs:78-170 (the tree as the ABI carries it: leaf <=> index_count > 0) ------------
+def aabb_intersect(bmin, bmax, ro, rd, t_min, t_max):
+    for a in range(3):
+        with np.errstate(all="ignore"):
+            inv = f32(f32(1.0) / rd[a])
+            t0 = f32(f32(bmin[a] - ro[a]) * inv)
+            t1 = f32(f32(bmax[a] - ro[a]) * inv)
+        if inv < 0:
+            t0, t1 = t1, t0
+        t_min, t_max = np.fmax(t_min, t0), np.fmin(t_max, t1)
+        if t_max <= t_min:
+            return False
+    return True
+
+
+def hit_triangle(tri, ro, rd, t_min, t_max):
+    """The leaf loop's test of one triangle (bvh.rs:99-116 and the record after it); tri: [12] f32 = v0, v1, v2, normal."""
+    v0, v1, v2, tn = tri[0:3], tri[3:6], tri[6:9], tri[9:12]
+    with np.errstate(all="ignore"):
+        e1, e2 = v1 - v0, v2 - v0
+        h = cross(rd, e2)
+        a = dot(e1, h)
+        if abs(a) < EPS:
+            return None
+        f = f32(f32(1.0) / a)
+        s = ro - v0
+        u = f32(f * dot(s, h))
+        if not (f32(0.0) <= u <= f32(1.0)):
+            return None
+        q = cross(s, e1)
+        v = f32(f * dot(rd, q))
+        if v < 0 or f32(u + v) > 1:
+            return None
+        t = f32(f * dot(e2, q))
+        if not (t > t_min and t < t_max):
+            return None
+        p = ro + rd * t
+    n, front = set_face(rd, tn)
+    return t, p, n, front
+
+
+def bvh_hit(nodes, idx, tris, node, ro, rd, t_min, t_max):
+    """intersect_recursive: nodes [k] of (bmin, bmax, left, right, first_index, index_count), child links and leaf ranges local to the mesh."""
+    bmin, bmax, left, right, first, count = nodes[node]
+    if not aabb_intersect(bmin, bmax, ro, rd, t_min, t_max):
+        return None
+    if count > 0:
+        best = None
+        for k in range(first, first + count):
+            h = hit_triangle(tris[idx[k]], ro, rd, t_min, t_max)
+            if h is not None:
+                t_max, best = h[0], h
+        return best
+    hl = bvh_hit(nodes, idx, tris, left, ro, rd, t_min, t_max)
+    if hl is not None:
+        t_max = hl[0]
+    hr = bvh_hit(nodes, idx, tris, right, ro, rd, t_min, t_max)
+    if hl is not None and hr is not None:
+        return hl if hl[0] < hr[0] else hr
+    return hl if hl is not None else hr
+
+
+# ---- mesh/mesh_object.rs:263-329 ---------------------------------------------------------------------------------------
+def hit_mesh(o2w, w2o, nodes, idx, tris, ro, rd, t_min, t_max):
+    ro_o = mat4_vec4(w2o, ro[0], ro[1], ro[2], 1.0)
+    rd_o = mat4_vec4(w2o, rd[0], rd[1], rd[2], 0.0)
+    o_obj, d_obj = ray_new(ro_o, normalized(rd_o))
+    h = bvh_hit(nodes, idx, tris, 0, o_obj, d_obj, t_min, t_max)
+    if h is None:
+        return None
+    t, p, n, _ = h
+    pw = mat4_vec4(o2w, p[0], p[1], p[2], 1.0)
+    nw = normalized(mat4_vec4(mat4_transpose(w2o), n[0], n[1], n[2], 0.0))
+    t_world = f32(f32(t * length(rd_o)) / length(rd))
+    if t_world < t_min or t_world > t_max:
+        return None
+    n, front = set_face(rd, nw)
+    return t_world, pw, n, front
+
+
+# ---- hittable.rs:45-58 ---------------------------------------------------------------------------------------------------
+def hit_list(hitters, ro, rd, t_min=EPS, t_max=f32(np.inf)):
+    """hitters: [(material, fn(ro, rd, t_min, t_max) -> (t, p, n, front) | None)] in list order.  Returns (t, p, n, front, material) or None."""
+    best = None
+    for mat, fn in hitters:
+        h = fn(ro, rd, t_min, t_max)
+        if h is not None:
+            t_max, best = h[0], (*h, mat)
+    return best
