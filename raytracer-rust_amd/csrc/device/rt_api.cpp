@@ -171,14 +171,11 @@ static int report_device_error(mi355rt_context* ctx, bool this_render) {
     if (count == ctx->err_reported) return MI355RT_OK;
     const unsigned long long n = count - ctx->err_reported;
     ctx->err_reported = count;
-    static const char* const kernel_names[KERNEL_VARIANTS] = {"k_render_ctr_nomesh", "k_render_ctr_mesh", "k_render_ctr_sm", "k_render_ctr_simple", "k_render_ctr_sm_fixaabb",
-        "(retired)", "(retired)", "k_render_ctr_wf", "k_render_ctr_wf_fixaabb", "k_render_ctr_nospec", "k_render_ctr_wf_nometal", "k_render_ctr_wf_meshfree",
-        "k_render_ctr_wf_nometal_ident", "k_render_ctr_wf_nometal_shallow", "k_render_ctr_simple_qc"};
     static const struct { uint32_t bit; const char* what; } waits[] = {
         {WAIT_WF_IDLE, "idle: no progress in the workgroup"}, {WAIT_WF_RING, "ring entry: a reserved ticket was never written, or an entry never emptied"},
         {WAIT_WF_FOLLOWED, "waves that followed their workgroup's error flag out"}};
     std::string kernels, which;
-    for (uint32_t v = 0; v < KERNEL_VARIANTS; ++v) if ((ctx->launched_variants >> v) & 1u) kernels += std::string(kernels.empty() ? "" : ", ") + kernel_names[v] + " (variant " + std::to_string(v) + ")";
+    for (uint32_t v = 0; v < KERNEL_VARIANTS; ++v) if ((ctx->launched_variants >> v) & 1u) kernels += std::string(kernels.empty() ? "" : ", ") + VARIANT_TABLE[v].kernel + " (variant " + std::to_string(v) + ")";
     ctx->launched_variants = 0;
     for (const auto& w : waits) if ((now >> 32) & w.bit) which += std::string(which.empty() ? "" : "; ") + w.what;
     return fail(MI355RT_ERR_HIP, "kernel watchdog: " + std::to_string(n) + " wave(s) gave up a bounded wait " + (this_render ? "in this render" : "in an earlier render on this context") +
@@ -474,11 +471,11 @@ int build_device_scene(mi355rt_context* ctx, const mi355rt_scene* sc) {
     uint32_t scene_mats = 0u;                                        // which material kinds a ray can meet (bit k = MI355RT_MAT_k): those the primitives refer to
     uint32_t scene_prim_kinds = 0u;                                  // ... and which primitive kinds the list holds (bit k = MI355RT_PRIM_k)
     for (uint32_t i = 0; i < sc->n_primitives; ++i) { scene_mats |= MATBIT(sc->materials[sc->primitives[i].material].kind); scene_prim_kinds |= 1u << sc->primitives[i].kind; }
-    auto covers = [&](uint32_t variant) { return (scene_mats & ~mats_of_variant(variant)) == 0u; };
-    auto kinds_covered = [&](uint32_t variant) { return (scene_prim_kinds & ~prims_of_variant(variant)) == 0u; };          // likewise for the primitive kinds of the list
+    auto covers = [&](uint32_t variant) { return (scene_mats & ~VARIANT_TABLE[variant].mats) == 0u; };
+    auto kinds_covered = [&](uint32_t variant) { return (scene_prim_kinds & ~VARIANT_TABLE[variant].prims) == 0u; };       // likewise for the primitive kinds of the list (a mesh among them)
     ctx->has_mesh = has_mesh;
     // Scenes with meshes: the wavefront kernel (path state in LDS, stage queues).  No mesh: a lockstep kernel.  In both
-    // families the most pruned instantiation whose material set covers the scene's (rt_device.h, mats_of_variant): the branches of
+    // families the most pruned instantiation whose material set covers the scene's (rt_device.h, VARIANT_TABLE): the branches of
     // the kinds a scene does not have are compiled out -- they set the register peak.  The library reads NO environment
     // variables; the diagnostic hook mi355rt_debug_set_knob("kernel", v) may name another variant this library was built with.
     // ... and, where the meshes are all untransformed (OBJ data in world space: teapot), the instantiation whose mesh_setup skips the matrix products.
@@ -498,12 +495,8 @@ int build_device_scene(mi355rt_context* ctx, const mi355rt_scene* sc) {
     }
     if (ctx->forced_variant >= 0) {
         const uint32_t v = (uint32_t)ctx->forced_variant;
-        const bool mesh_free_only = v == KERNEL_LOCKSTEP || v == KERNEL_LOCKSTEP_SIMPLE || v == KERNEL_LOCKSTEP_SIMPLE_QC || v == KERNEL_LOCKSTEP_NOSPEC || v == KERNEL_WAVEFRONT_MESHFREE;
-        const bool selectable = v == KERNEL_LOCKSTEP || v == KERNEL_LOCKSTEP_MESH || v == KERNEL_STATE_MACHINE || v == KERNEL_WAVEFRONT ||
-                                v == KERNEL_LOCKSTEP_SIMPLE || v == KERNEL_LOCKSTEP_SIMPLE_QC || v == KERNEL_LOCKSTEP_NOSPEC || v == KERNEL_WAVEFRONT_NOMETAL || v == KERNEL_WAVEFRONT_MESHFREE ||
-                                v == KERNEL_WAVEFRONT_NOMETAL_IDENT || v == KERNEL_WAVEFRONT_NOMETAL_SHALLOW;   // (the _FIXAABB forms follow options.flags; _SHALLOW is only a tuning: any tree is walked correctly)
-        const bool ok = render_ctr_variant_built(v) && selectable && covers(v) && kinds_covered(v) && !(mesh_free_only && has_mesh) &&
-                        !(v == KERNEL_WAVEFRONT_NOMETAL_IDENT && !(has_mesh && all_meshes_identity));     // (that form ASSUMES untransformed meshes)
+        const bool ok = render_ctr_variant_built(v) && VARIANT_TABLE[v].forceable && covers(v) && kinds_covered(v) &&
+                        !(VARIANT_TABLE[v].identity_meshes && !(has_mesh && all_meshes_identity));
         if (ok) ctx->variant = v;
     }
     // Root-box test right at mesh set-up (reference build's state machine): when several meshes share the list (teapot +5..12 %; a single
@@ -730,13 +723,10 @@ static int render_samples(mi355rt_context* ctx, const mi355rt_options* opt, uint
     if (opt && (opt->flags & ~MI355RT_FLAG_FIXED_AABB) != 0u) return fail(MI355RT_ERR_INVALID, "options.flags has unknown bits");
     if (fixed_aabb && rng_mode != MI355RT_RNG_CTR) return fail(MI355RT_ERR_INVALID, "MI355RT_FLAG_FIXED_AABB needs MI355RT_RNG_CTR (the replay mode reproduces the reference as it is)");
     uint32_t variant = ctx->variant;
-    if (fixed_aabb && ctx->has_mesh) {                                // without a mesh the flag changes nothing
-        variant = ctx->variant == KERNEL_STATE_MACHINE ? (uint32_t)KERNEL_STATE_MACHINE_FIXAABB : (uint32_t)KERNEL_WAVEFRONT_FIXAABB;
-        if (!render_ctr_variant_built(variant)) variant = KERNEL_WAVEFRONT_FIXAABB;
-    }
+    if (fixed_aabb && ctx->has_mesh) variant = VARIANT_TABLE[variant].fixed_aabb;     // without a mesh the flag changes nothing
     // The mesh-free lockstep kernels are compiled under the assumption that the list holds something and that a path may take a step (rt_kernels.hip,
     // render_ctr_lockstep); the two degenerate renders -- every sample is the miss colour / BLACK -- go to the plain per-lane loop, which assumes nothing.
-    if ((ctx->n_prims == 0 || st.max_depth == 0) && (variant == KERNEL_LOCKSTEP || variant == KERNEL_LOCKSTEP_SIMPLE || variant == KERNEL_LOCKSTEP_SIMPLE_QC || variant == KERNEL_LOCKSTEP_NOSPEC))
+    if ((ctx->n_prims == 0 || st.max_depth == 0) && VARIANT_TABLE[variant].family == FAMILY_LOCKSTEP && !(VARIANT_TABLE[variant].prims & (1u << MI355RT_PRIM_MESH)))
         variant = KERNEL_LOCKSTEP_MESH;
     const uint64_t seed = opt ? opt->seed : 0;
     const uint32_t n_rows = (uint32_t)ctx->rows_host.size();
@@ -825,7 +815,7 @@ static int render_samples(mi355rt_context* ctx, const mi355rt_options* opt, uint
         // F launches are co-resident, and a frame whose last paths are draining shares every SIMD with frames in their steady state.  A full-size grid
         // leaves the next frame's workgroups waiting for the draining frame's to retire one by one ("tail").
         const uint32_t resident = std::max(1u, (uint32_t)(ctx->cu_count * ctx->blocks_per_cu[variant]) / ctx->grid_div);
-        block_threads = block_threads_of(variant);
+        block_threads = VARIANT_TABLE[variant].block_threads;
         std::vector<float> band_ms;
         for (uint32_t b = 0; b < n_bands; ++b) {
             const uint64_t p0 = (uint64_t)b * band_pixels_max;
@@ -833,7 +823,7 @@ static int render_samples(mi355rt_context* ctx, const mi355rt_options* opt, uint
             p.band_pixel0 = (uint32_t)p0; p.band_samples = (uint32_t)(np * spp);
             p.batch_counter = ctx->counters.p + (size_t)b * ctr_words;
             if (d_row_counters) p.stats = d_row_counters + STATS_WORDS * (size_t)b;   // (a whole counter block per row: diagnostic builds write all of it)
-            const bool wf = is_wavefront(variant);
+            const bool wf = VARIANT_TABLE[variant].family == FAMILY_WAVEFRONT;
             const uint32_t run_min = wf ? RUN_WAVEFRONT_MIN : BATCH_MIN, run_max = wf ? RUN_WAVEFRONT : BATCH_MAX;   // what the kernel's WorkCursorT is compiled with
             p.shard_samples = (p.band_samples + WORK_SHARDS - 1) / WORK_SHARDS;
             p.shard_samples = (p.shard_samples + run_max - 1) / run_max * run_max;           // shards begin on run boundaries (fixed runs then stay aligned)

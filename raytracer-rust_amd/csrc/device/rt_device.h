@@ -113,29 +113,17 @@ enum : uint32_t { WAIT_WF_IDLE = 1u, WAIT_WF_RING = 2u, WAIT_WF_FOLLOWED = 4u };
 constexpr uint32_t SPIN_LIMIT_IDLE = 1u << 22;    // watchdog bounds: seconds of polling, never reached by a healthy launch
 constexpr uint32_t SPIN_LIMIT_ENTRY = 1u << 20;
 
-// Which counter-mode kernel serves a scene
+// Which counter-mode kernel serves a scene.  The numbers are what logs, profiles, tests and the "kernel" knob use; VARIANT_TABLE (below) describes each.
 enum : uint32_t {
-    KERNEL_LOCKSTEP = 0,         // no mesh at the top level: every lane traces a whole ray per iteration
-    KERNEL_LOCKSTEP_MESH = 1,    // same loop with the per-lane BVH walk inlined (A/B reference for the state machine)
-    KERNEL_STATE_MACHINE = 2,    // wave-voted TRAV / TOP / SHADE blocks (scenes with meshes)
-    KERNEL_LOCKSTEP_SIMPLE = 3,  // KERNEL_LOCKSTEP for scenes whose materials are only Lambertian (solid) / Emissive / Null
-    KERNEL_STATE_MACHINE_FIXAABB = 4,   // KERNEL_STATE_MACHINE with the opt-in slab test (MI355RT_FLAG_FIXED_AABB)
-    KERNEL_RETIRED_5 = 5,        // (round 2's LDS walk pool and its fixed-AABB form; removed in round 5, numbers kept so that the others stay what
-    KERNEL_RETIRED_6 = 6,        //  logs and tests of earlier rounds call them; no library holds them)
-    KERNEL_WAVEFRONT = 7,        // path state in LDS, stages as queues: every pass runs with (nearly) full lanes (scenes with meshes)
-    KERNEL_WAVEFRONT_FIXAABB = 8,
-    KERNEL_LOCKSTEP_NOSPEC = 9,  // KERNEL_LOCKSTEP without the metal and dielectric branches: 72 VGPRs = 7 waves per SIMD (veach-mis)
-    KERNEL_WAVEFRONT_NOMETAL = 10,   // KERNEL_WAVEFRONT without the metal branch (teapot, semesterbild)
-    KERNEL_WAVEFRONT_MESHFREE = 11,  // the wavefront for lists WITHOUT a mesh, no metal / dielectric: material-sorted SHADE passes for scenes whose materials diverge (veach-mis)
-    KERNEL_WAVEFRONT_NOMETAL_IDENT = 12,   // KERNEL_WAVEFRONT_NOMETAL for lists whose meshes are all untransformed (teapot): mesh_setup without its matrix products
-    KERNEL_WAVEFRONT_NOMETAL_SHALLOW = 13, // KERNEL_WAVEFRONT_NOMETAL for lists whose meshes all have small trees (semesterbild): WALK passes of 3 x 6 instead of 3 x 8 box tests
-    KERNEL_LOCKSTEP_SIMPLE_QC = 14,  // KERNEL_LOCKSTEP_SIMPLE for lists of quads and cubes only (cornell): no sphere / plane run checks in the walk, a two-way finish_hit
-    KERNEL_VARIANTS = 15
+    KERNEL_LOCKSTEP = 0, KERNEL_LOCKSTEP_MESH = 1, KERNEL_STATE_MACHINE = 2, KERNEL_LOCKSTEP_SIMPLE = 3, KERNEL_STATE_MACHINE_FIXAABB = 4,
+    KERNEL_RETIRED_5 = 5, KERNEL_RETIRED_6 = 6, KERNEL_WAVEFRONT = 7, KERNEL_WAVEFRONT_FIXAABB = 8, KERNEL_LOCKSTEP_NOSPEC = 9,
+    KERNEL_WAVEFRONT_NOMETAL = 10, KERNEL_WAVEFRONT_MESHFREE = 11, KERNEL_WAVEFRONT_NOMETAL_IDENT = 12, KERNEL_WAVEFRONT_NOMETAL_SHALLOW = 13,
+    KERNEL_LOCKSTEP_SIMPLE_QC = 14, KERNEL_VARIANTS = 15
 };
 // Primitive-kind sets (bit k = kind MI355RT_PRIM_k may occur), like the material sets below: the run checks and record branches of the other kinds are compiled out.
 constexpr uint32_t PRIMS_ALL = 0xFFFFFFFFu;
+constexpr uint32_t PRIMS_MESH_FREE = PRIMS_ALL & ~(1u << MI355RT_PRIM_MESH);
 constexpr uint32_t PRIMS_QUAD_CUBE = (1u << MI355RT_PRIM_QUAD) | (1u << MI355RT_PRIM_CUBE);
-inline uint32_t prims_of_variant(uint32_t variant) { return variant == KERNEL_LOCKSTEP_SIMPLE_QC ? PRIMS_QUAD_CUBE : PRIMS_ALL; }
 constexpr uint32_t WF_SHALLOW_NODES = 4096;      // "small tree": at most this many BVH nodes per mesh (a median-split tree of <= ~6 000 triangles, depth <= 11)
 // Material sets (bit k = kind MI355RT_MAT_k may occur) the kernels are instantiated for; set_scene picks, per kernel family, the
 // most pruned instantiation whose set covers the scene's materials.  The branches compiled out set the register peak.
@@ -147,10 +135,6 @@ constexpr uint32_t MATS_DIFFUSE = MATS_LAMBERT | MATBIT(MI355RT_MAT_LAMBERT_CHEC
 constexpr uint32_t MATS_ROUGH = MATBIT(MI355RT_MAT_ROUGH_GGX) | MATBIT(MI355RT_MAT_ROUGH_BECKMANN);
 constexpr uint32_t MATS_NO_METAL = MATS_ALL & ~MATBIT(MI355RT_MAT_METAL);
 constexpr uint32_t MATS_NO_SPECULAR = MATS_ALL & ~(MATBIT(MI355RT_MAT_METAL) | MATBIT(MI355RT_MAT_DIELECTRIC));
-inline uint32_t mats_of_variant(uint32_t variant) {
-    return (variant == KERNEL_LOCKSTEP_SIMPLE || variant == KERNEL_LOCKSTEP_SIMPLE_QC) ? MATS_LAMBERT : (variant == KERNEL_LOCKSTEP_NOSPEC || variant == KERNEL_WAVEFRONT_MESHFREE) ? MATS_NO_SPECULAR
-         : (variant == KERNEL_WAVEFRONT_NOMETAL || variant == KERNEL_WAVEFRONT_NOMETAL_IDENT || variant == KERNEL_WAVEFRONT_NOMETAL_SHALLOW) ? MATS_NO_METAL : MATS_ALL;
-}
 
 struct ResolveParams {
     const float* radiance;       // 3 floats per band sample
@@ -228,15 +212,43 @@ constexpr uint32_t WF_FIXED_WORDS = WF_CTRL_WORDS + WF_QUEUES * WF_RING / 2u + W
 constexpr uint32_t WF_LDS_BUDGET_WORDS = 163840u / 4u / 2u;
 static_assert(WF_FIXED_WORDS <= WF_LDS_BUDGET_WORDS, "wavefront kernel LDS budget");
 constexpr uint32_t STATS_WORDS = 40;                         // u64 device counters per render: [0] paths, [1] rays, the rest diagnostic builds only
-inline bool is_wavefront(uint32_t variant) { return variant == KERNEL_WAVEFRONT || variant == KERNEL_WAVEFRONT_FIXAABB || variant == KERNEL_WAVEFRONT_NOMETAL || variant == KERNEL_WAVEFRONT_MESHFREE || variant == KERNEL_WAVEFRONT_NOMETAL_IDENT || variant == KERNEL_WAVEFRONT_NOMETAL_SHALLOW; }
 // The mesh-free form runs 2 x 16 waves per CU at 64 VGPRs (8 per SIMD): veach-mis 16.71 -> 16.09 ms; the forms with the BVH walk lose a third
 // there (42 spilled registers).  Waves per workgroup must be a multiple of 4: a workgroup's waves are dealt round-robin over the CU's
 // four SIMDs, and with 10, 13 or 14 of them the second workgroup no longer fits the per-SIMD wave budget (measured: +40 %; this also explains
 // round 2's "2 x 10 waves at 96 VGPRs" result).
 constexpr uint32_t BLOCK_THREADS_WF_MESHFREE = 1024;
-inline uint32_t block_threads_of(uint32_t variant) {
-    return variant == KERNEL_WAVEFRONT_MESHFREE ? BLOCK_THREADS_WF_MESHFREE : is_wavefront(variant) ? BLOCK_THREADS_WF
-         : (variant == KERNEL_STATE_MACHINE || variant == KERNEL_STATE_MACHINE_FIXAABB) ? BLOCK_THREADS_SM : BLOCK_THREADS;
-}
+// What each counter-mode variant is: the one description that decides which kernel launch_render_ctr starts and with how many threads, what
+// the "kernel" knob may force on which scenes (set_scene), which form MI355RT_FLAG_FIXED_AABB swaps in, and what the watchdog message calls it.
+enum : uint32_t { FAMILY_LOCKSTEP, FAMILY_WAVEFRONT, FAMILY_STATE_MACHINE, FAMILY_RETIRED };
+struct VariantInfo {
+    uint32_t variant;            // = its row
+    const char* kernel;          // name of its kernel (bench.py KERNEL_NAMES)
+    uint32_t block_threads;      // workgroup size of its launch
+    uint32_t family;             // FAMILY_*: the wavefront kernels claim fixed runs of RUN_WAVEFRONT samples, the others guided runs of BATCH_MIN..BATCH_MAX
+    uint32_t mats, prims;        // the material kinds and primitive kinds it is compiled for: a scene with another kind cannot run on it
+    bool identity_meshes;        // it assumes a list with meshes, all of them untransformed
+    bool forceable;              // the "kernel" knob may name it
+    uint32_t fixed_aabb;         // what MI355RT_FLAG_FIXED_AABB launches in its place on a list with a mesh (itself where it walks no mesh)
+};
+constexpr VariantInfo VARIANT_TABLE[KERNEL_VARIANTS] = {
+    // variant                         kernel                             workgroup                   family                materials         primitives       ident  knob   fixed-AABB form
+    {KERNEL_LOCKSTEP,                  "k_render_ctr_nomesh",             BLOCK_THREADS,              FAMILY_LOCKSTEP,      MATS_ALL,         PRIMS_MESH_FREE, false, true,  KERNEL_LOCKSTEP},                 // no mesh at the top level: every lane traces a whole ray per iteration
+    {KERNEL_LOCKSTEP_MESH,             "k_render_ctr_mesh",               BLOCK_THREADS,              FAMILY_LOCKSTEP,      MATS_ALL,         PRIMS_ALL,       false, true,  KERNEL_WAVEFRONT_FIXAABB},        // same loop with the per-lane BVH walk inlined (A/B reference; the two degenerate renders)
+    {KERNEL_STATE_MACHINE,             "k_render_ctr_sm",                 BLOCK_THREADS_SM,           FAMILY_STATE_MACHINE, MATS_ALL,         PRIMS_ALL,       false, true,  KERNEL_STATE_MACHINE_FIXAABB},    // wave-voted TRAV / TOP / SHADE blocks (scenes with meshes; the tests' reference build only)
+    {KERNEL_LOCKSTEP_SIMPLE,           "k_render_ctr_simple",             BLOCK_THREADS,              FAMILY_LOCKSTEP,      MATS_LAMBERT,     PRIMS_MESH_FREE, false, true,  KERNEL_LOCKSTEP_SIMPLE},          // KERNEL_LOCKSTEP for scenes whose materials are only Lambertian (solid) / Emissive / Null
+    {KERNEL_STATE_MACHINE_FIXAABB,     "k_render_ctr_sm_fixaabb",         BLOCK_THREADS_SM,           FAMILY_STATE_MACHINE, MATS_ALL,         PRIMS_ALL,       false, false, KERNEL_STATE_MACHINE_FIXAABB},    // KERNEL_STATE_MACHINE with the opt-in slab test
+    {KERNEL_RETIRED_5,                 "(retired)",                       0,                          FAMILY_RETIRED,       0,                0,               false, false, KERNEL_RETIRED_5},                // round 2's LDS walk pool and its fixed-AABB form: removed in round 5, numbers kept so that the
+    {KERNEL_RETIRED_6,                 "(retired)",                       0,                          FAMILY_RETIRED,       0,                0,               false, false, KERNEL_RETIRED_6},                //   others stay what logs and tests of earlier rounds call them; no library holds them
+    {KERNEL_WAVEFRONT,                 "k_render_ctr_wf",                 BLOCK_THREADS_WF,           FAMILY_WAVEFRONT,     MATS_ALL,         PRIMS_ALL,       false, true,  KERNEL_WAVEFRONT_FIXAABB},        // path state in LDS, stages as queues: every pass runs with (nearly) full lanes (scenes with meshes)
+    {KERNEL_WAVEFRONT_FIXAABB,         "k_render_ctr_wf_fixaabb",         BLOCK_THREADS_WF,           FAMILY_WAVEFRONT,     MATS_ALL,         PRIMS_ALL,       false, false, KERNEL_WAVEFRONT_FIXAABB},        // KERNEL_WAVEFRONT with the opt-in slab test: the form of every product kernel that walks meshes
+    {KERNEL_LOCKSTEP_NOSPEC,           "k_render_ctr_nospec",             BLOCK_THREADS,              FAMILY_LOCKSTEP,      MATS_NO_SPECULAR, PRIMS_MESH_FREE, false, true,  KERNEL_LOCKSTEP_NOSPEC},          // KERNEL_LOCKSTEP without the metal and dielectric branches: 72 VGPRs = 7 waves per SIMD (veach-mis)
+    {KERNEL_WAVEFRONT_NOMETAL,         "k_render_ctr_wf_nometal",         BLOCK_THREADS_WF,           FAMILY_WAVEFRONT,     MATS_NO_METAL,    PRIMS_ALL,       false, true,  KERNEL_WAVEFRONT_FIXAABB},        // KERNEL_WAVEFRONT without the metal branch (teapot, semesterbild)
+    {KERNEL_WAVEFRONT_MESHFREE,        "k_render_ctr_wf_meshfree",        BLOCK_THREADS_WF_MESHFREE,  FAMILY_WAVEFRONT,     MATS_NO_SPECULAR, PRIMS_MESH_FREE, false, true,  KERNEL_WAVEFRONT_MESHFREE},       // the wavefront for lists WITHOUT a mesh, no metal / dielectric: material-sorted SHADE passes for scenes whose materials diverge (veach-mis)
+    {KERNEL_WAVEFRONT_NOMETAL_IDENT,   "k_render_ctr_wf_nometal_ident",   BLOCK_THREADS_WF,           FAMILY_WAVEFRONT,     MATS_NO_METAL,    PRIMS_ALL,       true,  true,  KERNEL_WAVEFRONT_FIXAABB},        // KERNEL_WAVEFRONT_NOMETAL for lists whose meshes are all untransformed (teapot): mesh_setup without its matrix products
+    {KERNEL_WAVEFRONT_NOMETAL_SHALLOW, "k_render_ctr_wf_nometal_shallow", BLOCK_THREADS_WF,           FAMILY_WAVEFRONT,     MATS_NO_METAL,    PRIMS_ALL,       false, true,  KERNEL_WAVEFRONT_FIXAABB},        // KERNEL_WAVEFRONT_NOMETAL for lists whose meshes all have small trees (semesterbild): WALK passes of 3 x 6 instead of 3 x 8 box tests (only a tuning: any tree is walked correctly)
+    {KERNEL_LOCKSTEP_SIMPLE_QC,        "k_render_ctr_simple_qc",          BLOCK_THREADS,              FAMILY_LOCKSTEP,      MATS_LAMBERT,     PRIMS_QUAD_CUBE, false, true,  KERNEL_LOCKSTEP_SIMPLE_QC},       // KERNEL_LOCKSTEP_SIMPLE for lists of quads and cubes only (cornell): no sphere / plane run checks in the walk, a two-way finish_hit
+};
+constexpr bool variant_rows_in_order() { for (uint32_t v = 0; v < KERNEL_VARIANTS; ++v) if (VARIANT_TABLE[v].variant != v) return false; return true; }
+static_assert(variant_rows_in_order(), "row v of VARIANT_TABLE describes variant v");
 
 }  // namespace mi355rt

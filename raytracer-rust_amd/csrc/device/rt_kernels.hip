@@ -810,34 +810,26 @@ int launch_debug_hit(const DevPrim* prims, uint32_t n_prims, const DevNode* node
     hipLaunchKernelGGL(k_debug_hit, dim3((n + 63u) / 64u), dim3(64), 0, (hipStream_t)stream, prims, n_prims, nodes, tris, in, out, n);
     return (int)hipGetLastError();
 }
-int launch_render_ctr(const RenderParams& p, uint32_t variant, uint32_t grid_blocks, void* stream) {
-    switch (variant) {
-        case KERNEL_LOCKSTEP:        hipLaunchKernelGGL(k_render_ctr_nomesh, dim3(grid_blocks), dim3(BLOCK_THREADS), 0, (hipStream_t)stream, p); break;
-        case KERNEL_LOCKSTEP_MESH:   hipLaunchKernelGGL(k_render_ctr_mesh, dim3(grid_blocks), dim3(BLOCK_THREADS), 0, (hipStream_t)stream, p); break;
-        case KERNEL_LOCKSTEP_SIMPLE: hipLaunchKernelGGL(k_render_ctr_simple, dim3(grid_blocks), dim3(BLOCK_THREADS), 0, (hipStream_t)stream, p); break;
-        case KERNEL_LOCKSTEP_SIMPLE_QC: hipLaunchKernelGGL(k_render_ctr_simple_qc, dim3(grid_blocks), dim3(BLOCK_THREADS), 0, (hipStream_t)stream, p); break;
-        case KERNEL_LOCKSTEP_NOSPEC: hipLaunchKernelGGL(k_render_ctr_nospec, dim3(grid_blocks), dim3(BLOCK_THREADS), 0, (hipStream_t)stream, p); break;
-        case KERNEL_WAVEFRONT_MESHFREE: hipLaunchKernelGGL(k_render_ctr_wf_meshfree, dim3(grid_blocks), dim3(BLOCK_THREADS_WF_MESHFREE), 0, (hipStream_t)stream, p); break;
-        case KERNEL_WAVEFRONT_NOMETAL: hipLaunchKernelGGL(k_render_ctr_wf_nometal, dim3(grid_blocks), dim3(BLOCK_THREADS_WF), 0, (hipStream_t)stream, p); break;
-        case KERNEL_WAVEFRONT_NOMETAL_IDENT: hipLaunchKernelGGL(k_render_ctr_wf_nometal_ident, dim3(grid_blocks), dim3(BLOCK_THREADS_WF), 0, (hipStream_t)stream, p); break;
-        case KERNEL_WAVEFRONT_NOMETAL_SHALLOW: hipLaunchKernelGGL(k_render_ctr_wf_nometal_shallow, dim3(grid_blocks), dim3(BLOCK_THREADS_WF), 0, (hipStream_t)stream, p); break;
-        case KERNEL_WAVEFRONT:       hipLaunchKernelGGL(k_render_ctr_wf, dim3(grid_blocks), dim3(BLOCK_THREADS_WF), 0, (hipStream_t)stream, p); break;
-        case KERNEL_WAVEFRONT_FIXAABB: hipLaunchKernelGGL(k_render_ctr_wf_fixaabb, dim3(grid_blocks), dim3(BLOCK_THREADS_WF), 0, (hipStream_t)stream, p); break;
+// The counter-mode kernels by variant (rt_device.h, VARIANT_TABLE); null where this build holds none: the reference build's state machine
+// outside -DMI355RT_REFS, the retired numbers always.
+#define KFN(k) reinterpret_cast<const void*>(k)
 #ifdef MI355RT_REFS
-        case KERNEL_STATE_MACHINE_FIXAABB: hipLaunchKernelGGL(k_render_ctr_sm_fixaabb, dim3(grid_blocks), dim3(BLOCK_THREADS_SM), 0, (hipStream_t)stream, p); break;
-        case KERNEL_STATE_MACHINE:   hipLaunchKernelGGL(k_render_ctr_sm, dim3(grid_blocks), dim3(BLOCK_THREADS_SM), 0, (hipStream_t)stream, p); break;
-#endif
-        default: return -1;                                  // a variant this library was not built with (render_ctr_variant_built)
-    }
-    return (int)hipGetLastError();
-}
-bool render_ctr_variant_built(uint32_t variant) {
-#ifdef MI355RT_REFS
-    return variant < KERNEL_VARIANTS && variant != KERNEL_RETIRED_5 && variant != KERNEL_RETIRED_6;
+#define REFS_KFN(k) KFN(k)
 #else
-    return variant == KERNEL_LOCKSTEP || variant == KERNEL_LOCKSTEP_MESH || variant == KERNEL_LOCKSTEP_SIMPLE || variant == KERNEL_LOCKSTEP_SIMPLE_QC || variant == KERNEL_LOCKSTEP_NOSPEC ||
-           is_wavefront(variant);
+#define REFS_KFN(k) nullptr
 #endif
+static const void* const render_ctr_kernel[KERNEL_VARIANTS] = {
+    KFN(k_render_ctr_nomesh), KFN(k_render_ctr_mesh), REFS_KFN(k_render_ctr_sm), KFN(k_render_ctr_simple), REFS_KFN(k_render_ctr_sm_fixaabb),
+    nullptr, nullptr, KFN(k_render_ctr_wf), KFN(k_render_ctr_wf_fixaabb), KFN(k_render_ctr_nospec), KFN(k_render_ctr_wf_nometal),
+    KFN(k_render_ctr_wf_meshfree), KFN(k_render_ctr_wf_nometal_ident), KFN(k_render_ctr_wf_nometal_shallow), KFN(k_render_ctr_simple_qc)};
+#undef KFN
+#undef REFS_KFN
+bool render_ctr_variant_built(uint32_t variant) { return variant < KERNEL_VARIANTS && render_ctr_kernel[variant]; }
+int launch_render_ctr(const RenderParams& p, uint32_t variant, uint32_t grid_blocks, void* stream) {
+    if (!render_ctr_variant_built(variant)) return -1;
+    void* args[] = {const_cast<RenderParams*>(&p)};
+    (void)hipLaunchKernel(render_ctr_kernel[variant], dim3(grid_blocks), dim3(VARIANT_TABLE[variant].block_threads), args, 0, (hipStream_t)stream);
+    return (int)hipGetLastError();
 }
 int launch_resolve(const ResolveParams& p, void* stream) {
     const uint32_t blocks = (p.band_pixels + 15u) / 16u;         // 4 waves x 4 pixels per block
@@ -862,23 +854,9 @@ int launch_render_ref(const RefParams& p, void* stream) {
 }
 int query_render_ctr_occupancy(uint32_t variant, int* blocks_per_cu, int* vgprs, int* sgprs) {
     if (!render_ctr_variant_built(variant)) return -1;
-    const void* fn = variant == KERNEL_LOCKSTEP ? reinterpret_cast<const void*>(k_render_ctr_nomesh)
-                   : variant == KERNEL_LOCKSTEP_MESH ? reinterpret_cast<const void*>(k_render_ctr_mesh)
-                   : variant == KERNEL_LOCKSTEP_SIMPLE ? reinterpret_cast<const void*>(k_render_ctr_simple)
-                   : variant == KERNEL_LOCKSTEP_SIMPLE_QC ? reinterpret_cast<const void*>(k_render_ctr_simple_qc)
-                   : variant == KERNEL_LOCKSTEP_NOSPEC ? reinterpret_cast<const void*>(k_render_ctr_nospec)
-                   : variant == KERNEL_WAVEFRONT_NOMETAL ? reinterpret_cast<const void*>(k_render_ctr_wf_nometal)
-                   : variant == KERNEL_WAVEFRONT_NOMETAL_IDENT ? reinterpret_cast<const void*>(k_render_ctr_wf_nometal_ident)
-                   : variant == KERNEL_WAVEFRONT_NOMETAL_SHALLOW ? reinterpret_cast<const void*>(k_render_ctr_wf_nometal_shallow)
-                   : variant == KERNEL_WAVEFRONT_MESHFREE ? reinterpret_cast<const void*>(k_render_ctr_wf_meshfree)
-                   : variant == KERNEL_WAVEFRONT ? reinterpret_cast<const void*>(k_render_ctr_wf)
-#ifdef MI355RT_REFS
-                   : variant == KERNEL_STATE_MACHINE_FIXAABB ? reinterpret_cast<const void*>(k_render_ctr_sm_fixaabb)
-                   : variant == KERNEL_STATE_MACHINE ? reinterpret_cast<const void*>(k_render_ctr_sm)
-#endif
-                                                       : reinterpret_cast<const void*>(k_render_ctr_wf_fixaabb);
+    const void* fn = render_ctr_kernel[variant];
     int nb = 0;
-    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, (int)block_threads_of(variant), 0);
+    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, (int)VARIANT_TABLE[variant].block_threads, 0);
     if (e != hipSuccess) return (int)e;
     hipFuncAttributes fa;
     e = hipFuncGetAttributes(&fa, fn);

@@ -183,38 +183,62 @@ def _source(path):
     return re.sub(r"\s+", " ", open(os.path.join(ROOT, path)).read())
 
 
-def test_ledger_table_follows_set_scenes_rules():
-    """The table restated from rt_device.h / rt_api.cpp: mats_of_variant's sets, prims_of_variant, and set_scene's forced-variant check
-    (selectable, mesh-free only, the untransformed form's condition)."""
+def test_ledger_table_follows_the_librarys_variant_table():
+    """The table restated from the library's own description of its variants (rt_device.h VARIANT_TABLE: materials, primitive kinds, the
+    untransformed-mesh condition, forceability, the fixed-AABB form, the kernel name and workgroup), the kernel pointers rt_kernels.hip launches
+    by it, and set_scene's forced-variant check that reads it (rt_api.cpp)."""
+    import importlib
     dev = _source("raytracer-rust_amd/csrc/device/rt_device.h")
     api = _source("raytracer-rust_amd/csrc/device/rt_api.cpp")
+    hip = _source("raytracer-rust_amd/csrc/device/rt_kernels.hip")
     num = {name: int(v) for name, v in re.findall(r"\b(KERNEL_\w+) = (\d+)", dev)}
-    kinds = {"METAL": METAL, "DIELECTRIC": DIELECTRIC, "LAMBERT_SOLID": LAMBERT, "EMISSIVE": EMISSIVE, "NULL": NULL}
+    kinds = {"MAT_METAL": METAL, "MAT_DIELECTRIC": DIELECTRIC, "MAT_LAMBERT_SOLID": LAMBERT, "MAT_EMISSIVE": EMISSIVE, "MAT_NULL": NULL,
+             "PRIM_SPHERE": SPHERE, "PRIM_PLANE": PLANE, "PRIM_QUAD": QUAD, "PRIM_CUBE": CUBE, "PRIM_MESH": MESH}
+    assert "constexpr uint32_t MATS_ALL = (1u << MI355RT_MAT_KIND_COUNT) - 1u;" in dev and "constexpr uint32_t PRIMS_ALL = 0xFFFFFFFFu;" in dev
 
-    def matset(name):                                            # MATS_X = MATS_Y [| or & ~] MATBIT(...) ... , evaluated
+    def kindset(name):                                           # MATS_X / PRIMS_X = [MATS_Y | PRIMS_Y] [| or & ~] MATBIT(...) / (1u << ...) ..., evaluated
+        if name in ("0", "MATS_ALL", "PRIMS_ALL"):
+            return {"0": frozenset(), "MATS_ALL": MATS_ALL, "PRIMS_ALL": PRIMS_ALL}[name]
         expr = re.search(rf"constexpr uint32_t {name} = ([^;]+);", dev).group(1)
-        if name == "MATS_ALL":
-            return MATS_ALL
-        head = re.match(r"(MATS_\w+|MATBIT\(MI355RT_MAT_\w+\))", expr).group(1)
-        out = set(matset(head)) if head.startswith("MATS_") else {kinds[head[len("MATBIT(MI355RT_MAT_"):-1]]}
-        bits = {kinds[k] for k in re.findall(r"MATBIT\(MI355RT_MAT_(\w+)\)", expr[len(head):])}
+        head = re.match(r"(MATS_\w+|PRIMS_\w+)", expr)
+        out = set(kindset(head.group(1))) if head else set()
+        bits = {kinds[k] for k in re.findall(r"(?:MATBIT\(|1u << )MI355RT_(\w+?)\)", expr)}
         return frozenset(out - bits if "& ~" in expr else out | bits)
 
-    body = re.search(r"inline uint32_t mats_of_variant\(uint32_t variant\) \{(.*?)\}", dev).group(1)
-    rules = {num[v]: matset(m) for cond, m in re.findall(r"\(([^()?]*)\) \? (MATS_\w+)", body) for v in re.findall(r"variant == (\w+)", cond)}
-    assert body.strip().endswith(": MATS_ALL;"), body
-    for v, (_, _, mats, prims, meshes) in CAPABILITY.items():
-        assert rules.get(v, MATS_ALL) == mats, (v, sorted(rules.get(v, MATS_ALL)), sorted(mats))
-    qc = re.search(r"inline uint32_t prims_of_variant\(uint32_t variant\) \{ return variant == (\w+) \? PRIMS_QUAD_CUBE : PRIMS_ALL; \}", dev).group(1)
-    for v, c in CAPABILITY.items():                              # (a mesh-free-only variant takes no mesh: the forced-variant check below)
-        assert c[3] == (PRIMS_QC if v == num[qc] else PRIMS_MESH_FREE if c[4] == "free" else PRIMS_ALL), v
-    selectable = re.search(r"const bool selectable = ([^;]+);", api).group(1)
-    assert {num[n] for n in re.findall(r"v == (\w+)", selectable)} == set(CAPABILITY)
-    free = re.search(r"const bool mesh_free_only = ([^;]+);", api).group(1)
-    assert {num[n] for n in re.findall(r"v == (\w+)", free)} == {v for v, c in CAPABILITY.items() if c[4] == "free"}
-    assert "!(v == KERNEL_WAVEFRONT_NOMETAL_IDENT && !(has_mesh && all_meshes_identity))" in api
-    assert {v for v, c in CAPABILITY.items() if c[4] == "identity"} == {num["KERNEL_WAVEFRONT_NOMETAL_IDENT"]}
-    assert {num["KERNEL_WAVEFRONT_FIXAABB"], num["KERNEL_STATE_MACHINE_FIXAABB"]} == set(FLAG_FORMS)
+    body = re.search(r"constexpr VariantInfo VARIANT_TABLE\[KERNEL_VARIANTS\] = \{(.*?)\};", dev).group(1)
+    rows = re.findall(r"\{(KERNEL_\w+), \"([^\"]+)\", (\w+), (FAMILY_\w+), (\w+), (\w+), (true|false), (true|false), (KERNEL_\w+)\}", body)
+    assert [num[r[0]] for r in rows] == list(range(num["KERNEL_VARIANTS"])), "one row per variant, in order"
+    table = {num[r[0]]: dict(kernel=r[1], block=_header_int("raytracer-rust_amd/csrc/device/rt_device.h", r[2]) if r[2] != "0" else 0, family=r[3],
+                             mats=kindset(r[4]), prims=kindset(r[5]), identity=r[6] == "true", forceable=r[7] == "true", fixed_aabb=num[r[8]]) for r in rows}
+    bench = importlib.import_module("bench")
+    assert {v: t["kernel"] for v, t in table.items()} == bench.KERNEL_NAMES
+    form_of = {of: f for f, (_, _, of) in FLAG_FORMS.items()}    # the variant a flag form stands for -> the form (None: every other one that walks meshes)
+    for v, (kernel, _, mats, prims, meshes) in CAPABILITY.items():
+        t = table[v]
+        assert (t["kernel"], t["mats"], t["prims"], t["forceable"]) == (kernel, mats, prims, True), (v, t)
+        assert (MESH not in t["prims"]) == (meshes == "free") and t["identity"] == (meshes == "identity"), (v, t)
+        form = v if meshes == "free" else form_of.get(v, form_of[None])
+        assert t["fixed_aabb"] == form, (v, t["fixed_aabb"], form)
+    for v, (kernel, _, of) in FLAG_FORMS.items():              # a flag form accepts what the kernel it stands for does, and is its own form
+        t, base = table[v], CAPABILITY[of if of is not None else 7]
+        assert (t["kernel"], t["mats"], t["prims"], t["forceable"], t["identity"], t["fixed_aabb"]) == (kernel, base[2], base[3], False, False, v), (v, t)
+    for v in RETIRED:
+        t = table[v]
+        assert (t["kernel"], t["family"], t["forceable"], t["mats"], t["prims"]) == ("(retired)", "FAMILY_RETIRED", False, frozenset(), frozenset()), (v, t)
+    for v in SHAPE_VARIANTS:
+        assert table[v]["block"] == block_threads(v), v
+    # rt_kernels.hip's kernel pointers, indexed by variant: each row's kernel, the reference build's only under -DMI355RT_REFS, none for the retired
+    fns = re.search(r"static const void\* const render_ctr_kernel\[KERNEL_VARIANTS\] = \{(.*?)\};", hip).group(1)
+    lib = {v: c[1] for v, c in list(CAPABILITY.items()) + list(FLAG_FORMS.items())}
+    expect = ["nullptr" if v in RETIRED else f"{'REFS_' if lib[v] == 'refs' else ''}KFN({t['kernel']})" for v, t in sorted(table.items())]
+    assert re.findall(r"(?:REFS_)?KFN\(\w+\)|nullptr", fns) == expect, fns
+    # set_scene's forced-variant check and render_samples' flag form read the table
+    assert "auto covers = [&](uint32_t variant) { return (scene_mats & ~VARIANT_TABLE[variant].mats) == 0u; };" in api
+    assert "auto kinds_covered = [&](uint32_t variant) { return (scene_prim_kinds & ~VARIANT_TABLE[variant].prims) == 0u; };" in api
+    ok = re.search(r"const bool ok = ([^;]+);", api).group(1)
+    assert ok == ("render_ctr_variant_built(v) && VARIANT_TABLE[v].forceable && covers(v) && kinds_covered(v) && "
+                  "!(VARIANT_TABLE[v].identity_meshes && !(has_mesh && all_meshes_identity))"), ok
+    assert "if (fixed_aabb && ctx->has_mesh) variant = VARIANT_TABLE[variant].fixed_aabb;" in api
 
 
 def test_families_hold_what_the_ledger_plans(native, abi):
@@ -291,7 +315,7 @@ def _forced(v):
 
 
 def block_threads(v):
-    """The workgroup size the render launch of variant v reports (rt_device.h block_threads_of): it tells the kernel families apart, so a
+    """The workgroup size the render launch of variant v reports (rt_device.h VARIANT_TABLE): it tells the kernel families apart, so a
     flagged render that fell back from the state machine's form (4) to the wavefront's (8) is seen."""
     return 1024 if v in (2, 4, 11) else 768 if v in (7, 8, 10, 12, 13) else 256
 
