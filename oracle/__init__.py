@@ -78,6 +78,9 @@ def lib():
                                          C.c_void_p]
         L.oracle_sort_paths.restype = None
         L.oracle_sort_paths.argtypes = [C.POINTER(C.c_uint64), C.c_int]
+        L.oracle_debug_stages.restype = C.c_int
+        L.oracle_debug_stages.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_int, C.c_void_p]
         L.oracle_bvh_dump.restype = C.c_int
         L.oracle_bvh_dump.argtypes = [C.POINTER(abi.Triangle), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
@@ -148,6 +151,26 @@ def render(scene, camera, settings, options=None, threads=0, fold=-1, want_linea
     if rc != 0:
         raise RuntimeError(f"oracle_render failed: {rc}")
     return packed, linear, cnt
+
+
+def debug_stages(args, n, in4=None, mat=None, tex=None, sky=None, dev=None, want_words=False, threads=1):
+    """oracle_debug_stages: the stage of `args` (a device.StageArgs) on n elements through the oracle's own functions, compared with the device's
+    words `dev` (uint32 [n, words]) if given.  tex: an abi.Texture; sky: float32 [img_h, img_w, 3].  Returns (res float64 [64], the oracle's
+    words uint32 [n, words] or None); res's layout is documented at oracle_debug_stages in rt_oracle.cpp.  threads: the worker threads
+    (tests pass tests/parity.py oracle_threads(); 0 would take every hardware thread of the machine)."""
+    W = 1 if args.stage in (2, 3) else (0 if args.stage >= 6 else 8)
+    ora = np.zeros((n, W), np.uint32) if want_words and W else None
+    res = np.zeros(64, np.float64)
+    arrays = [None if a is None else np.ascontiguousarray(a) for a in (in4, sky, dev)]
+    ptrs = [None if a is None else a.ctypes.data for a in arrays]
+    if dev is not None and arrays[2].size != n * W:
+        raise ValueError("dev holds the wrong number of words")
+    rc = lib().oracle_debug_stages(C.addressof(args), n, ptrs[0], C.addressof(mat) if mat is not None else None,
+                                   C.addressof(tex) if tex is not None else None, ptrs[1], ptrs[2],
+                                   None if ora is None else ora.ctypes.data, threads, res.ctypes.data)
+    if rc != 0:
+        raise RuntimeError(f"oracle_debug_stages failed: {rc}")
+    return res, ora
 
 
 def scene_hit(scene, origin, direction):

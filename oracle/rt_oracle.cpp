@@ -848,40 +848,80 @@ inline float beckmann_lambda(float a, float x) {                                
 inline float beckmann_g(float roughness, float ndv, float ndl) {                      // tungsten/materials.rs:223-234
     return 1.0f / (1.0f + beckmann_lambda(roughness, ndv) + beckmann_lambda(roughness, ndl));
 }
+// ln / atan / sin / cos of the microfacet sampling in a sampler's form (S::exact_libm: in double, rounded once; otherwise the platform's
+// float functions) -- one definition for the render and for oracle_debug_stages.
+template <bool EXACT> struct MicrofacetLibm {
+    static float ln(float x) { return EXACT ? (float)std::log((double)x) : std::log(x); }
+    static float at(float x) { return EXACT ? (float)std::atan((double)x) : std::atan(x); }
+    static float sn(float x) { return EXACT ? (float)std::sin((double)x) : std::sin(x); }
+    static float cs(float x) { return EXACT ? (float)std::cos((double)x) : std::cos(x); }
+};
+template <bool EXACT> float microfacet_theta_arg(bool ggx, float roughness, float u1) {
+    using M = MicrofacetLibm<EXACT>;
+    if (ggx) { float a = roughness * roughness; return a * a * (-M::ln(u1)) / (1.0f - u1); }
+    return -(roughness * roughness * M::ln(u1));
+}
 template <class S> V3 sample_half_vector(bool ggx, V3 normal, float roughness, S& rng) {   // tungsten/materials.rs:236-290
     if (has_nan(normal) || is_zero_vec(normal)) return nan3();
+    using M = MicrofacetLibm<S::exact_libm>;
     float u1 = std::fmax(rng.uniform01(0), 1e-6f);
     float u2 = rng.uniform01(1);
-    float theta_arg;
-    auto ln = [](float x) { return S::exact_libm ? (float)std::log((double)x) : std::log(x); };
-    auto at = [](float x) { return S::exact_libm ? (float)std::atan((double)x) : std::atan(x); };
-    auto sn = [](float x) { return S::exact_libm ? (float)std::sin((double)x) : std::sin(x); };
-    auto cs = [](float x) { return S::exact_libm ? (float)std::cos((double)x) : std::cos(x); };
-    if (ggx) { float a = roughness * roughness; theta_arg = a * a * (-ln(u1)) / (1.0f - u1); }
-    else     { theta_arg = -(roughness * roughness * ln(u1)); }
+    float theta_arg = microfacet_theta_arg<S::exact_libm>(ggx, roughness, u1);
     if (std::isnan(theta_arg) || std::isinf(theta_arg) || theta_arg < 0.0f) return to_world(v3(0, 0, 1), normal);
-    float theta = at(std::sqrt(theta_arg));
+    float theta = M::at(std::sqrt(theta_arg));
     float phi = 2.0f * PI_F * u2;
-    float sin_theta = sn(theta), cos_theta = cs(theta);
-    V3 h_local = {sin_theta * cs(phi), sin_theta * sn(phi), cos_theta};
+    float sin_theta = M::sn(theta), cos_theta = M::cs(theta);
+    V3 h_local = {sin_theta * M::cs(phi), sin_theta * M::sn(phi), cos_theta};
     if (has_nan(h_local)) return to_world(v3(0, 0, 1), normal);
     return to_world(h_local, normal);
 }
 
 // TextureMaterial (tungsten/parser.rs:199-243).  The images of the scene being rendered; set by build_scene() /
 // oracle_set_textures() before any worker thread starts, read-only afterwards.
-static Col texture_value(const mi355rt_material& m, V3 normal_tex) {                  // parser.rs:222-241
-    if (m.texture >= g_n_textures) return BLACK;
-    const mi355rt_texture& t = g_textures[m.texture];
+static Col texture_texel(const mi355rt_texture& t, float h_offset, V3 normal_tex) {   // parser.rs:222-241
     float theta = std::acos(normal_tex.y);
     float phi = std::atan2(normal_tex.z, normal_tex.x) + PI_F;
     float u = phi / (2.0f * PI_F);
     float v = theta / PI_F;
-    u = std::fmod(u + m.p0, 1.0f);                                                    // f32 % f32
+    u = std::fmod(u + h_offset, 1.0f);                                                // f32 % f32
     uint32_t x_pixel = rust_as_u32(std::fmax(u, 0.0f) * (float)(t.width - 1));
     uint32_t y_pixel = rust_as_u32(std::fmax(v, 0.0f) * (float)(t.height - 1));
     const uint8_t* px = t.rgba8 + 4 * ((size_t)std::min(y_pixel, t.height - 1) * t.width + std::min(x_pixel, t.width - 1));
     return {(float)px[0] / 255.0f, (float)px[1] / 255.0f, (float)px[2] / 255.0f};
+}
+static Col texture_value(const mi355rt_material& m, V3 normal_tex) {
+    if (m.texture >= g_n_textures) return BLACK;
+    return texture_texel(g_textures[m.texture], m.p0, normal_tex);
+}
+
+// RoughConductor::scatter (tungsten/materials.rs:306-377) up to the scattered direction `l` before Ray::new -- shared by scatter() and
+// oracle_debug_stages.  Returns false for None.
+template <class S> bool rough_conductor(const mi355rt_material& m, V3 ray_dir, V3 normal, S& rng, V3& l_out, Col& atten) {
+    bool ggx = m.kind == MI355RT_MAT_ROUGH_GGX;
+    if (has_nan(ray_dir)) return false;
+    if (has_nan(normal) || is_zero_vec(normal)) return false;
+    V3 n = normal;
+    V3 v = -normalized(ray_dir);
+    if (has_nan(v)) return false;
+    Col eta = {m.eta[0], m.eta[1], m.eta[2]}, k = {m.k[0], m.k[1], m.k[2]};
+    float rough = m.p0;
+    V3 hv = sample_half_vector(ggx, n, rough, rng);
+    if (has_nan(hv)) return false;
+    V3 l = mat_reflect(-v, hv);
+    if (has_nan(l)) return false;
+    if (dot(l, n) <= 0.0f) return false;
+    float n_dot_l = std::fmax(dot(n, l), 0.0f);
+    float n_dot_v = std::fmax(dot(n, v), 0.0f);
+    float n_dot_h = std::fmax(dot(n, hv), 0.0f);
+    float v_dot_h = std::fmax(dot(v, hv), 0.0f);
+    float g = ggx ? ggx_g(rough, n_dot_v, n_dot_l) : beckmann_g(rough, n_dot_v, n_dot_l);
+    Col f = fresnel_conductor(v_dot_h, eta, k);
+    Col brdf_numerator = f * g * v_dot_h;
+    float brdf_denominator = n_dot_v * n_dot_h + EPSILON;
+    Col albedo = {m.albedo[0], m.albedo[1], m.albedo[2]};
+    atten = (brdf_denominator > EPSILON) ? albedo * cdivf(brdf_numerator, brdf_denominator) : BLACK;
+    l_out = l;
+    return true;
 }
 
 // Material::scatter for all kinds.  Returns false for None.
@@ -952,30 +992,9 @@ bool scatter(const mi355rt_material& m, const Ray& ray_in, const HitRecord& h, S
     }
     case MI355RT_MAT_ROUGH_GGX:
     case MI355RT_MAT_ROUGH_BECKMANN: {                                                // tungsten/materials.rs:306-377
-        bool ggx = m.kind == MI355RT_MAT_ROUGH_GGX;
-        if (has_nan(ray_in.direction)) return false;
-        if (has_nan(h.normal) || is_zero_vec(h.normal)) return false;
-        V3 n = h.normal;
-        V3 v = -normalized(ray_in.direction);
-        if (has_nan(v)) return false;
-        Col eta = {m.eta[0], m.eta[1], m.eta[2]}, k = {m.k[0], m.k[1], m.k[2]};
-        float rough = m.p0;
-        V3 hv = sample_half_vector(ggx, n, rough, rng);
-        if (has_nan(hv)) return false;
-        V3 l = mat_reflect(-v, hv);
-        if (has_nan(l)) return false;
-        if (dot(l, n) <= 0.0f) return false;
-        float n_dot_l = std::fmax(dot(n, l), 0.0f);
-        float n_dot_v = std::fmax(dot(n, v), 0.0f);
-        float n_dot_h = std::fmax(dot(n, hv), 0.0f);
-        float v_dot_h = std::fmax(dot(v, hv), 0.0f);
-        float g = ggx ? ggx_g(rough, n_dot_v, n_dot_l) : beckmann_g(rough, n_dot_v, n_dot_l);
-        Col f = fresnel_conductor(v_dot_h, eta, k);
-        Col brdf_numerator = f * g * v_dot_h;
-        float brdf_denominator = n_dot_v * n_dot_h + EPSILON;
-        Col albedo = {m.albedo[0], m.albedo[1], m.albedo[2]};
-        atten = (brdf_denominator > EPSILON) ? albedo * cdivf(brdf_numerator, brdf_denominator) : BLACK;
-        scattered = ray_new(h.position + n * EPSILON, normalized(l));
+        V3 l;
+        if (!rough_conductor(m, ray_in.direction, h.normal, rng, l, atten)) return false;
+        scattered = ray_new(h.position + h.normal * EPSILON, normalized(l));
         return true;
     }
     }
@@ -987,17 +1006,20 @@ inline Col emitted(const mi355rt_material& m) {                                 
 }
 
 // renderer.rs:38-63 -- what a missing ray returns
-inline Col miss_colour(const Scene& sc, const Ray& ray_in) {
-    if (sc.sky_w == 0) return sc.miss;                                                // :61
-    V3 dir = normalized(ray_in.direction);                                            // :41
+inline Col sky_lookup(const float* sky, uint32_t sky_w, uint32_t sky_h, V3 direction) {   // :41-54, also oracle_debug_stages'
+    V3 dir = normalized(direction);                                                   // :41
     float theta = std::acos(dir.y);                                                   // :42
     float phi = std::atan2(dir.z, dir.x) + PI_F;                                      // :43
     float u = phi / (2.0f * PI_F);                                                    // :44
     float v = theta / PI_F;                                                           // :45
-    uint32_t xp = rust_as_u32(std::fmax(u * (float)(sc.sky_w - 1), 0.0f));            // :47
-    uint32_t yp = rust_as_u32(std::fmax(v * (float)(sc.sky_h - 1), 0.0f));            // :48
-    size_t o = 3 * ((size_t)std::min(yp, sc.sky_h - 1) * sc.sky_w + std::min(xp, sc.sky_w - 1));   // :50-53
-    return {sc.sky[o], sc.sky[o + 1], sc.sky[o + 2]};                                 // :54
+    uint32_t xp = rust_as_u32(std::fmax(u * (float)(sky_w - 1), 0.0f));               // :47
+    uint32_t yp = rust_as_u32(std::fmax(v * (float)(sky_h - 1), 0.0f));               // :48
+    size_t o = 3 * ((size_t)std::min(yp, sky_h - 1) * sky_w + std::min(xp, sky_w - 1));   // :50-53
+    return {sky[o], sky[o + 1], sky[o + 2]};                                          // :54
+}
+inline Col miss_colour(const Scene& sc, const Ray& ray_in) {
+    if (sc.sky_w == 0) return sc.miss;                                                // :61
+    return sky_lookup(sc.sky.data(), sc.sky_w, sc.sky_h, ray_in.direction);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1250,6 +1272,250 @@ int oracle_bvh_dump(const mi355rt_triangle* tris_in, uint32_t n, float* bounds, 
     if (n_nodes_out) *n_nodes_out = ni;
     if (n_leaf_ids_out) *n_leaf_ids_out = li;
     if (max_depth_out) *max_depth_out = md;
+    return MI355RT_OK;
+}
+
+}  // extern "C"
+
+// ================================================================================================================================================
+// oracle_debug_stages -- the twin of the device's mi355rt_debug_stages (the tests' reference build, csrc/refs/rt_stages.hip): the same stages on
+// the same inputs through the oracle's own functions (sample_half_vector via rough_conductor, texture_texel, sky_lookup), a float64
+// reference of every transcendental rounded once, and the comparison with the device's words chunk by chunk (tests/test_gpu_transcendental_stages.py).
+// ================================================================================================================================================
+namespace {
+
+enum : uint32_t { STAGE_LATTICE = 0, STAGE_HALF = 1, STAGE_ACOS = 2, STAGE_ATAN2 = 3, STAGE_TEX = 4, STAGE_SKY = 5, STAGE_ATAN2_EXACT = 6,
+                  STAGE_FMOD_EXACT = 7 };
+constexpr uint64_t STAGE_ACOS_POS = 0x3F800009u;
+struct StageArgs {                                    // the layout of rt_stages.hip's StageArgs
+    uint32_t stage, form;
+    uint64_t first, stride;
+    uint32_t ggx, axis, set, img_w;
+    uint32_t img_h, pad0;
+    float rough, fixed_u, h_offset, pad1;
+    float n[4], rd[4];
+};
+static_assert(sizeof(StageArgs) == 96, "StageArgs");
+constexpr uint32_t stage_words(uint32_t stage) { return (stage == STAGE_ACOS || stage == STAGE_ATAN2) ? 1u : (stage >= STAGE_ATAN2_EXACT ? 0u : 8u); }
+
+// The input rules of rt_stages.hip
+inline float stage_lattice_u(uint64_t k) { return u32_to_f01((uint32_t)k << 8); }
+inline float f_bits(uint32_t b) { float f; std::memcpy(&f, &b, 4); return f; }
+inline uint32_t bits_f(float f) { uint32_t b; std::memcpy(&b, &f, 4); return b; }
+inline float stage_acos_arg(uint64_t k) { return f_bits(k < STAGE_ACOS_POS ? (uint32_t)k : 0x80000000u | (uint32_t)(k - STAGE_ACOS_POS)); }
+inline V3 stage_dir(uint64_t k) {
+    uint32_t b[4];
+    pcg4d((uint32_t)k, (uint32_t)(k >> 32), 0x9E3779B9u, 0x7F4A7C15u, b);
+    return {u32_to_range11(b[0]), u32_to_range11(b[1]), u32_to_range11(b[2])};
+}
+template <bool EXACT> void stage_transcendentals(float u1_drawn, float u2, bool ggx, float rough, float o[8]) {
+    using M = MicrofacetLibm<EXACT>;
+    const float u1 = std::fmax(u1_drawn, 1e-6f);
+    o[0] = M::ln(u1); o[1] = microfacet_theta_arg<EXACT>(ggx, rough, u1); o[2] = M::at(std::sqrt(o[1]));
+    o[3] = M::sn(o[2]); o[4] = M::cs(o[2]); o[7] = 2.0f * PI_F * u2; o[5] = M::sn(o[7]); o[6] = M::cs(o[7]);
+}
+inline uint32_t stage_signature(const float t[8]) {
+    uint32_t h = 0x811C9DC5u;
+    for (int w = 0; w < 8; ++w) h = (h ^ (std::isnan(t[w]) ? 0x7FC00000u : bits_f(t[w]))) * 16777619u;
+    return h;
+}
+template <bool EXACT> struct SamplerStub {            // the two draws of the rough conductor, given
+    static constexpr bool exact_libm = EXACT;
+    float u[2];
+    float uniform01(int slot) { return u[slot]; }
+};
+
+// One element: the oracle's words `o` and the input the float64 references need.
+struct StageInput { float u1, u2; V3 d; };
+inline StageInput stage_input(const StageArgs& a, uint64_t i, const float* in4) {
+    const uint64_t k = a.first + i * a.stride;
+    StageInput s{0.f, 0.f, {0.f, 0.f, 0.f}};
+    if (in4) { const float* e = in4 + 4 * i; s.u1 = e[0]; s.u2 = e[1]; s.d = {e[0], e[1], e[2]}; }
+    if (a.stage == STAGE_LATTICE) { if (!in4) s.u1 = stage_lattice_u(k); s.u2 = s.u1; }
+    else if (a.stage == STAGE_HALF) {
+        if (!in4) { const float run = stage_lattice_u(k); s.u1 = a.axis == 0u ? run : a.fixed_u; s.u2 = a.axis == 0u ? a.fixed_u : run; }
+    }
+    else if (a.stage == STAGE_ACOS) { if (!in4) s.d.y = stage_acos_arg(k); else s.d.y = in4[4 * i]; }
+    else if (a.stage == STAGE_TEX) { if (!in4) s.d = normalized(stage_dir(k)); }
+    else if (!in4) s.d = stage_dir(k);                                                       // ATAN2, SKY
+    return s;
+}
+void stage_oracle(const StageArgs& a, const StageInput& s, const mi355rt_material* mat, const mi355rt_texture* tex, const float* sky, uint32_t o[8]) {
+    float f[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    for (int w = 0; w < 8; ++w) o[w] = 0u;
+    switch (a.stage) {
+    case STAGE_LATTICE:
+        if (a.form) stage_transcendentals<true>(s.u1, s.u2, a.ggx != 0u, a.rough, f); else stage_transcendentals<false>(s.u1, s.u2, a.ggx != 0u, a.rough, f);
+        for (int w = 0; w < 8; ++w) o[w] = bits_f(f[w]);
+        return;
+    case STAGE_HALF: {
+        V3 l = {0.f, 0.f, 0.f}; Col at = BLACK; bool ok;
+        float t[8];
+        const V3 rd = {a.rd[0], a.rd[1], a.rd[2]}, n = {a.n[0], a.n[1], a.n[2]};
+        if (a.form) { SamplerStub<true> g{{s.u1, s.u2}}; ok = rough_conductor(*mat, rd, n, g, l, at); stage_transcendentals<true>(s.u1, s.u2, a.ggx != 0u, a.rough, t); }
+        else { SamplerStub<false> g{{s.u1, s.u2}}; ok = rough_conductor(*mat, rd, n, g, l, at); stage_transcendentals<false>(s.u1, s.u2, a.ggx != 0u, a.rough, t); }
+        if (!ok) { l = {0.f, 0.f, 0.f}; at = BLACK; }
+        o[0] = bits_f(l.x); o[1] = bits_f(l.y); o[2] = bits_f(l.z); o[3] = bits_f(at.r); o[4] = bits_f(at.g); o[5] = bits_f(at.b);
+        o[6] = bits_f(ok ? 1.0f : 0.0f); o[7] = stage_signature(t);
+        return;
+    }
+    case STAGE_ACOS: o[0] = bits_f(std::acos(s.d.y)); return;
+    case STAGE_ATAN2: o[0] = bits_f(std::atan2(s.d.z, s.d.x)); return;
+    case STAGE_TEX: {
+        const Col c = texture_texel(*tex, a.h_offset, s.d);
+        const float phi = std::atan2(s.d.z, s.d.x);
+        o[0] = bits_f(c.r); o[1] = bits_f(c.g); o[2] = bits_f(c.b); o[3] = bits_f(std::acos(s.d.y)); o[4] = bits_f(phi);
+        o[5] = bits_f(std::fmod((phi + PI_F) / (2.0f * PI_F) + a.h_offset, 1.0f));
+        return;
+    }
+    case STAGE_SKY: {
+        const Col c = sky_lookup(sky, a.img_w, a.img_h, s.d);
+        const V3 d = normalized(s.d);
+        o[0] = bits_f(c.r); o[1] = bits_f(c.g); o[2] = bits_f(c.b); o[3] = bits_f(std::acos(d.y)); o[4] = bits_f(std::atan2(d.z, d.x));
+        return;
+    }
+    }
+}
+// The float64 reference of word w of a record `o` (from that record's own inputs: a side's theta comes from its own theta_arg), rounded
+// once; false for words that are not a transcendental's output.
+bool stage_ref(const StageArgs& a, const StageInput& s, const uint32_t o[8], int w, double& ref) {
+    const float* f = nullptr; float fo[8];
+    for (int j = 0; j < 8; ++j) fo[j] = f_bits(o[j]);
+    f = fo;
+    switch (a.stage) {
+    case STAGE_LATTICE:
+        if (w == 0) { ref = std::log((double)std::fmax(s.u1, 1e-6f)); return true; }
+        if (w == 2) { ref = std::atan((double)std::sqrt(f[1])); return true; }
+        if (w == 3) { ref = std::sin((double)f[2]); return true; }
+        if (w == 4) { ref = std::cos((double)f[2]); return true; }
+        if (w == 5) { ref = std::sin((double)f[7]); return true; }
+        if (w == 6) { ref = std::cos((double)f[7]); return true; }
+        return false;
+    case STAGE_ACOS: ref = std::acos((double)s.d.y); return w == 0;
+    case STAGE_ATAN2: ref = std::atan2((double)s.d.z, (double)s.d.x); return w == 0;
+    case STAGE_TEX:
+        if (w == 3) { ref = std::acos((double)s.d.y); return true; }
+        if (w == 4) { ref = std::atan2((double)s.d.z, (double)s.d.x); return true; }
+        if (w == 5) { ref = std::fmod((double)((f[4] + PI_F) / (2.0f * PI_F) + a.h_offset), 1.0); return true; }
+        return false;
+    case STAGE_SKY: {
+        const V3 d = normalized(s.d);
+        if (w == 3) { ref = std::acos((double)d.y); return true; }
+        if (w == 4) { ref = std::atan2((double)d.z, (double)d.x); return true; }
+        return false;
+    }
+    }
+    return false;
+}
+// Which words are a stage's final outputs and which are the transcendentals they are made from (attribution: final words may differ only
+// where one of those differs too)
+inline void stage_masks(uint32_t stage, uint32_t& final_mask, uint32_t& trans_mask) {
+    final_mask = trans_mask = 0u;
+    if (stage == STAGE_LATTICE) { final_mask = 0x02u; trans_mask = 0x01u; }     // theta_arg from ln(u1)
+    if (stage == STAGE_HALF) { final_mask = 0x7Fu; trans_mask = 0x80u; }
+    if (stage == STAGE_TEX) { final_mask = 0x07u; trans_mask = 0x38u; }
+    if (stage == STAGE_SKY) { final_mask = 0x07u; trans_mask = 0x18u; }
+}
+inline bool is_nan_bits(uint32_t b) { return (b & 0x7FFFFFFFu) > 0x7F800000u; }
+inline int64_t ordered(float f) { const uint32_t b = bits_f(f); return (b & 0x80000000u) ? -(int64_t)(b & 0x7FFFFFFFu) : (int64_t)b; }
+inline double ulps(uint32_t got_bits, double ref) {                          // distance in f32 steps from the reference rounded once; NaN = NaN
+    const float got = f_bits(got_bits), r = (float)ref;
+    if (std::isnan(got) || std::isnan(r)) return (std::isnan(got) && std::isnan(r)) ? 0.0 : 4294967295.0;
+    return (double)std::llabs(ordered(got) - ordered(r));
+}
+
+struct StageTally {
+    double diffs[8] = {0}, ulp_dev[8] = {0}, ulp_ora[8] = {0}, first_diff[8], unattributed = 0, first_unattributed = -1, final_differs = 0;
+    StageTally() { for (double& v : first_diff) v = -1; }
+};
+
+}  // namespace
+
+extern "C" {
+
+// The stage `args` (rt_stages.hip's StageArgs) on n elements: in4 = 4 explicit floats per element or null; mat (HALF), tex (TEX), sky
+// (SKY, img_w * img_h * 3 floats) as the device had them.  dev = the device's words (stage_words per element) or null; ora = where the
+// oracle's words go, or null.  res[64]: per word w < 8: [4w] elements whose device and oracle words differ (any NaN equals any NaN; HALF's
+// signature word bit for bit), [4w+1] the device's and [4w+2] the oracle's largest distance in f32 steps from the float64 reference (words
+// that are a transcendental's output), [4w+3] the first differing element or -1; [32] elements whose final words differ although every
+// transcendental word agrees, [33] the first of them or -1, [34] elements whose final words differ, [35] n.  FMOD_EXACT: res[0] = u in
+// [first, ...) (bit patterns) where std::fmod(u + h, 1) != a - floor(a), res[1] one of them.  threads <= 0: one per hardware thread.
+int oracle_debug_stages(const void* args, uint64_t n, const float* in4, const mi355rt_material* mat, const mi355rt_texture* tex, const float* sky,
+                        const uint32_t* dev, uint32_t* ora, int threads, double* res) {
+    if (!args || !res) return MI355RT_ERR_INVALID;
+    const StageArgs a = *static_cast<const StageArgs*>(args);
+    for (int j = 0; j < 64; ++j) res[j] = 0.0;
+    if (a.stage == STAGE_ATAN2_EXACT || a.stage > STAGE_FMOD_EXACT) return MI355RT_ERR_INVALID;   // ATAN2_EXACT: checked on the device alone
+    if ((a.stage == STAGE_HALF && !mat) || (a.stage == STAGE_TEX && !tex) || (a.stage == STAGE_SKY && (!sky || !a.img_w || !a.img_h)))
+        return MI355RT_ERR_INVALID;
+    if (threads <= 0) threads = (int)std::thread::hardware_concurrency();
+    if (threads <= 0) threads = 1;
+    const uint32_t W = stage_words(a.stage);
+    uint32_t final_mask, trans_mask;
+    stage_masks(a.stage, final_mask, trans_mask);
+    std::vector<StageTally> tally((size_t)threads);
+    std::vector<double> fmod_bad((size_t)threads, 0.0), fmod_which((size_t)threads, -1.0);
+    auto worker = [&](int t) {
+        const uint64_t lo = n * (uint64_t)t / (uint64_t)threads, hi = n * (uint64_t)(t + 1) / (uint64_t)threads;
+        StageTally& T = tally[(size_t)t];
+        for (uint64_t i = lo; i < hi; ++i) {
+            if (a.stage == STAGE_FMOD_EXACT) {
+                const uint64_t k = a.first + i * a.stride;
+                const float x = f_bits((uint32_t)k) + a.h_offset;
+                if (bits_f(std::fmod(x, 1.0f)) != bits_f(x - std::floor(x))) { fmod_bad[(size_t)t] += 1; fmod_which[(size_t)t] = (double)k; }
+                continue;
+            }
+            const StageInput s = stage_input(a, i, in4);
+            uint32_t o[8];
+            stage_oracle(a, s, mat, tex, sky, o);
+            if (ora) for (uint32_t w = 0; w < W; ++w) ora[i * W + w] = o[w];
+            const uint32_t* d = dev ? dev + i * W : nullptr;
+            uint32_t differ = 0u;
+            for (uint32_t w = 0; w < W; ++w) {
+                double ref;
+                const bool has_ref = stage_ref(a, s, o, (int)w, ref);
+                if (has_ref) T.ulp_ora[w] = std::max(T.ulp_ora[w], ulps(o[w], ref));
+                if (!d) continue;
+                const bool hash_word = a.stage == STAGE_HALF && w == 7u;
+                const bool same = d[w] == o[w] || (!hash_word && is_nan_bits(d[w]) && is_nan_bits(o[w]));
+                if (!same) { differ |= 1u << w; T.diffs[w] += 1; if (T.first_diff[w] < 0) T.first_diff[w] = (double)i; }
+                if (has_ref) {
+                    uint32_t dw[8];
+                    for (uint32_t j = 0; j < W; ++j) dw[j] = d[j];
+                    double dref;
+                    stage_ref(a, s, dw, (int)w, dref);
+                    T.ulp_dev[w] = std::max(T.ulp_dev[w], ulps(d[w], dref));
+                }
+            }
+            if (differ & final_mask) {
+                T.final_differs += 1;
+                if (!(differ & trans_mask)) { T.unattributed += 1; if (T.first_unattributed < 0) T.first_unattributed = (double)i; }
+            }
+        }
+    };
+    std::vector<std::thread> pool;
+    for (int t = 1; t < threads; ++t) pool.emplace_back(worker, t);
+    worker(0);
+    for (auto& th : pool) th.join();
+    if (a.stage == STAGE_FMOD_EXACT) {
+        res[1] = -1;
+        for (int t = 0; t < threads; ++t) { res[0] += fmod_bad[(size_t)t]; if (fmod_which[(size_t)t] >= 0) res[1] = fmod_which[(size_t)t]; }
+        return MI355RT_OK;
+    }
+    for (uint32_t w = 0; w < 8; ++w) res[4 * w + 3] = -1;
+    res[33] = -1;
+    for (const StageTally& T : tally) {                                      // threads hold ascending element ranges: the first -1-free value wins
+        for (uint32_t w = 0; w < 8; ++w) {
+            res[4 * w] += T.diffs[w];
+            res[4 * w + 1] = std::max(res[4 * w + 1], T.ulp_dev[w]);
+            res[4 * w + 2] = std::max(res[4 * w + 2], T.ulp_ora[w]);
+            if (res[4 * w + 3] < 0) res[4 * w + 3] = T.first_diff[w];
+        }
+        res[32] += T.unattributed;
+        if (res[33] < 0) res[33] = T.first_unattributed;
+        res[34] += T.final_differs;
+    }
+    res[35] = (double)n;
     return MI355RT_OK;
 }
 

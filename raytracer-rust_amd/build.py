@@ -35,6 +35,9 @@ CXX_FLAGS = ["-O2", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-fPIC"
 DEVICE_SRCS = [os.path.join(CSRC, "device", "rt_kernels.hip"), os.path.join(CSRC, "device", "rt_api.cpp"), os.path.join(CSRC, "device", "rt_multi.cpp")]
 DEVICE_HEADERS = sorted(os.path.join(CSRC, "device", f) for f in os.listdir(os.path.join(CSRC, "device")) if f.endswith(".h"))
 DEVICE_DEPS = DEVICE_SRCS + DEVICE_HEADERS + [os.path.join(ROOT, "include", "mi355rt.h")]
+# Compiled into the tests' reference build (-DMI355RT_REFS) only, so neither the product library nor kernel_hash() contains it:
+# mi355rt_debug_stages, the transcendental stages over enumerated inputs (tests/test_gpu_transcendental_stages.py).
+REFS_SRCS = [os.path.join(CSRC, "refs", "rt_stages.hip")]
 
 
 def _host_srcs():
@@ -109,8 +112,9 @@ def build_device_variant(name, defines=(), force=False, verbose=False, flags=())
     """Diagnostic / A-B builds (e.g. cycle stamps) into their own library; never loaded by the product path."""
     os.makedirs(OUT, exist_ok=True)
     so = os.path.join(OUT, f"libmi355rt_{name}.so")
-    if force or _stale(so, DEVICE_DEPS):
-        cmd = [hipcc_path(), *HIPCC_FLAGS, *flags, *[f"-D{d}" for d in defines], "-o", so, *DEVICE_SRCS]
+    srcs = DEVICE_SRCS + (REFS_SRCS if "MI355RT_REFS" in defines else [])
+    if force or _stale(so, DEVICE_DEPS + srcs):
+        cmd = [hipcc_path(), *HIPCC_FLAGS, *flags, *[f"-D{d}" for d in defines], "-o", so, *srcs]
         if verbose:
             print(" ".join(cmd))
         subprocess.check_call(cmd)

@@ -30,8 +30,46 @@ def load(so):
 
 
 def refs():
-    """The tests' reference build: the product sources plus the retired mesh kernel (the state machine), -DMI355RT_REFS."""
-    return load(build.build_device_variant("refs", ["MI355RT_REFS"]))
+    """The tests' reference build: the product sources plus the retired mesh kernel (the state machine) and mi355rt_debug_stages, -DMI355RT_REFS."""
+    L = load(build.build_device_variant("refs", ["MI355RT_REFS"]))
+    L.mi355rt_debug_stages.restype = C.c_int
+    L.mi355rt_debug_stages.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+    return L
+
+
+# mi355rt_debug_stages (csrc/refs/rt_stages.hip; the oracle's twin is oracle_debug_stages): stage numbers and the argument record
+STAGES = {"lattice": 0, "half": 1, "acos": 2, "atan2": 3, "tex": 4, "sky": 5, "atan2_exact": 6, "fmod_exact": 7}
+
+
+class StageArgs(C.Structure):
+    _fields_ = [("stage", C.c_uint32), ("form", C.c_uint32), ("first", C.c_uint64), ("stride", C.c_uint64),
+                ("ggx", C.c_uint32), ("axis", C.c_uint32), ("set", C.c_uint32), ("img_w", C.c_uint32), ("img_h", C.c_uint32), ("pad0", C.c_uint32),
+                ("rough", C.c_float), ("fixed_u", C.c_float), ("h_offset", C.c_float), ("pad1", C.c_float),
+                ("n", C.c_float * 4), ("rd", C.c_float * 4)]
+
+
+def stage_words(stage):
+    """Words per element of a stage's output (0: the exact stages, which return 3 words per call)."""
+    return 1 if stage in (2, 3) else (0 if stage >= 6 else 8)
+
+
+def _ptr(a):
+    return None if a is None else a.ctypes.data
+
+
+def debug_stages(args, n, in4=None, mat=None, tex_rgba=None, sky=None, hip_device=0):
+    """Diagnostic (reference build): stage `args.stage` on n elements on the device.  in4: float32 [n, 4] explicit inputs or None; mat: an
+    abi.Material (HALF); tex_rgba: uint32 [img_h, img_w] texels (TEX); sky: float32 [img_h, img_w, 3] (SKY).  Returns uint32 [n, words], or
+    uint32 [3] for the exact stages (mismatches, the smallest mismatching index, results one f32 step off on atan2's diagonal)."""
+    L = refs()
+    W = stage_words(args.stage)
+    out = np.zeros(n * W if W else 3, np.uint32)
+    in4 = None if in4 is None else np.ascontiguousarray(in4, np.float32)
+    tex_rgba = None if tex_rgba is None else np.ascontiguousarray(tex_rgba, np.uint32)
+    sky = None if sky is None else np.ascontiguousarray(sky, np.float32)
+    _check(L.mi355rt_debug_stages(C.addressof(args), n, _ptr(in4), C.addressof(mat) if mat is not None else None, _ptr(tex_rgba), _ptr(sky),
+                                  out.ctypes.data, hip_device), "mi355rt_debug_stages", L)
+    return out.reshape(n, W) if W else out
 
 
 def lib():
