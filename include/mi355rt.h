@@ -159,6 +159,11 @@ typedef struct mi355rt_scene {
     const mi355rt_triangle*  triangles;   uint32_t n_triangles;
     const mi355rt_bvh_node*  nodes;       uint32_t n_nodes;
     const uint32_t*          tri_indices; uint32_t n_tri_indices;
+    /* Colours -- miss_color, sky texels, albedos, emitted colours -- are not validated: non-finite and out-of-range values are accepted
+     * and propagate as in the reference's f32 arithmetic (inf * 0 = NaN: a path that runs out of depth with an infinite throughput is NaN,
+     * not black; sums overflow to +-inf; negative and denormal values stay what they are) through the path ends, the sample-order sum,
+     * the progressive sums and the multi-device gathers into the linear output.  The packed pixel is sqrt, clamp(0, 1) where NaN stays,
+     * * 255, saturating conversion: NaN and negative channels pack as 0, +inf as 255. */
     float        miss_color[3];           /* Color::GRAY at HEAD, src/renderer.rs:61             */
     uint32_t     sky_width, sky_height;   /* equirect HDR skybox, src/renderer.rs:40-54; 0 = none */
     const float* sky_rgb;                 /* sky_width*sky_height*3 f32, row 0 = top; NULL = constant miss_color */

@@ -30,11 +30,48 @@ def load(so):
 
 
 def refs():
-    """The tests' reference build: the product sources plus the retired mesh kernel (the state machine) and mi355rt_debug_stages, -DMI355RT_REFS."""
+    """The tests' reference build: the product sources plus the retired mesh kernel (the state machine), mi355rt_debug_stages and the
+    resolve / gather probe (mi355rt_debug_resolve, mi355rt_debug_gather), -DMI355RT_REFS."""
     L = load(build.build_device_variant("refs", ["MI355RT_REFS"]))
     L.mi355rt_debug_stages.restype = C.c_int
     L.mi355rt_debug_stages.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+    L.mi355rt_debug_resolve.restype = C.c_int
+    L.mi355rt_debug_resolve.argtypes = [C.c_void_p]
+    L.mi355rt_debug_gather.restype = C.c_int
+    L.mi355rt_debug_gather.argtypes = [C.c_void_p]
     return L
+
+
+# mi355rt_debug_resolve / mi355rt_debug_gather (csrc/refs/rt_resolve_probe.hip): the shipped launch_resolve, launch_gather_strips and
+# launch_gather_accum on the caller's device buffers.  Every pointer is a device address of the current device (torch: tensor.data_ptr()),
+# 0 = null; the caller sizes the buffers.
+class ResolveProbeArgs(C.Structure):
+    _fields_ = [("radiance", C.c_uint64), ("out_packed", C.c_uint64), ("out_linear", C.c_uint64), ("accum", C.c_uint64), ("out_row", C.c_uint64),
+                ("accum_load", C.c_uint32), ("band_pixel0", C.c_uint32), ("band_pixels", C.c_uint32), ("spp", C.c_uint32),
+                ("inv_spp", C.c_float), ("width", C.c_uint32)]
+
+
+class GatherProbeArgs(C.Structure):
+    _fields_ = [("src_row", C.c_uint64), ("src_packed", C.c_uint64), ("dst_packed", C.c_uint64), ("src_linear", C.c_uint64), ("dst_linear", C.c_uint64),
+                ("accum_src", C.c_uint64), ("accum_dst", C.c_uint64), ("n_rows", C.c_uint32), ("width", C.c_uint32)]
+
+
+def debug_resolve(radiance, out_packed, spp, inv_spp, band_pixels, band_pixel0=0, out_linear=0, accum=0, accum_load=False, out_row=0, width=0):
+    """Diagnostic (reference build): one k_resolve launch through launch_resolve, waited for.  radiance: 3 * spp * band_pixels floats, the
+    band's samples; the outputs are indexed by band_pixel0 + p, or through out_row (processing row -> output row of an image `width` wide)."""
+    a = ResolveProbeArgs(int(radiance), int(out_packed), int(out_linear), int(accum), int(out_row), 1 if accum_load else 0,
+                         int(band_pixel0), int(band_pixels), int(spp), float(inv_spp), int(width))
+    L = refs()
+    _check(L.mi355rt_debug_resolve(C.addressof(a)), "mi355rt_debug_resolve", L)
+
+
+def debug_gather(src_row, n_rows, width, src_packed=0, dst_packed=0, src_linear=0, dst_linear=0, accum_src=0, accum_dst=0):
+    """Diagnostic (reference build): k_gather_strips (src_packed given) and / or k_gather_accum (accum_src given) through their launchers,
+    waited for.  Output row r is staging row src_row[r]."""
+    a = GatherProbeArgs(int(src_row), int(src_packed), int(dst_packed), int(src_linear), int(dst_linear), int(accum_src), int(accum_dst),
+                        int(n_rows), int(width))
+    L = refs()
+    _check(L.mi355rt_debug_gather(C.addressof(a)), "mi355rt_debug_gather", L)
 
 
 # mi355rt_debug_stages (csrc/refs/rt_stages.hip; the oracle's twin is oracle_debug_stages): stage numbers and the argument record

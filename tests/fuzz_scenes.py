@@ -6,7 +6,7 @@ import numpy as np
 
 
 def random_scene(abi, host, seed, exact_only, n_prims=14, mesh_tris=60, only_kinds=None, lambert_only=False, identity_meshes=False, no_metal=False,
-                 no_specular=False, textures=False, sky=False, coincident=False, big_mesh_tris=0, every_material=False):
+                 no_specular=False, textures=False, sky=False, coincident=False, big_mesh_tris=0, every_material=False, poison=None):
     """The options after no_metal are off by default, and then the scene of a seed is the one earlier versions made:
       no_specular    no metal and no dielectric (what the no-specular lockstep / mesh-free wavefront kernels accept);
       textures       two small RGBA8 textures whose neighbouring texels differ, and texture materials (h_offset != 0) over them;
@@ -15,7 +15,9 @@ def random_scene(abi, host, seed, exact_only, n_prims=14, mesh_tris=60, only_kin
                      the end of the list
                      (equal t: the list order decides); meshes also repeat some of their triangles with the opposite winding;
       big_mesh_tris  > 0: one more mesh of that many small triangles (its tree passes LDS_NODE_CAP and WF_SHALLOW_NODES);
-      every_material the first primitives take the material kinds in turn, so that every material of the list is hit-able.
+      every_material the first primitives take the material kinds in turn, so that every material of the list is hit-able;
+      poison         a name of POISONS: non-finite or out-of-range values written into COLOURS of the finished scene (emitters, the miss
+                     colour, sky texels, albedos) -- never into geometry, roughness, IOR or the camera, and no draw is made for it.
     They draw from a generator of their own, so the draws of the options before them stay what they were."""
     from oracle import scene_loader as L
     rng = np.random.default_rng(seed)
@@ -129,6 +131,50 @@ def random_scene(abi, host, seed, exact_only, n_prims=14, mesh_tris=60, only_kin
         sc._tex_arrays = tex_arrays
         sc._textures = (abi.Texture * len(tex_arrays))(*[abi.Texture(a.ctypes.data_as(C.POINTER(C.c_uint8)), a.shape[1], a.shape[0]) for a in tex_arrays])
         sc.c.textures, sc.c.n_textures = sc._textures, len(tex_arrays)
+    if poison is not None:
+        apply_poison(abi, sc, poison)
     sc._keep = host.attach_bvh(sc)
     sc.camera = L.camera_new((0.0, 1.0, 9.0), (0.0, 0.0, 0.0), (0.0, 1.0, 0.0), F(50.0), F(4.0 / 3.0))
     return sc
+
+
+_INF, _NAN = float("inf"), float("nan")
+_FOUR = {"inf": (_INF, _INF, _INF), "mixed": (_INF, -_INF, _NAN), "overflow": (3e38, 3e38, 1e-42), "signed": (-1.0, -0.0, 1e-40)}
+# name -> (what is poisoned, the colour).  "lambert": the albedo of EVERY solid Lambert material (0 * inf at lights, inf * 0 where a path runs
+# out of depth); "sky": texels of the HDR map (the scene must be made with sky=True).
+POISONS = {**{f"emissive_{k}": ("emissive", v) for k, v in _FOUR.items()}, **{f"miss_{k}": ("miss", v) for k, v in _FOUR.items()},
+           "sky": ("sky", None),
+           "lambert_zero": ("lambert", (0.0, 0.0, 0.0)), "lambert_gt1": ("lambert", (1.5, 4.0, 1.0000001)), "lambert_inf": ("lambert", (_INF, _INF, _INF)),
+           "lambert_negative": ("lambert", (-0.5, -2.0, -0.0)),
+           "metal_inf": ("metal", (_INF, _INF, _INF)), "checker_nan": ("checker", (_NAN, _NAN, _NAN)), "rough_inf": ("rough", (_INF, _INF, _INF))}
+
+
+def apply_poison(abi, sc, name):
+    """Writes the poison `name` into the colours of the finalized scene `sc` (its ctypes arrays).  Raises if the scene holds nothing to poison."""
+    what, colour = POISONS[name]
+    F = np.float32
+    if what == "miss":
+        sc.c.miss_color[:] = [float(F(v)) for v in colour]
+        return
+    if what == "sky":
+        sky = sc._sky_np                                               # [H, W, 3]: a pattern over the texels, every fourth stays as drawn
+        h, w, _ = sky.shape
+        k = (np.arange(h)[:, None] * 5 + np.arange(w)[None, :]) % 8
+        sky[k == 1] = F(np.inf)
+        sky[k == 3] = F(np.nan)
+        sky[k == 5] = F(1e-41)                                         # denormal
+        sky[k == 7] = (F(np.inf), F(1e-45), F(0.5))
+        return
+    kinds = {"emissive": (abi.MAT_EMISSIVE,), "lambert": (abi.MAT_LAMBERT_SOLID,), "metal": (abi.MAT_METAL,), "checker": (abi.MAT_LAMBERT_CHECKER,),
+             "rough": (abi.MAT_ROUGH_GGX, abi.MAT_ROUGH_BECKMANN)}[what]
+    hit = 0
+    for i in range(sc.c.n_materials):
+        m = sc.c.materials[i]
+        if m.kind in kinds:
+            if what == "checker":
+                m.aux[:] = [float(F(v)) for v in colour]                 # the checker's second colour
+            else:
+                m.albedo[:] = [float(F(v)) for v in colour]
+            hit += 1
+    if not hit:
+        raise ValueError(f"poison {name}: the scene holds no such material")

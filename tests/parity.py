@@ -82,3 +82,28 @@ def assert_parity(gpu_packed, gpu_linear, ora_packed, ora_linear, *, exact, rows
     assert abs(gm - om) <= MEAN_REL * max(om, 1e-6), f"image means differ: gpu {gm} oracle {om}; {msg}"
     if have_rays:
         assert abs(int(gpu_rays) - int(oracle_rays)) <= ray_rel * int(oracle_rays), f"ray counts differ by more than {ray_rel:g}: {rays}"
+
+
+NAN_WORD = np.uint32(0x7FC00000)
+
+
+def nan_folded_bits(a):
+    """The f32 words of `a` with every NaN as one word: x86 and gfx950 give a default NaN different signs, and which payload an operation
+    on two NaNs keeps is not part of the contract.  Everything else -- the sign of a zero or an infinity, a denormal -- stays what it is."""
+    a = np.ascontiguousarray(a, np.float32)
+    return np.where(np.isnan(a), NAN_WORD, a.view(np.uint32))
+
+
+def assert_same_bits_nan_folded(got, want, what=""):
+    """got == want word for word, every NaN being one value: a NaN is equal to a NaN only, so a NaN paired with a number (an infinity
+    included) fails like any other difference.  Names the first differing elements."""
+    got, want = np.asarray(got, np.float32), np.asarray(want, np.float32)
+    assert got.shape == want.shape, f"{what}: shapes {got.shape} vs {want.shape}"
+    g, w = nan_folded_bits(got), nan_folded_bits(want)
+    bad = g != w
+    if bad.any():
+        idx = np.argwhere(bad)
+        first = "; ".join(f"{tuple(int(v) for v in i)}: got {got[tuple(i)]!r} ({int(g[tuple(i)]):#010x}) want {want[tuple(i)]!r} ({int(w[tuple(i)]):#010x})"
+                          for i in idx[:6])
+        nan_vs_number = int((bad & (np.isnan(got) != np.isnan(want))).sum())
+        raise AssertionError(f"{what}: {len(idx)} of {g.size} words differ ({nan_vs_number} pair a NaN with a number); first: {first}")

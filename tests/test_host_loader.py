@@ -122,6 +122,7 @@ def test_pfm_writer_roundtrip(native, tmp_path):
     rng = np.random.default_rng(2)
     img = rng.standard_normal((5, 9, 3)).astype(np.float32)
     img[0, 0] = [np.inf, -0.0, np.float32(1e-42)]                  # special values and a denormal survive untouched
+    img[0, 1] = [np.nan, -np.inf, np.array([0xFFC12345], np.uint32).view(np.float32)[0]]   # NaNs (one with a sign and a payload) and -inf too
     path = str(tmp_path / "x.pfm")
     host.write_pfm(path, img, 9, 5)
     raw = open(path, "rb").read()
@@ -170,6 +171,7 @@ def test_exr_writer_roundtrip(native, tmp_path):
     rng = np.random.default_rng(5)
     img = rng.standard_normal((7, 13, 3)).astype(np.float32)
     img[0, 0] = [np.inf, -0.0, np.float32(1e-42)]
+    img[0, 1] = [np.nan, -np.inf, np.array([0xFFC12345], np.uint32).view(np.float32)[0]]   # NaNs (one with a sign and a payload) and -inf
     path = str(tmp_path / "x.exr")
     host.write_exr(path, img, 13, 7)
     got = _read_exr(open(path, "rb").read())

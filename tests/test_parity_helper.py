@@ -137,3 +137,26 @@ def test_oracle_threads(monkeypatch):
     assert oracle_threads() == min(3, n)
     monkeypatch.setenv("OMP_NUM_THREADS", "64")
     assert oracle_threads() == n
+
+
+def test_nan_folded_comparison_takes_any_nan_for_a_nan_and_nothing_else():
+    """assert_same_bits_nan_folded: NaNs of any sign and payload are one value; a NaN paired with a number, a zero of the other sign, an
+    infinity of the other sign and a denormal paired with zero are differences."""
+    from parity import assert_same_bits_nan_folded, nan_folded_bits
+    words = np.array([0x7FC00000, 0xFFC00000, 0x7F800001, 0xFFFFFFFF, 0x7F800000, 0xFF800000, 0x00000000, 0x80000000, 0x00000001, 0x3F800000], np.uint32)
+    a = words.view(np.float32)
+    b = a.copy().view(np.uint32)
+    b[:4] = [0xFFC00000, 0x7FC12345, 0x7FC00000, 0x7FA00000]              # other NaNs in the NaN places
+    assert_same_bits_nan_folded(a, b.view(np.float32), "NaNs of any payload")
+    assert (nan_folded_bits(a)[:4] == 0x7FC00000).all() and (nan_folded_bits(a)[4:] == words[4:]).all()
+    for i, other in ((0, 1.0), (0, np.inf), (0, 0.0), (9, np.nan), (4, np.nan), (5, np.nan), (6, np.nan),      # a NaN paired with a number, both ways
+                     (4, -np.inf), (6, -0.0), (7, 0.0), (8, 0.0), (9, np.float32(1.0000001))):
+        c = a.copy()
+        c[i] = other
+        with pytest.raises(AssertionError, match="1 of 10 words differ"):
+            assert_same_bits_nan_folded(c, a, "one word")
+    with pytest.raises(AssertionError, match=r"1 pair a NaN with a number"):
+        c = a.copy(); c[0] = 2.0
+        assert_same_bits_nan_folded(c, a, "NaN against 2")
+    with pytest.raises(AssertionError, match="shapes"):
+        assert_same_bits_nan_folded(a[:3], a[:4], "shapes")
