@@ -37,6 +37,7 @@ struct DevPrim {                 // 60 words = 240 B
                                                      // the hit record and the head of its material arrive with ONE memory round trip (finish_hit)
 };
 static_assert(sizeof(DevPrim) == 240, "DevPrim must stay 16-byte granular");
+static_assert(offsetof(DevPrim, d) % 16 == 0, "DevPrim::d is read sixteen words at a time as a 16-byte aligned vector (rt_intersect.h load_rec16)");
 
 struct DevMat {                  // 64 B, same field order as mi355rt_material
     uint32_t kind; float albedo[3];

@@ -44,7 +44,11 @@ DI void set_face(Hit& h, f3 rd, f3 outward, uint32_t material) {                
 // place that changes the loop-carried candidate is cand_take()'s selects.  (A test that assigned the candidate inside its own
 // branches made the compiler carry two copies of it through the structurised switch: ~10 v_mov per quad, ~25 per cube.)
 struct Probe { float t, aux; f3 po; };
-typedef float rec16_t __attribute__((ext_vector_type(16)));
+// Sixteen words of a primitive record in one load.  A vector of 16 floats would be 64-byte aligned by default; DevPrim::d is 16-byte aligned (rt_device.h),
+// and the type says so.  load_rec16() is the one place that casts: through the constant address space (cprim_t), so a wave-uniform `pr` gives ONE s_load_dwordx16.
+typedef float rec16_t __attribute__((ext_vector_type(16), aligned(16)));
+static_assert(alignof(rec16_t) == 16, "rec16_t claims the alignment of DevPrim::d, not a vector's natural 64 bytes");
+DI rec16_t load_rec16(cprim_t pr) { return *reinterpret_cast<const __attribute__((address_space(4))) rec16_t*>(pr->d); }
 DI bool cand_take(Cand& c, bool acc, uint32_t i, float t) { c.t = acc ? t : c.t; c.idx = acc ? i : c.idx; return acc; }
 DI bool cand_take(Cand& c, bool acc, uint32_t i, const Probe& o) { c.aux = acc ? o.aux : c.aux; return cand_take(c, acc, i, o.t); }
 DI bool cand_take(CandP& c, bool acc, uint32_t i, const Probe& o) {
@@ -86,7 +90,7 @@ DI bool hit_plane(cprim_t pr, uint32_t i, f3 ro, f3 rd, float t_min, Cand& c) {
 // compiler's division (ballot); infinities and NaN come out of v_div_fixup_f32 as they do there.
 template <bool FASTD = false>
 DI bool hit_quad(cprim_t pr, uint32_t i, f3 ro, f3 rd, float t_min, Cand& c) {
-    const rec16_t q = *reinterpret_cast<const __attribute__((address_space(4))) rec16_t*>(pr->d);     // the whole record: ONE scalar load
+    const rec16_t q = load_rec16(pr);                                                               // the whole record: ONE scalar load
     f3 n = mk(q[0], q[1], q[2]);
     float denom = dot(n, rd);
     const float num = q[3] - dot(n, ro);
@@ -157,7 +161,7 @@ DI uint32_t cube_axis(f3 po) {                                                  
 }
 template <bool FASTR = false, class C>
 DI bool hit_cube(cprim_t pr, uint32_t i, f3 ro_w, f3 rd_w, float t_min, C& c) {
-    const rec16_t m = *reinterpret_cast<const __attribute__((address_space(4))) rec16_t*>(pr->d);     // w2o (3 x 4) and zd: ONE scalar load
+    const rec16_t m = load_rec16(pr);                                                               // w2o (3 x 4) and zd: ONE scalar load
     f3 ro = mk(((m[0] * ro_w.x + m[3] * ro_w.y) + m[6] * ro_w.z) + m[9], ((m[1] * ro_w.x + m[4] * ro_w.y) + m[7] * ro_w.z) + m[10],
                ((m[2] * ro_w.x + m[5] * ro_w.y) + m[8] * ro_w.z) + m[11]);                             // xform_w2o_point
     f3 rd = mk(((m[0] * rd_w.x + m[3] * rd_w.y) + m[6] * rd_w.z) + m[12], ((m[1] * rd_w.x + m[4] * rd_w.y) + m[7] * rd_w.z) + m[13],
@@ -246,6 +250,7 @@ DI void mesh_setup(PrimPtr pr, f3 ro_w, f3 rd_w, float t_max, MeshTrav& m, bool 
 // USE_LDS: nodes below `lds_count` are read from the workgroup's LDS copy (ds_read_b128), the rest from global memory.
 typedef float lds_v4f __attribute__((ext_vector_type(4)));
 typedef const __attribute__((address_space(3))) lds_v4f* lds_nodes_t;
+static_assert(alignof(lds_v4f) == 16 && alignof(float4) == 16 && sizeof(DevNode) == 2 * sizeof(lds_v4f), "lds_v4f is read at node << 5 from a float4 array: 16-byte aligned as its type says");
 // USE_LDS (the reference build's state machine only; the product kernels read nodes from L1 / L2): 0 = global memory; 1 = the LDS copy when EVERY lane
 //          of the wave is below `lds_count` (a wave-uniform choice; a per-lane choice was measured too: the LDS readers then wait for the slowest global load).
 // SPEC (wavefront kernel's WALK stage): the walk does not stop at a hit leaf.  The leaf is left pending (leaf_a / leaf_b, and

@@ -53,6 +53,22 @@ DI uint32_t wave_sum(uint32_t v) {
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
     return v;
 }
+// The hand-off of WAVE-PRIVATE LDS between the lanes of one wave (RayStock, HitStock: entries that one lane writes and another reads, or reads and another
+// overwrites).  The hardware needs nothing for it: a wave's DS instructions execute in the order they were issued, for all of its lanes at once.  The
+// compiler has to be told: to it every lane is a thread of its own, and without a fence it may move one thread's LDS accesses past each other wherever it
+// can show that THAT thread's addresses differ.  This orders every LDS access of the wave in front of the call before every LDS access behind it -- a release
+// fence, a wave barrier, an acquire fence, all of wavefront scope and for the local address space only (global loads and stores stay free to move).  It
+// emits no instruction: wavefront-scope fences and the wave barrier are constraints on the compiler's schedule, nothing else.
+// Call it wherever an entry changes hands; memory that each lane writes and reads back itself (HitStock's parking area) needs none.
+// FENCED = false leaves the wave barrier alone.  The compiler moves no memory access across it either (to the optimiser it is a call that may read and write
+// anything, to the scheduler an instruction with side effects), but it is no memory operation to the language.  deal_stocked uses this form: there the
+// fences, on their own or around the barrier, make the compiler lay k_render_ctr_nomesh out differently, 0.8 ... 1.7 % slower (profiles/ab_defined_handoffs.txt).
+template <bool FENCED = true>
+DI void wave_lds_handoff() {
+    if constexpr (FENCED) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
+    __builtin_amdgcn_wave_barrier();
+    if constexpr (FENCED) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local");
+}
 
 // ===================================================================================================
 // Shared pieces of the two counter-mode kernels
@@ -129,11 +145,13 @@ struct WorkCursorT {
                 claim(P, lane);
                 if (next == end) break;                      // no work left anywhere
                 stock_end = next + min(64u, end - next);
+                wave_lds_handoff<false>();                   // the entries that lanes took, in this call or an earlier one, are overwritten by other lanes ...
                 refill(next, stock_end - next);
+                wave_lds_handoff<false>();                   // ... and a lane takes an entry that another lane wrote (the barrier alone: see wave_lds_handoff)
             }
             const uint32_t take = min(n_idle, stock_end - next);
             const uint32_t rank = mbcnt64(idle);
-            if (want && !got && rank < take) { sidx = next + rank; got = true; take_entry(sidx); }   // (read before a refill reuses the entry)
+            if (want && !got && rank < take) { sidx = next + rank; got = true; take_entry(sidx); }
             next += take;
             idle = __ballot(want && !got);
             if (idle == 0ull) break;
@@ -191,7 +209,7 @@ struct PathState {
 // of the sample index.  So the wave prepares the rays of the next (up to) 64 samples of its run AT ONCE, with all lanes, whenever its stock runs out
 // (WorkCursorT::deal_stocked), and keeps them in 2 KB of LDS: per sample the direction before its two normalisations (camera.rs:33-42; the shared
 // tail of the iteration normalises it with the scattered rays, as before) and the generator base.  A lane that is dealt sample i reads entry i mod 64:
-// two ds_read_b128.  Same arithmetic per path, same bits.  LDS operations of one wave execute in order: no barrier between refill and take.
+// two ds_read_b128.  Same arithmetic per path, same bits.  Entries change hands between lanes: wave_lds_handoff() around refill (deal_stocked).
 struct RayStock {
     float4* dir; uint4* key;                                   // [64] each, this wave's
     template <bool FASTN>
@@ -230,9 +248,10 @@ struct RayStock {
 // key, x and s -- the ray word is 0).  The parking area holds ro and rd of the 64 lanes (24 bytes each) during a refill pass.
 struct HitStock {
     float4* e;                                                 // [64][4] this wave's ring of entries
-    float4* park_a; float2* park_b;                            // [64] each: {ro, rd.x}, {rd.y, rd.z}
+    float4* park_a; float2* park_b;                            // [64] each: {ro, rd.x}, {rd.y, rd.z}; lane i writes and reads back element i only: no hand-off
     // Before the walk: the camera ray of sample `sidx` into (ro, rd) -- what RayStock::refill and the loop's shared tail computed -- and its key
-    // into the entry at `slot` (the entry's other words are written after the walk).
+    // into the entry at `slot` (the entry's other words are written after the walk).  The slot is one that another lane was dealt earlier, and append()
+    // reads the key from another lane: the caller puts a wave_lds_handoff() in front of the camera() calls and one behind them.
     DI void camera(const RenderParams& P, uint32_t sidx, uint32_t slot, f3& ro, f3& rd) const {
         RngCtr rng; uint32_t px, py;
         start_path(P, sidx, rng, px, py);
@@ -262,7 +281,8 @@ struct HitStock {
         }
         const uint64_t km = __ballot(keep);
         if (keep) {
-            const float4 key = e[4u * ((tail + lane) & 63u) + 3u];                          // (every lane reads before any lane writes: one wave, in order)
+            const float4 key = e[4u * ((tail + lane) & 63u) + 3u];
+            wave_lds_handoff();                                                             // every lane has read its key before any lane writes an entry
             float4* d = e + 4u * ((tail + mbcnt64(km)) & 63u);
             d[0] = make_float4(h.p.x, h.p.y, h.p.z, __uint_as_float(first + lane));
             d[1] = make_float4(h.n.x, h.n.y, h.n.z, __uint_as_float(h.mat_ff));
@@ -553,6 +573,7 @@ DI void render_ctr_lockstep(const RenderParams& P) {
         if constexpr (PREHIT) {
             n_cam = wc.template refill_size<MI355RT_PREHIT_LOW>(P, lane);
             if (n_cam != 0u) {                             // park the paths' rays; lane i takes the camera ray of sample next + i
+                wave_lds_handoff();                        // (camera() writes into slots whose entries other lanes were dealt)
                 stock.park_a[lane] = make_float4(ps.ro.x, ps.ro.y, ps.ro.z, ps.rd.x); stock.park_b[lane] = make_float2(ps.rd.y, ps.rd.z);
                 if (lane < n_cam) stock.camera(P, wc.next + lane, (wc.ring_head + wc.ring_count + lane) & 63u, ps.ro, ps.rd);
             }
@@ -563,7 +584,9 @@ DI void render_ctr_lockstep(const RenderParams& P) {
             if (n_cam != 0u) {                             // finish or stock the camera paths, take the parked rays back, and walk them next
                 const bool cam = lane < n_cam;
                 if (cam) { ++n_paths; ++n_rays; }
+                wave_lds_handoff();                        // camera() wrote the keys, append() reads them from other lanes ...
                 wc.ring_count += stock.append(P, lane, wc.next, wc.ring_head + wc.ring_count, cam, hit, h, ps.rd);
+                wave_lds_handoff();                        // ... and deal_ring() hands the entries it wrote to whichever lanes are idle
                 wc.next += n_cam;
                 const float4 a = stock.park_a[lane]; const float2 b = stock.park_b[lane];
                 ps.ro = mk(a.x, a.y, a.z); ps.rd = mk(a.w, b.x, b.y);
