@@ -38,7 +38,8 @@ extern "C" {
                                     4: mi355rt_context_set_share exported; MI355RT_RNG_CTR draws from pcg4d (other numbers than versions 1-3, same distribution);
                                     5: mi355rt_multi_context_* exported.  No struct changed in 5: options.abi_version 4 is still accepted.
                                     Added within version 5 (no struct changed, the number stays): mi355rt_multi_context_render_progressive and
-                                    mi355rt_render_progressive_multi -- a caller that needs them probes for the symbols (dlsym), not the number. */
+                                    mi355rt_render_progressive_multi -- a caller that needs them probes for the symbols (dlsym), not the number.
+                                    Likewise the ray queries: mi355rt_context_trace_rays, mi355rt_context_first_hits, mi355rt_trace_rays. */
 
 /* ---- error codes ------------------------------------------------------------------------- */
 #define MI355RT_OK               0
@@ -278,6 +279,54 @@ int  mi355rt_context_render_progressive(mi355rt_context* ctx, const mi355rt_opti
                                         uint32_t sample_begin, uint32_t sample_end, void* d_accum,
                                         void* d_out_packed_rgb, void* d_out_linear_rgb_or_null,
                                         void* hip_stream, mi355rt_stats* stats_or_null);
+
+/* ---- ray queries: what does a ray hit in the resident scene? (added within ABI version 5: probe for the symbols) -------------------
+ * The closest hit of HittableList::hit (src/hittable.rs:45-58) with t_min = EPSILON, t_max = INFINITY -- exactly what trace_ray asks
+ * (src/renderer.rs:24) -- as the geometric HitRecord (hittable.rs:10-27) plus WHICH primitive won and its material INDEX: the caller owns
+ * the material table and gets the hit position, so albedos and checker cells are looked up on its side.  For picking, visibility,
+ * ambient-occlusion and lightmap baking, sensor simulation, and the normal / depth guides of a denoiser.  Bit for bit the reference's
+ * arithmetic: the render kernels' own intersection code.
+ *   - The calls only READ the resident scene: no workspace, no counters.  They may be enqueued on another stream while a render of the same
+ *     context is in flight, do not consult mi355rt_context_set_share, and cannot fail inside a kernel (no bounded waits: the list is walked
+ *     once, the stackless BVH walk follows child and escape links only, whatever the values are -- NaN and infinite rays included).
+ *   - A pending watchdog failure of an EARLIER render on the context is returned the way mi355rt_context_render returns it.
+ *   - Null context, no scene, a null or misaligned pointer (with n_rays > 0), a bad abi_version or row selection: MI355RT_ERR_INVALID, decided
+ *     before any HIP call.  options.flags & MI355RT_FLAG_FIXED_AABB: MI355RT_ERR_UNSUPPORTED (the queries answer as the reference does).
+ *     options.rng_mode, seed and workspace_bytes are ignored.
+ *   - mi355rt_context_set_scene and mi355rt_context_destroy replace and free what a query reads: synchronise the streams that carry
+ *     queries before calling them (a query leaves no event behind that they could wait on).
+ *   - One device only: there is no mi355rt_multi_context_* form of the queries. */
+typedef struct mi355rt_ray {       /* 32 bytes; arrays 16-byte aligned */
+    float origin[3];    float _pad0;
+    float direction[3]; float _pad1;   /* need not be unit: normalised ONCE, as Ray::new does (src/ray.rs:12-17, src/vec3.rs:37-44:
+                                          a length below 1e-4 leaves it as it is).  Pads are ignored. */
+} mi355rt_ray;
+
+#define MI355RT_NO_HIT 0xFFFFFFFFu
+typedef struct mi355rt_hit {       /* 48 bytes; HitRecord, src/hittable.rs:10-27 */
+    float position[3];  float t;             /* t along the normalised direction */
+    float normal[3];    uint32_t front_face; /* normal already flipped against the ray (set_face_normal); 0 / 1 */
+    uint32_t primitive;                      /* index into mi355rt_scene.primitives; MI355RT_NO_HIT = miss */
+    uint32_t material;                       /* that primitive's material index; MI355RT_NO_HIT on a miss */
+    uint32_t _pad[2];                        /* written as 0 */
+} mi355rt_hit;
+/* A miss writes primitive = material = MI355RT_NO_HIT, t = +inf and every other word 0.  EVERY word of every record is written: the caller
+ * never clears the buffer, and two results compare bytewise. */
+
+/* n_rays arbitrary rays.  DEVICE pointers, 16-byte aligned; enqueues on hip_stream (NULL = default stream) and returns.
+ * n_rays == 0 is a no-op that returns MI355RT_OK. */
+int  mi355rt_context_trace_rays(mi355rt_context* ctx, const void* d_rays, uint32_t n_rays, void* d_hits, void* hip_stream);
+/* (mi355rt_context_first_hits, below: the FIRST call with a row selection this context has not seen since set_scene allocates a small device
+ * table for it -- hipMalloc, which may wait for the device -- and uploads it on hip_stream; later calls with that selection only enqueue.  A
+ * context that has seen 16 different selections waits for the device once and starts over.) */
+/* The same record for the ray through the CENTRE of every selected pixel: u = (x + 0.5) / width, v = (y + 0.5) / height, Camera::get_ray
+ * (src/camera.rs:33-42) with the camera and settings of set_scene; rows selected by options exactly as mi355rt_context_render selects them
+ * (mi355rt_rows_selected sizes the buffer); d_hits (DEVICE, 16-byte aligned) holds rows * width records, row-major over the selected rows. */
+int  mi355rt_context_first_hits(mi355rt_context* ctx, const mi355rt_options* options_or_null, void* d_hits, void* hip_stream);
+/* One-shot with HOST buffers (context on device 0, upload, query, copy back, destroy): what a host that owns no device memory calls.
+ * It pays mi355rt_context_set_scene in full on every call -- the scene upload and, for the scenes named there, its probe render -- so a caller
+ * with more than one batch of rays keeps a context and calls mi355rt_context_trace_rays. */
+int  mi355rt_trace_rays(const mi355rt_scene* scene, const mi355rt_ray* rays, uint32_t n_rays, mi355rt_hit* out_hits);
 
 /* mi355rt_render over several GPUs from ONE host process (the reference's host is a single `main`):
  * row strips of options.strip_rows rows (0 -> 4) are dealt round-robin over `hip_devices`, each device

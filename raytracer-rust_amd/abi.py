@@ -5,6 +5,8 @@ the sizes against the values the C compiler reports (`mi355rt_host` exports them
 """
 import ctypes as C
 
+import numpy as np
+
 ABI_VERSION = 5
 
 OK, ERR_INVALID, ERR_NO_DEVICE, ERR_HIP, ERR_OOM, ERR_IO, ERR_UNSUPPORTED = 0, -1, -2, -3, -4, -5, -6
@@ -80,6 +82,24 @@ class Stats(C.Structure):
     _fields_ = [("render_kernel_ms", C.c_double), ("resolve_kernel_ms", C.c_double), ("total_ms", C.c_double),
                 ("samples", u64), ("rays", u64), ("rows_rendered", u32), ("bands", u32),
                 ("grid_blocks", u32), ("block_threads", u32), ("kernel_vgprs", u32), ("kernel_sgprs", u32)]
+
+
+NO_HIT = 0xFFFFFFFF
+
+
+class Ray(C.Structure):                                   # mi355rt_ray, 32 bytes
+    _fields_ = [("origin", f32 * 3), ("_pad0", f32), ("direction", f32 * 3), ("_pad1", f32)]
+
+
+class Hit(C.Structure):                                   # mi355rt_hit, 48 bytes
+    _fields_ = [("position", f32 * 3), ("t", f32), ("normal", f32 * 3), ("front_face", u32),
+                ("primitive", u32), ("material", u32), ("_pad", u32 * 2)]
+
+
+# numpy twins of Ray / Hit: arrays of them are what the query calls read and write
+RAY_DTYPE = np.dtype([("origin", "<f4", 3), ("_pad0", "<f4"), ("direction", "<f4", 3), ("_pad1", "<f4")])
+HIT_DTYPE = np.dtype([("position", "<f4", 3), ("t", "<f4"), ("normal", "<f4", 3), ("front_face", "<u4"),
+                      ("primitive", "<u4"), ("material", "<u4"), ("_pad", "<u4", 2)])
 
 
 # mi355rt_progress_fn: int (*)(void* user, uint32_t samples_done, uint32_t samples_total, const uint32_t* packed_rgb)

@@ -22,6 +22,7 @@
 #include "../../../include/mi355rt.h"
 #include "rt_device.h"
 #include "rt_host.h"
+#include "rt_query.h"
 
 using namespace mi355rt;
 
@@ -153,6 +154,15 @@ struct mi355rt_context {
     bool timing = false;
     std::vector<hipEvent_t> pool; size_t pool_used = 0;
     uint32_t timed_launches = 0;
+    // Row tables of mi355rt_context_first_hits (local output row -> absolute y), one per row selection seen since set_scene.  They are the queries' own:
+    // a query never touches `rows` above, which belongs to the render in flight.  A table is written once (its host copy outlives the upload) and
+    // never changed, so queries on any streams may read it; `ready` orders the upload before a query on another stream.
+    struct QueryRows { std::vector<uint32_t> rows; uint32_t* d = nullptr; hipEvent_t ready = nullptr; hipStream_t stream = nullptr; };
+    std::vector<QueryRows> query_rows;
+    void query_rows_release() {                                      // (hipFree waits for the device: no query still reads a table)
+        for (auto& t : query_rows) { if (t.d) (void)hipFree(t.d); if (t.ready) (void)hipEventDestroy(t.ready); }
+        query_rows.clear();
+    }
     hipEvent_t pool_get() {
         if (pool_used == pool.size()) { hipEvent_t e = nullptr; if (hipEventCreate(&e) != hipSuccess) return nullptr; pool.push_back(e); }
         return pool[pool_used++];
@@ -595,7 +605,7 @@ void mi355rt_context_destroy(mi355rt_context* ctx) {                 // (nothing
     (void)hipSetDevice(ctx->device);
     ctx->prims.release(); ctx->mats.release(); ctx->nodes.release(); ctx->tris.release(); ctx->rows.release();
     ctx->radiance.release(); ctx->counters.release(); ctx->stats.release(); ctx->fold_stack.release(); ctx->wave_times.release(); ctx->sky.release();
-    ctx->textures.release(); ctx->texels.release(); ctx->errword.release();
+    ctx->textures.release(); ctx->texels.release(); ctx->errword.release(); ctx->query_rows_release();
     if (ctx->h_err) (void)hipHostFree(ctx->h_err);
     for (auto& e : ctx->ev) if (e) (void)hipEventDestroy(e);
     if (ctx->done) (void)hipEventDestroy(ctx->done);
@@ -614,6 +624,7 @@ int mi355rt_context_set_scene(mi355rt_context* ctx, const mi355rt_scene* scene, 
     int rc = check_settings(settings); if (rc) return rc;
     HIP_TRY(hipSetDevice(ctx->device));
     ctx->have_scene = false; ctx->rows_valid = false;
+    ctx->query_rows_release();                                       // (the tables belong to the old settings)
     rc = build_device_scene(ctx, scene); if (rc) return rc;
     static_assert(sizeof(DevCamera) == sizeof(mi355rt_camera), "camera layout is shared with the ABI");
     std::memcpy(&ctx->cam, camera, sizeof(DevCamera));
@@ -899,6 +910,101 @@ int mi355rt_context_render_progressive(mi355rt_context* ctx, const mi355rt_optio
     if (!d_accum) return fail(MI355RT_ERR_INVALID, "d_accum is null");
     if (sample_end <= sample_begin) return fail(MI355RT_ERR_INVALID, "sample_end must be greater than sample_begin");
     return render_samples(ctx, opt, sample_begin, sample_end, d_accum, d_out_packed, d_out_linear, hip_stream, stats);
+    });
+}
+
+// ---- ray queries (rt_query.hip): what does a ray hit in the resident scene? ------------------------------------------------------
+// They read the scene arrays only -- no workspace, no counters, no error word of their own -- so they neither wait on `done` nor
+// record it, and may run beside a render of the same context on another stream.  mi355rt_context_set_share is not consulted: the
+// kernels are plain grids that end with their rays.
+static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0u; }
+static void query_scene(const mi355rt_context* ctx, QueryParams& q) {
+    q.prims = ctx->prims.p; q.nodes = ctx->nodes.p; q.tris = ctx->tris.p; q.n_prims = ctx->n_prims;
+}
+
+int mi355rt_context_trace_rays(mi355rt_context* ctx, const void* d_rays, uint32_t n_rays, void* d_hits, void* hip_stream) {
+    return guard([&]() -> int {
+    static_assert(sizeof(mi355rt_ray) == 32 && sizeof(mi355rt_hit) == 48, "the query kernels read a ray as two 16-byte halves and write a record as three 16-byte words");
+    if (!ctx || !ctx->have_scene) return fail(MI355RT_ERR_INVALID, "context has no scene");
+    if (n_rays == 0) return MI355RT_OK;
+    if (!d_rays || !d_hits) return fail(MI355RT_ERR_INVALID, "trace_rays: d_rays / d_hits is null");
+    if (!aligned16(d_rays) || !aligned16(d_hits)) return fail(MI355RT_ERR_INVALID, "trace_rays: d_rays / d_hits must be 16-byte aligned");
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (int erc = report_device_error(ctx)) return erc;              // an earlier asynchronous render on this context failed
+    QueryParams q{};
+    query_scene(ctx, q);
+    q.rays = d_rays; q.hits = d_hits; q.n = n_rays;
+    if (launch_query(q, ctx->has_mesh, hip_stream) != 0) return fail(MI355RT_ERR_HIP, "k_query_rays launch failed");
+    return MI355RT_OK;
+    });
+}
+
+int mi355rt_context_first_hits(mi355rt_context* ctx, const mi355rt_options* opt, void* d_hits, void* hip_stream) {
+    return guard([&]() -> int {
+    if (!ctx || !ctx->have_scene) return fail(MI355RT_ERR_INVALID, "context has no scene");
+    if (!d_hits) return fail(MI355RT_ERR_INVALID, "first_hits: d_hits is null");
+    if (!aligned16(d_hits)) return fail(MI355RT_ERR_INVALID, "first_hits: d_hits must be 16-byte aligned");
+    if (opt && (opt->flags & ~MI355RT_FLAG_FIXED_AABB) != 0u) return fail(MI355RT_ERR_INVALID, "options.flags has unknown bits");
+    const mi355rt_settings& st = ctx->settings;
+    RowSel sel;
+    {   mi355rt_options rows_only{};                                 // rng_mode, seed and workspace_bytes are not this call's business
+        if (opt) { rows_only = *opt; rows_only.rng_mode = MI355RT_RNG_CTR; }
+        const int rc = select_rows(st, opt ? &rows_only : nullptr, sel); if (rc) return rc; }
+    if (opt && (opt->flags & MI355RT_FLAG_FIXED_AABB) != 0u)
+        return fail(MI355RT_ERR_UNSUPPORTED, "first_hits: MI355RT_FLAG_FIXED_AABB is not built for ray queries (they answer as the reference does)");
+    if (sel.rows.empty()) return MI355RT_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (int erc = report_device_error(ctx)) return erc;              // an earlier asynchronous render on this context failed
+    hipStream_t stream = (hipStream_t)hip_stream;
+    mi355rt_context::QueryRows* table = nullptr;
+    for (auto& t : ctx->query_rows) if (t.rows == sel.rows) { table = &t; break; }
+    if (!table) {
+        if (ctx->query_rows.size() >= 16) { HIP_TRY(hipDeviceSynchronize()); ctx->query_rows_release(); }   // a caller that keeps changing its selection: start over
+        mi355rt_context::QueryRows t;
+        t.rows.swap(sel.rows); t.stream = stream;
+        if (hipMalloc((void**)&t.d, t.rows.size() * sizeof(uint32_t)) != hipSuccess) return fail(MI355RT_ERR_OOM, "hipMalloc(first_hits row table)");
+        ctx->query_rows.push_back(std::move(t));                     // (the vector's storage moves with it: the upload's source stays where it is)
+        table = &ctx->query_rows.back();
+        if (hipEventCreateWithFlags(&table->ready, hipEventDisableTiming) != hipSuccess ||
+            hipMemcpyAsync(table->d, table->rows.data(), table->rows.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream) != hipSuccess ||
+            hipEventRecord(table->ready, stream) != hipSuccess) {
+            (void)hipDeviceSynchronize();                            // a table that may not have arrived is not kept
+            (void)hipFree(table->d); if (table->ready) (void)hipEventDestroy(table->ready);
+            ctx->query_rows.pop_back();
+            return fail(MI355RT_ERR_HIP, "first_hits: row table upload failed");
+        }
+    } else if (table->stream != stream) HIP_TRY(hipStreamWaitEvent(stream, table->ready, 0));
+    QueryParams q{};
+    query_scene(ctx, q);
+    q.rays = nullptr; q.hits = d_hits; q.rows = table->d; q.n = (uint32_t)(table->rows.size() * (size_t)st.width);   // (< 2^31: check_settings)
+    q.cam = ctx->cam; q.width = st.width; q.width_f = (float)st.width; q.height_f = (float)st.height;
+    magic_div(st.width, q.width_mul, q.width_shift);
+    if (launch_query(q, ctx->has_mesh, hip_stream) != 0) return fail(MI355RT_ERR_HIP, "k_query_pixels launch failed");
+    return MI355RT_OK;
+    });
+}
+
+// Host buffers in, host buffers out: a context on device 0, the scene uploaded, one query, the records copied back.
+int mi355rt_trace_rays(const mi355rt_scene* scene, const mi355rt_ray* rays, uint32_t n_rays, mi355rt_hit* out_hits) {
+    return guard([&]() -> int {
+    if (!scene) return fail(MI355RT_ERR_INVALID, "scene is null");
+    if (n_rays && (!rays || !out_hits)) return fail(MI355RT_ERR_INVALID, "trace_rays: rays / out_hits is null");
+    if (n_rays == 0) return MI355RT_OK;
+    mi355rt_context* ctx = nullptr;
+    int rc = mi355rt_context_create(0, &ctx); if (rc) return rc;
+    const mi355rt_camera no_camera{}; const mi355rt_settings one_pixel{1, 1, 1, 1};      // set_scene wants a view; the query does not look at it
+    rc = mi355rt_context_set_scene(ctx, scene, &no_camera, &one_pixel);
+    DevBuf<mi355rt_ray> d_rays; DevBuf<mi355rt_hit> d_hits;
+    if (!rc) rc = d_rays.ensure(n_rays);
+    if (!rc) rc = d_hits.ensure(n_rays);
+    if (!rc && hipMemcpy(d_rays.p, rays, (size_t)n_rays * sizeof(mi355rt_ray), hipMemcpyHostToDevice) != hipSuccess) rc = fail(MI355RT_ERR_HIP, "upload rays");
+    if (!rc) rc = mi355rt_context_trace_rays(ctx, d_rays.p, n_rays, d_hits.p, nullptr);
+    if (!rc && hipMemcpy(out_hits, d_hits.p, (size_t)n_rays * sizeof(mi355rt_hit), hipMemcpyDeviceToHost) != hipSuccess) rc = fail(MI355RT_ERR_HIP, "copy back hits");   // (waits for the query)
+    d_rays.release(); d_hits.release();
+    std::string keep; keep.swap(g_err);                               // (destroy may overwrite the message of the failure being reported; swap never throws)
+    mi355rt_context_destroy(ctx);
+    g_err.swap(keep);
+    return rc;
     });
 }
 

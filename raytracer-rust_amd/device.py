@@ -15,7 +15,8 @@ EXPORTS = ["mi355rt_render", "mi355rt_render_multi", "mi355rt_render_progressive
            "mi355rt_rows_selected", "mi355rt_context_render", "mi355rt_context_render_progressive", "mi355rt_context_set_timing", "mi355rt_context_read_timing",
            "mi355rt_context_check", "mi355rt_context_set_share", "mi355rt_last_error", "mi355rt_abi_version",
            "mi355rt_multi_context_create", "mi355rt_multi_context_destroy", "mi355rt_multi_context_set_scene", "mi355rt_multi_context_render",
-           "mi355rt_multi_context_check", "mi355rt_multi_context_render_progressive", "mi355rt_render_progressive_multi"]
+           "mi355rt_multi_context_check", "mi355rt_multi_context_render_progressive", "mi355rt_render_progressive_multi",
+           "mi355rt_context_trace_rays", "mi355rt_context_first_hits", "mi355rt_trace_rays"]
 
 _lib = None
 _extra = {}
@@ -168,6 +169,12 @@ def _bind(so):
         L.mi355rt_render_progressive_multi.argtypes = [C.POINTER(abi.Scene), C.POINTER(abi.Camera), C.POINTER(abi.Settings), C.POINTER(abi.Options),
                                                        C.POINTER(C.c_int), C.c_uint32, C.c_uint32, abi.ProgressFn, C.c_void_p,
                                                        C.c_void_p, C.c_void_p, C.POINTER(abi.Stats)]
+        L.mi355rt_context_trace_rays.restype = C.c_int
+        L.mi355rt_context_trace_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+        L.mi355rt_context_first_hits.restype = C.c_int
+        L.mi355rt_context_first_hits.argtypes = [C.c_void_p, C.POINTER(abi.Options), C.c_void_p, C.c_void_p]
+        L.mi355rt_trace_rays.restype = C.c_int
+        L.mi355rt_trace_rays.argtypes = [C.POINTER(abi.Scene), C.c_void_p, C.c_uint32, C.c_void_p]
         L.mi355rt_debug_multi_part_ms.restype = C.c_int
         L.mi355rt_debug_multi_part_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_uint32, C.POINTER(C.c_uint32)]
         L.mi355rt_debug_set_knob.restype = C.c_int
@@ -265,6 +272,19 @@ def render_progressive_multi(scene, camera, settings, devices, chunk_spp, on_chu
     return packed, linear, stats
 
 
+def trace_rays(scene, rays, library=None):
+    """One-shot mi355rt_trace_rays with host buffers: the closest hit of every ray in `scene`.  rays: a numpy array of abi.RAY_DTYPE (or
+    float32 [n, 8]: origin, pad, direction, pad; the directions need not be unit).  Returns an array of abi.HIT_DTYPE, one record per ray."""
+    L = library or lib()
+    sc = getattr(scene, "c", scene)
+    rays = np.ascontiguousarray(rays)
+    if rays.dtype != abi.RAY_DTYPE:
+        rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 8).view(abi.RAY_DTYPE).reshape(-1)
+    hits = np.zeros(rays.size, abi.HIT_DTYPE)
+    _check(L.mi355rt_trace_rays(C.byref(sc), C.c_void_p(rays.ctypes.data), rays.size, C.c_void_p(hits.ctypes.data)), "mi355rt_trace_rays", L)
+    return hits
+
+
 def debug_scatter(materials, records, hip_device=0, textures=None):
     """Diagnostic: one Material::scatter per record on the device.  materials: ctypes array of abi.Material;
     records: (material index, front_face, rd[3], p[3], n[3], (k0, k1, x, s, ray)).  Returns float32 [n, 10] rows
@@ -359,6 +379,18 @@ class Context:
                                                         C.c_void_p(stream) if stream else None,
                                                         C.byref(stats) if stats is not None else None), "mi355rt_context_render_progressive", self._L)
         return stats
+
+    def trace_rays(self, d_rays, n, d_hits, stream=None):
+        """mi355rt_context_trace_rays: the closest hit of n rays in the resident scene, enqueued on `stream`.  d_rays / d_hits: integer device
+        addresses (16-byte aligned) of n abi.Ray and n abi.Hit records; every word of every record is written."""
+        _check(self._L.mi355rt_context_trace_rays(self._h, C.c_void_p(d_rays) if d_rays else None, int(n), C.c_void_p(d_hits) if d_hits else None,
+                                                  C.c_void_p(stream) if stream else None), "mi355rt_context_trace_rays", self._L)
+
+    def first_hits(self, d_hits, options=None, stream=None):
+        """mi355rt_context_first_hits: the closest hit of the ray through the centre of every selected pixel (rows as render() selects them);
+        d_hits: device address of rows_selected(options) * width abi.Hit records, row-major over the selected rows."""
+        _check(self._L.mi355rt_context_first_hits(self._h, C.byref(options) if options is not None else None, C.c_void_p(d_hits) if d_hits else None,
+                                                  C.c_void_p(stream) if stream else None), "mi355rt_context_first_hits", self._L)
 
     def kernel_variant(self):
         """Diagnostic: the counter-mode kernel chosen for the resident scene (0 lockstep, 1 lockstep+mesh, 2 state machine, 3 lockstep simple)."""

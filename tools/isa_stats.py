@@ -14,54 +14,55 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LLVM = "/opt/rocm/lib/llvm/bin"
 
 
-def code_object(so, workdir):
-    """Extracts the gfx950 code object of `so` into workdir and returns its path."""
+def code_objects(so, workdir):
+    """Extracts the gfx950 code objects of `so` -- one per device translation unit (rt_kernels.hip, rt_query.hip, ...) -- into workdir and
+    returns their paths, in the order of the translation units."""
     base = os.path.join(workdir, os.path.basename(so))
     subprocess.check_call(["cp", so, base])
     subprocess.check_output([os.path.join(LLVM, "llvm-objdump"), "--offloading", base], cwd=workdir, stderr=subprocess.STDOUT)
-    for f in os.listdir(workdir):
-        if f.startswith(os.path.basename(so)) and "amdgcn" in f:
-            return os.path.join(workdir, f)
-    raise RuntimeError("no amdgcn code object in " + so)
+    found = sorted(os.path.join(workdir, f) for f in os.listdir(workdir) if f.startswith(os.path.basename(so)) and "amdgcn" in f)
+    if not found:
+        raise RuntimeError("no amdgcn code object in " + so)
+    return found
 
 
 def kernel_stats(so):
     out = {}
     with tempfile.TemporaryDirectory() as wd:
-        co = code_object(so, wd)
-        syms = subprocess.check_output([os.path.join(LLVM, "llvm-readelf"), "-sW", co], text=True)
-        for line in syms.splitlines():
-            m = re.match(r"\s*\d+:\s+([0-9a-f]+)\s+(\d+)\s+FUNC\s+\S+\s+\S+\s+\S+\s+(\S+)", line)
-            if m and "k_" in m.group(3):
-                out[m.group(3)] = {"code_bytes": int(m.group(2))}
-        notes = subprocess.check_output([os.path.join(LLVM, "llvm-readelf"), "--notes", co], text=True)
-        # amdhsa.kernels: one YAML map per kernel, keys in alphabetical order, each map starts at "- .agpr_count"
-        for entry in re.split(r"\n\s*- \.agpr_count:", notes)[1:]:
-            m = re.search(r"\.symbol:\s+(\S+)\.kd", entry)
-            if not m:
-                continue
-            st = out.setdefault(m.group(1), {})
-            for key in ("vgpr_count", "sgpr_count", "vgpr_spill_count", "sgpr_spill_count", "private_segment_fixed_size", "group_segment_fixed_size"):
-                mm = re.search(r"\n\s*\." + key + r":\s+(\d+)", entry)
-                if mm:
-                    st[key] = int(mm.group(1))
-        dis = subprocess.check_output([os.path.join(LLVM, "llvm-objdump"), "-d", co], text=True)
-        cur = None
-        for line in dis.splitlines():
-            m = re.match(r"[0-9a-f]+ <(\S+)>:", line)
-            if m:
-                cur = m.group(1)
-                continue
-            if cur in out:
-                st = out[cur]
-                t = line.split()
-                if len(t) < 1:
+        for co in code_objects(so, wd):
+            syms = subprocess.check_output([os.path.join(LLVM, "llvm-readelf"), "-sW", co], text=True)
+            for line in syms.splitlines():
+                m = re.match(r"\s*\d+:\s+([0-9a-f]+)\s+(\d+)\s+FUNC\s+\S+\s+\S+\s+\S+\s+(\S+)", line)
+                if m and "k_" in m.group(3):
+                    out[m.group(3)] = {"code_bytes": int(m.group(2))}
+            notes = subprocess.check_output([os.path.join(LLVM, "llvm-readelf"), "--notes", co], text=True)
+            # amdhsa.kernels: one YAML map per kernel, keys in alphabetical order, each map starts at "- .agpr_count"
+            for entry in re.split(r"\n\s*- \.agpr_count:", notes)[1:]:
+                m = re.search(r"\.symbol:\s+(\S+)\.kd", entry)
+                if not m:
                     continue
-                op = t[0]
-                st["insts"] = st.get("insts", 0) + 1
-                if op.startswith("scratch_"):
-                    st["scratch_insts"] = st.get("scratch_insts", 0) + 1
-                    st["scratch_" + ("loads" if "load" in op else "stores")] = st.get("scratch_" + ("loads" if "load" in op else "stores"), 0) + 1
+                st = out.setdefault(m.group(1), {})
+                for key in ("vgpr_count", "sgpr_count", "vgpr_spill_count", "sgpr_spill_count", "private_segment_fixed_size", "group_segment_fixed_size"):
+                    mm = re.search(r"\n\s*\." + key + r":\s+(\d+)", entry)
+                    if mm:
+                        st[key] = int(mm.group(1))
+            dis = subprocess.check_output([os.path.join(LLVM, "llvm-objdump"), "-d", co], text=True)
+            cur = None
+            for line in dis.splitlines():
+                m = re.match(r"[0-9a-f]+ <(\S+)>:", line)
+                if m:
+                    cur = m.group(1)
+                    continue
+                if cur in out:
+                    st = out[cur]
+                    t = line.split()
+                    if len(t) < 1:
+                        continue
+                    op = t[0]
+                    st["insts"] = st.get("insts", 0) + 1
+                    if op.startswith("scratch_"):
+                        st["scratch_insts"] = st.get("scratch_insts", 0) + 1
+                        st["scratch_" + ("loads" if "load" in op else "stores")] = st.get("scratch_" + ("loads" if "load" in op else "stores"), 0) + 1
     return out
 
 
@@ -75,16 +76,16 @@ def kernel_isa(so):
     """{kernel: its instructions as text, one per line, without addresses / encodings} -- for comparing two builds instruction by instruction."""
     out = {}
     with tempfile.TemporaryDirectory() as wd:
-        co = code_object(so, wd)
-        dis = subprocess.check_output([os.path.join(LLVM, "llvm-objdump"), "-d", "--no-show-raw-insn", co], text=True)
-        cur = None
-        for line in dis.splitlines():
-            m = re.match(r"[0-9a-f]+ <(\S+)>:", line)
-            if m:
-                cur = m.group(1); out[cur] = []
-                continue
-            if cur and line.strip():
-                out[cur].append(re.sub(r"\s*//.*$", "", line).strip())
+        for co in code_objects(so, wd):
+            dis = subprocess.check_output([os.path.join(LLVM, "llvm-objdump"), "-d", "--no-show-raw-insn", co], text=True)
+            cur = None
+            for line in dis.splitlines():
+                m = re.match(r"[0-9a-f]+ <(\S+)>:", line)
+                if m:
+                    cur = m.group(1); out[cur] = []
+                    continue
+                if cur and line.strip():
+                    out[cur].append(re.sub(r"\s*//.*$", "", line).strip())
     return out
 
 
