@@ -2,7 +2,8 @@
 //
 // Replaces `render_scene(&scene, &camera, &render_settings) -> Vec<u32>` (src/renderer.rs:67,
 // called from src/main.rs:57).  There is NO CPU fallback in this library: without a HIP device every
-// render entry point returns MI355RT_ERR_NO_DEVICE.
+// render entry point returns MI355RT_ERR_NO_DEVICE.  What happens to a scene before a device is involved -- validation, the BVH re-lay, the
+// primitive records, the choice of the kernel variant -- is rt_prepare.cpp, which has no HIP in it; this file uploads and launches.
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -10,7 +11,6 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <limits>
 #include <map>
 #include <mutex>
 #include <new>
@@ -25,41 +25,6 @@
 #include "rt_query.h"
 
 using namespace mi355rt;
-
-namespace {
-thread_local std::string g_err;
-}  // namespace
-
-namespace mi355rt {
-
-int fail(int code, const std::string& msg) { g_err = msg; return code; }
-int fail_noexcept(int code, const char* msg) noexcept { try { g_err.assign(msg); } catch (...) { g_err.clear(); } return code; }
-
-// Options of ABI version 4 are accepted as well: version 5 added entry points (mi355rt_multi_context_*), no struct changed.
-int select_rows(const mi355rt_settings& st, const mi355rt_options* o, RowSel& sel) {
-    uint32_t rb = 0, re = st.height, strip = 1, parts = 1, part = 0;
-    if (o) {
-        if (o->abi_version != MI355RT_ABI_VERSION && o->abi_version != 4u) return fail(MI355RT_ERR_INVALID, "options.abi_version mismatch");
-        rb = o->row_begin; re = o->row_end ? o->row_end : st.height;
-        strip = o->strip_rows ? o->strip_rows : 1; parts = o->n_parts ? o->n_parts : 1; part = o->part;
-        if (o->rng_mode != MI355RT_RNG_CTR && o->rng_mode != MI355RT_RNG_REF) return fail(MI355RT_ERR_INVALID, "options.rng_mode");
-    }
-    if (re > st.height || rb > re || part >= parts) return fail(MI355RT_ERR_INVALID, "row selection out of range");
-    sel.rows.clear();
-    for (uint32_t y = rb; y < re; ++y) if ((y / strip) % parts == part) sel.rows.push_back(y);
-    return MI355RT_OK;
-}
-
-int check_settings(const mi355rt_settings* st) {
-    if (!st) return fail(MI355RT_ERR_INVALID, "settings is null");
-    if (st->width == 0 || st->height == 0 || st->samples_per_pixel == 0) return fail(MI355RT_ERR_INVALID, "width/height/spp must be > 0");
-    if ((uint64_t)st->width * st->height >= (1ull << 31)) return fail(MI355RT_ERR_INVALID, "image too large");
-    if (st->width >= (1u << 24) || st->height >= (1u << 24)) return fail(MI355RT_ERR_INVALID, "width/height must be < 2^24 (x as f32 is exact, renderer.rs:96)");
-    if (st->samples_per_pixel >= (1u << 30)) return fail(MI355RT_ERR_INVALID, "samples_per_pixel too large");
-    return MI355RT_OK;
-}
-
-}  // namespace mi355rt
 
 namespace {
 
@@ -195,264 +160,28 @@ static int report_device_error(mi355rt_context* ctx, bool this_render) {
 
 namespace {
 
-// Re-lay the meshes' BVHs (any node order, explicit child indices -- the shape of BVHNode, bvh.rs:7-12) into the
-// two-link form the kernels walk (rt_device.h, DevNode): every node carries where the walk goes when its box is hit
-// (inner: the left child, bvh.rs:142) and where it goes otherwise / afterwards (the "escape": the next node of the
-// reference's left-then-right recursion that is not below this one).  The links make the visit order independent of
-// the storage order, so nodes are stored LEVEL BY LEVEL (level 0 of every mesh, then level 1, ...): the levels every
-// ray touches come first and are the part the state-machine kernel keeps in LDS.  Triangles go into leaf-visit order.
-struct MeshFlat {
-    std::vector<uint32_t> order;                 // input node ids in BFS order
-    std::vector<uint32_t> level_begin;           // order[level_begin[L] .. level_begin[L+1]) = level L
-    std::vector<uint32_t> escape;                // per input node: input id of its escape node, NODE_END if none
-    std::vector<uint32_t> first_tri;             // per input leaf: index of its first triangle in out_tris
-    std::vector<uint32_t> global_id;             // per input node: index in the device array
-};
-
-int flatten_mesh(const mi355rt_scene* sc, const mi355rt_mesh& m, MeshFlat& f, std::vector<DevTri>& out_tris) {
-    if ((uint64_t)m.first_triangle + m.triangle_count > sc->n_triangles || m.triangle_count == 0) return fail(MI355RT_ERR_INVALID, "mesh triangle range");
-    if ((uint64_t)m.first_node + m.node_count > sc->n_nodes || m.node_count == 0) return fail(MI355RT_ERR_INVALID, "mesh node range (is the BVH missing? see mi355rt_bvh_build)");
-    if ((uint64_t)m.first_index + m.index_count > sc->n_tri_indices) return fail(MI355RT_ERR_INVALID, "mesh index range");
-    const mi355rt_bvh_node* nodes = sc->nodes + m.first_node;
-    const uint32_t* indices = sc->tri_indices + m.first_index;
-    const mi355rt_triangle* tris = sc->triangles + m.first_triangle;
-    f.escape.assign(m.node_count, NODE_END); f.first_tri.assign(m.node_count, 0u); f.global_id.assign(m.node_count, NODE_END);
-    // pre-order with an explicit stack (input depth is not trusted): escapes, leaf-order triangles, cycle check
-    std::vector<uint8_t> seen(m.node_count, 0);
-    std::vector<std::pair<uint32_t, uint32_t>> stack;   // (node, its escape)
-    stack.emplace_back(0u, NODE_END);
-    uint32_t visited = 0;
-    while (!stack.empty()) {
-        const auto [ni, esc] = stack.back(); stack.pop_back();
-        if (ni >= m.node_count) return fail(MI355RT_ERR_INVALID, "BVH child index out of range");
-        if (seen[ni] || ++visited > m.node_count) return fail(MI355RT_ERR_INVALID, "BVH has a cycle or shared nodes");
-        seen[ni] = 1;
-        f.escape[ni] = esc;
-        const mi355rt_bvh_node& n = nodes[ni];
-        if (n.index_count > 0) {
-            if ((uint64_t)n.first_index + n.index_count > m.index_count) return fail(MI355RT_ERR_INVALID, "BVH leaf index range");
-            f.first_tri[ni] = (uint32_t)out_tris.size();
-            for (uint32_t k = 0; k < n.index_count; ++k) {
-                const uint32_t id = indices[n.first_index + k];
-                if (id >= m.triangle_count) return fail(MI355RT_ERR_INVALID, "BVH leaf triangle id out of range");
-                const mi355rt_triangle& t = tris[id];
-                DevTri dt;
-                for (int c = 0; c < 3; ++c) { dt.v0[c] = t.v0[c]; dt.e1[c] = t.v1[c] - t.v0[c]; dt.e2[c] = t.v2[c] - t.v0[c]; dt.n[c] = t.normal[c]; }
-                out_tris.push_back(dt);
-            }
-        } else {
-            stack.emplace_back(n.right, esc);        // visited after the whole left subtree; it inherits the parent's escape
-            stack.emplace_back(n.left, n.right);     // a left child escapes to its sibling
-        }
-    }
-    // breadth-first order
-    f.order.clear(); f.level_begin.clear();
-    f.order.push_back(0u); f.level_begin.push_back(0u);
-    for (size_t lb = 0; lb < f.order.size();) {
-        const size_t le = f.order.size();
-        for (size_t i = lb; i < le; ++i) {
-            const mi355rt_bvh_node& n = nodes[f.order[i]];
-            if (n.index_count == 0) { f.order.push_back(n.left); f.order.push_back(n.right); }
-        }
-        lb = le;
-        if (f.order.size() > le) f.level_begin.push_back((uint32_t)le);
-    }
-    f.level_begin.push_back((uint32_t)f.order.size());
-    return MI355RT_OK;
+// 1 bit per counter-mode variant this library holds (rt_kernels.hip): what choose_variant (rt_prepare.h) may be made to force.
+uint32_t built_variants() {
+    uint32_t mask = 0u;
+    for (uint32_t v = 0; v < KERNEL_VARIANTS; ++v) if (render_ctr_variant_built(v)) mask |= 1u << v;
+    return mask;
 }
 
-int flatten_meshes(const mi355rt_scene* sc, std::vector<DevNode>& out_nodes, std::vector<DevTri>& out_tris, std::vector<uint32_t>& roots) {
-    std::vector<MeshFlat> flat(sc->n_meshes);
-    size_t max_levels = 0, total = 0;
-    for (uint32_t m = 0; m < sc->n_meshes; ++m) {
-        int rc = flatten_mesh(sc, sc->meshes[m], flat[m], out_tris);
-        if (rc) return rc;
-        max_levels = std::max(max_levels, flat[m].level_begin.size() - 1);
-        total += flat[m].order.size();
-    }
-    // the walk packs node indices into 26 bits (and addresses nodes / triangles with 32-bit byte offsets)
-    if (total >= NODE_END || out_tris.size() > (1u << 26)) return fail(MI355RT_ERR_INVALID, "more than 2^26 BVH nodes or triangles");
-    // Storage order: breadth-first, level by level across all meshes, until the LDS copy is full (LDS_NODE_CAP nodes: the
-    // levels every ray touches); every subtree hanging below that front then follows in depth-first pre-order, so that a
-    // walk through the global-memory part finds a node's left child right behind it (same or next cache line).
-    uint32_t next = 0;
-    for (size_t L = 0; L < max_levels && next < LDS_NODE_CAP; ++L)
-        for (uint32_t m = 0; m < sc->n_meshes && next < LDS_NODE_CAP; ++m) {
-            MeshFlat& f = flat[m];
-            if (L + 1 >= f.level_begin.size()) continue;
-            for (uint32_t i = f.level_begin[L]; i < f.level_begin[L + 1] && next < LDS_NODE_CAP; ++i) f.global_id[f.order[i]] = next++;
-        }
-    for (uint32_t m = 0; m < sc->n_meshes; ++m) {
-        MeshFlat& f = flat[m];
-        const mi355rt_bvh_node* nodes = sc->nodes + sc->meshes[m].first_node;
-        std::vector<uint32_t> stack;
-        for (uint32_t ni : f.order) {                                   // BFS order: parents before children
-            if (f.global_id[ni] != NODE_END) continue;
-            // ni is the root of an unplaced subtree (its parent was placed, or it is a mesh root beyond the cap)
-            stack.assign(1, ni);
-            while (!stack.empty()) {
-                const uint32_t x = stack.back(); stack.pop_back();
-                f.global_id[x] = next++;
-                if (nodes[x].index_count == 0) { stack.push_back(nodes[x].right); stack.push_back(nodes[x].left); }
-            }
-        }
-    }
-    out_nodes.assign(total, DevNode{});
-    roots.assign(sc->n_meshes, 0u);
-    for (uint32_t m = 0; m < sc->n_meshes; ++m) {
-        const MeshFlat& f = flat[m];
-        const mi355rt_bvh_node* nodes = sc->nodes + sc->meshes[m].first_node;
-        roots[m] = f.global_id[0];
-        for (uint32_t ni : f.order) {
-            const mi355rt_bvh_node& n = nodes[ni];
-            DevNode& d = out_nodes[f.global_id[ni]];
-            std::memcpy(d.bmin, n.bmin, 12); std::memcpy(d.bmax, n.bmax, 12);
-            const uint32_t esc = f.escape[ni] == NODE_END ? NODE_END : f.global_id[f.escape[ni]];
-            if (n.index_count == 0) { d.a = f.global_id[n.left]; d.b = esc; }
-            else if (n.index_count <= NODE_MAX_LEAF) { d.a = f.first_tri[ni]; d.b = esc | (n.index_count << NODE_LINK_BITS); }
-            else {
-                // A leaf with more triangles than the count field holds (BVHNode::new makes them only at depth 25, bvh.rs:31;
-                // a caller-built tree may have them anywhere): its box test stays where it is, as an inner node whose "left
-                // child" is a chain of chunk leaves with infinite bounds.  An infinite box is hit by every ray (the slab test
-                // leaves t_min / t_max untouched), so the chain only adds box tests that change nothing; a miss of the real
-                // box skips the whole chain.  The chunks live behind the level-ordered part of the array.
-                d.a = (uint32_t)out_nodes.size(); d.b = esc;
-                const float inf = std::numeric_limits<float>::infinity();
-                for (uint32_t k = 0; k < n.index_count; k += NODE_MAX_LEAF) {
-                    const uint32_t cnt = std::min(NODE_MAX_LEAF, n.index_count - k);
-                    const bool last = k + cnt == n.index_count;
-                    DevNode c;
-                    for (int x = 0; x < 3; ++x) { c.bmin[x] = -inf; c.bmax[x] = inf; }
-                    c.a = f.first_tri[ni] + k;
-                    c.b = (last ? esc : (uint32_t)out_nodes.size() + 1u) | (cnt << NODE_LINK_BITS);
-                    out_nodes.push_back(c);       // may reallocate: `d` is not used after this loop
-                }
-            }
-        }
-    }
-    if (out_nodes.size() >= NODE_END) return fail(MI355RT_ERR_INVALID, "more than 2^26 BVH nodes");
-    return MI355RT_OK;
-}
-
-// Is a mesh untransformed?  world_to_object (column-major, w2o[4 * column + row]) with a diagonal of exact ones, exact zeros (of either sign) off the
-// diagonal of the upper 3 x 3 and a zero translation: the case rt_intersect.h's ray_nonzero_finite() reasons about.
-bool xform_is_identity(const float* w2o) {
-    for (int k : {4, 8, 1, 9, 2, 6, 12, 13, 14}) if (w2o[k] != 0.0f) return false;            // (NaN != 0 too)
-    return w2o[0] == 1.0f && w2o[5] == 1.0f && w2o[10] == 1.0f;
-}
-
-// The 6 world normals a cube hit can produce (cube.rs:105-136): normalized(world_to_object^T * (+-e_k, 0)) with
-// exactly the device's operation order (xform_normal + normalized in rt_intersect.h / rt_math.h; this file is compiled
-// with -ffp-contract=off too), so the kernel can select instead of recomputing sqrt and divide per hit.
-void cube_normal_table(float* d) {
-    const float EPS = 1e-4f;
-    for (int k = 0; k < 3; ++k) for (int sgn = 0; sgn < 2; ++sgn) {
-        volatile float n[3] = {0.0f, 0.0f, 0.0f};
-        n[k] = sgn ? -1.0f : 1.0f;
-        float v[3];
-        for (int r = 0; r < 3; ++r) {
-            volatile float a = d[4 * r + 0] * n[0], b = d[4 * r + 1] * n[1], c = d[4 * r + 2] * n[2];
-            volatile float s1 = a + b; volatile float s2 = s1 + c; volatile float s3 = s2 + d[31 + r];
-            v[r] = s3;
-        }
-        volatile float xx = v[0] * v[0], yy = v[1] * v[1], zz = v[2] * v[2];
-        volatile float l2a = xx + yy; volatile float l2 = l2a + zz;
-        const float l = std::sqrt((float)l2);
-        float* out = d + 34 + 3 * (2 * k + sgn);
-        if (l < EPS) { out[0] = v[0]; out[1] = v[1]; out[2] = v[2]; }
-        else { volatile float inv = 1.0f / l; out[0] = v[0] * inv; out[1] = v[1] * inv; out[2] = v[2] * inv; }
-    }
-}
-
+// The upload of a prepared scene (rt_prepare.h: validated and laid out without HIP) and what the context keeps of it.
 int build_device_scene(mi355rt_context* ctx, const mi355rt_scene* sc) {
-    if (!sc) return fail(MI355RT_ERR_INVALID, "scene is null");
+    PreparedScene s;
+    int rc = prepare_scene(sc, s); if (rc) return rc;
     const bool has_sky = sc->sky_rgb != nullptr;
-    if (has_sky != (sc->sky_width != 0 && sc->sky_height != 0) || (!has_sky && (sc->sky_width || sc->sky_height)))
-        return fail(MI355RT_ERR_INVALID, "sky_rgb / sky_width / sky_height are inconsistent");
-    if (has_sky && ((uint64_t)sc->sky_width * sc->sky_height > (1ull << 28) || sc->sky_width >= (1u << 24) || sc->sky_height >= (1u << 24)))
-        return fail(MI355RT_ERR_INVALID, "skybox too large");
-    if (sc->n_primitives && !sc->primitives) return fail(MI355RT_ERR_INVALID, "primitives is null");
-    if (sc->n_materials && !sc->materials) return fail(MI355RT_ERR_INVALID, "materials is null");
-    if (sc->n_textures && !sc->textures) return fail(MI355RT_ERR_INVALID, "textures is null");
-    uint64_t n_texels = 0;
-    for (uint32_t i = 0; i < sc->n_textures; ++i) {
-        const mi355rt_texture& t = sc->textures[i];
-        if (!t.rgba8 || t.width == 0 || t.height == 0 || t.width >= (1u << 24) || t.height >= (1u << 24)) return fail(MI355RT_ERR_INVALID, "texture: null image or bad size");
-        n_texels += (uint64_t)t.width * t.height;
-    }
-    if (n_texels > (1ull << 30)) return fail(MI355RT_ERR_INVALID, "textures larger than 2^30 texels in total");
-    for (uint32_t i = 0; i < sc->n_materials; ++i) {
-        if (sc->materials[i].kind >= MI355RT_MAT_KIND_COUNT) return fail(MI355RT_ERR_INVALID, "material kind");
-        if (sc->materials[i].kind == MI355RT_MAT_TEXTURE && sc->materials[i].texture >= sc->n_textures) return fail(MI355RT_ERR_INVALID, "material texture index");
-    }
-
-    std::vector<DevNode> nodes; std::vector<DevTri> tris; std::vector<uint32_t> mesh_roots;
-    if (sc->n_meshes && (!sc->meshes || !sc->nodes || !sc->triangles || (!sc->tri_indices && sc->n_tri_indices))) return fail(MI355RT_ERR_INVALID, "mesh arrays are null");
-    { int rc = flatten_meshes(sc, nodes, tris, mesh_roots); if (rc) return rc; }
-    std::vector<DevPrim> prims(sc->n_primitives);
-    bool all_meshes_identity = true, all_meshes_shallow = true;
-    for (uint32_t i = 0; i < sc->n_primitives; ++i) {
-        const mi355rt_primitive& p = sc->primitives[i];
-        DevPrim& d = prims[i];
-        std::memset(&d, 0, sizeof d);
-        if (p.kind >= MI355RT_PRIM_KIND_COUNT) return fail(MI355RT_ERR_INVALID, "primitive kind");
-        if (p.material >= sc->n_materials) return fail(MI355RT_ERR_INVALID, "primitive material index");
-        d.kind = p.kind; d.material = p.material;
-        std::memcpy(d.mat0, &sc->materials[p.material], 16);      // kind + albedo, beside the geometry (rt_device.h)
-        // The reference cannot render a sphere of |radius| < 1e-4: sphere.rs:38 divides by the radius with `Vec3 / f32`, which panics
-        // below EPSILON (vec3.rs:120-122) the first time the sphere is hit.  Refused here rather than rendered.
-        if (p.kind == MI355RT_PRIM_SPHERE && std::fabs(p.data[3]) < 1e-4f)
-            return fail(MI355RT_ERR_INVALID, "sphere radius |r| < 1e-4: the reference panics on it (Vec3 / f32, vec3.rs:120-122 via sphere.rs:38)");
-        // The quad test divides by dot(normal, direction) with the short division of rt_math.h (div_bounded), proven equal to `/` for divisors of
-        // magnitude <= 2^25.  The reference's constructor always stores a unit normal (quad.rs:26-79, n = normalize(e0 x e1)), so |divisor| <= ~1;
-        // a caller that hands in a scaled normal would leave the proven range while the reference semantics (IEEE division) go on: refused.
-        if (p.kind == MI355RT_PRIM_QUAD) {
-            bool ok = true;
-            for (int k = 9; k < 12; ++k) ok = ok && std::fabs(p.data[k]) <= 0x1p20f;                       // (false for NaN and infinities too)
-            if (!ok) return fail(MI355RT_ERR_INVALID, "quad normal (data[9..11]) is not finite or larger than 2^20: the reference stores a unit normal (quad.rs:26-79)");
-        }
-        if (p.kind == MI355RT_PRIM_CUBE || p.kind == MI355RT_PRIM_MESH) {
-            const float* o2w = p.data; const float* w2o = p.data + 16;
-            float t[52] = {};                                 // matrix-shaped staging: w2o[16] column-major, o2w[12], zd[3], zn[3], the cube's normal table
-            std::memcpy(t, w2o, 64);
-            for (int c = 0; c < 4; ++c) for (int r = 0; r < 3; ++r) t[16 + 3 * c + r] = o2w[4 * c + r];
-            volatile float zero = 0.0f;                       // keep the IEEE product (sign of zero, NaN) exactly
-            for (int r = 0; r < 3; ++r) t[28 + r] = w2o[12 + r] * zero;
-            for (int r = 0; r < 3; ++r) t[31 + r] = w2o[4 * r + 3] * zero;
-            if (p.kind == MI355RT_PRIM_CUBE) cube_normal_table(t);
-            // The record (rt_device.h): what the hit test reads -- the 3 x 3 part of w2o, its translation, zd -- as ONE run of 15 words, so that the
-            // wave-uniform walk fetches it with one scalar load instead of ten pieces picked out of a 4 x 4 matrix.
-            for (int c = 0; c < 4; ++c) for (int r = 0; r < 3; ++r) d.d[3 * c + r] = t[4 * c + r];
-            for (int r = 0; r < 3; ++r) d.d[12 + r] = t[28 + r];
-            for (int k = 16; k < 28; ++k) d.d[k] = t[k];
-            for (int k = 31; k < 52; ++k) d.d[k] = t[k];
-            if (p.kind == MI355RT_PRIM_MESH) {
-                if (p.mesh >= sc->n_meshes) return fail(MI355RT_ERR_INVALID, "primitive mesh index");
-                d.node_begin = mesh_roots[p.mesh];
-                all_meshes_identity = all_meshes_identity && xform_is_identity(w2o);
-                all_meshes_shallow = all_meshes_shallow && sc->meshes[p.mesh].node_count <= WF_SHALLOW_NODES;
-            }
-        } else if (p.kind == MI355RT_PRIM_QUAD) {               // normal and plane constant first (what every ray needs), then base, e0, e1, the two 1 / |e|^2
-            for (int k = 0; k < 4; ++k) d.d[k] = p.data[9 + k];
-            for (int k = 0; k < 9; ++k) d.d[4 + k] = p.data[k];
-            d.d[13] = p.data[13]; d.d[14] = p.data[14];
-        } else {
-            std::memcpy(d.d, p.data, 32 * sizeof(float));
-        }
-    }
-    for (uint32_t i = sc->n_primitives; i-- > 0;)               // runs of one kind: the list walk loops over a run without re-dispatching on the kind
-        prims[i].run_end = (i + 1 < sc->n_primitives && prims[i + 1].kind == prims[i].kind) ? prims[i + 1].run_end : i + 1;
-    int rc;
-    if ((rc = ctx->prims.ensure(prims.size()))) return rc;
+    if ((rc = ctx->prims.ensure(s.prims.size()))) return rc;
     if ((rc = ctx->mats.ensure(sc->n_materials))) return rc;
-    if ((rc = ctx->nodes.ensure(nodes.size()))) return rc;
-    if ((rc = ctx->tris.ensure(tris.size()))) return rc;
+    if ((rc = ctx->nodes.ensure(s.nodes.size()))) return rc;
+    if ((rc = ctx->tris.ensure(s.tris.size()))) return rc;
     static_assert(sizeof(DevMat) == sizeof(mi355rt_material), "material layout is shared with the ABI");
-    if (!prims.empty()) HIP_TRY(hipMemcpy(ctx->prims.p, prims.data(), prims.size() * sizeof(DevPrim), hipMemcpyHostToDevice));
+    if (!s.prims.empty()) HIP_TRY(hipMemcpy(ctx->prims.p, s.prims.data(), s.prims.size() * sizeof(DevPrim), hipMemcpyHostToDevice));
     if (sc->n_materials) HIP_TRY(hipMemcpy(ctx->mats.p, sc->materials, sc->n_materials * sizeof(DevMat), hipMemcpyHostToDevice));
-    if (!nodes.empty()) HIP_TRY(hipMemcpy(ctx->nodes.p, nodes.data(), nodes.size() * sizeof(DevNode), hipMemcpyHostToDevice));
-    if (!tris.empty()) HIP_TRY(hipMemcpy(ctx->tris.p, tris.data(), tris.size() * sizeof(DevTri), hipMemcpyHostToDevice));
-    ctx->n_prims = sc->n_primitives; ctx->n_mats = sc->n_materials; ctx->n_nodes = nodes.size();
+    if (!s.nodes.empty()) HIP_TRY(hipMemcpy(ctx->nodes.p, s.nodes.data(), s.nodes.size() * sizeof(DevNode), hipMemcpyHostToDevice));
+    if (!s.tris.empty()) HIP_TRY(hipMemcpy(ctx->tris.p, s.tris.data(), s.tris.size() * sizeof(DevTri), hipMemcpyHostToDevice));
+    ctx->n_prims = sc->n_primitives; ctx->n_mats = sc->n_materials; ctx->n_nodes = s.nodes.size();
     std::memcpy(ctx->miss, sc->miss_color, 12);
     ctx->sky_w = ctx->sky_h = 0;
     if (has_sky) {
@@ -462,7 +191,7 @@ int build_device_scene(mi355rt_context* ctx, const mi355rt_scene* sc) {
         ctx->sky_w = sc->sky_width; ctx->sky_h = sc->sky_height;
     }
     if (sc->n_textures) {
-        if ((rc = ctx->texels.ensure((size_t)n_texels))) return rc;
+        if ((rc = ctx->texels.ensure((size_t)s.n_texels))) return rc;
         if ((rc = ctx->textures.ensure(sc->n_textures))) return rc;
         std::vector<DevTexture> table(sc->n_textures);
         size_t off = 0;
@@ -475,43 +204,9 @@ int build_device_scene(mi355rt_context* ctx, const mi355rt_scene* sc) {
         }
         HIP_TRY(hipMemcpy(ctx->textures.p, table.data(), table.size() * sizeof(DevTexture), hipMemcpyHostToDevice));
     }
-    uint32_t n_mesh_prims = 0;
-    for (const auto& pr : prims) n_mesh_prims += pr.kind == MI355RT_PRIM_MESH;
-    const bool has_mesh = n_mesh_prims != 0;
-    uint32_t scene_mats = 0u;                                        // which material kinds a ray can meet (bit k = MI355RT_MAT_k): those the primitives refer to
-    uint32_t scene_prim_kinds = 0u;                                  // ... and which primitive kinds the list holds (bit k = MI355RT_PRIM_k)
-    for (uint32_t i = 0; i < sc->n_primitives; ++i) { scene_mats |= MATBIT(sc->materials[sc->primitives[i].material].kind); scene_prim_kinds |= 1u << sc->primitives[i].kind; }
-    auto covers = [&](uint32_t variant) { return (scene_mats & ~VARIANT_TABLE[variant].mats) == 0u; };
-    auto kinds_covered = [&](uint32_t variant) { return (scene_prim_kinds & ~VARIANT_TABLE[variant].prims) == 0u; };       // likewise for the primitive kinds of the list (a mesh among them)
-    ctx->has_mesh = has_mesh;
-    // Scenes with meshes: the wavefront kernel (path state in LDS, stage queues).  No mesh: a lockstep kernel.  In both
-    // families the most pruned instantiation whose material set covers the scene's (rt_device.h, VARIANT_TABLE): the branches of
-    // the kinds a scene does not have are compiled out -- they set the register peak.  The library reads NO environment
-    // variables; the diagnostic hook mi355rt_debug_set_knob("kernel", v) may name another variant this library was built with.
-    // ... and, where the meshes are all untransformed (OBJ data in world space: teapot), the instantiation whose mesh_setup skips the matrix products.
-    // ... and, for transformed meshes whose trees are all small (semesterbild), the instantiation with the shorter WALK rounds (rt_wavefront.h).
-    if (has_mesh) ctx->variant = covers(KERNEL_WAVEFRONT_NOMETAL) ? (all_meshes_identity ? KERNEL_WAVEFRONT_NOMETAL_IDENT : all_meshes_shallow ? KERNEL_WAVEFRONT_NOMETAL_SHALLOW : KERNEL_WAVEFRONT_NOMETAL)
-                                                                  : KERNEL_WAVEFRONT;
-    else {
-        // Mesh-free lists run on a lockstep kernel -- unless the shading step diverges EXPENSIVELY: a rough conductor (ln, atan, two
-        // sin_cos, the conductor's Fresnel term: ~400 instructions) next to another scattering material.  In lockstep a wave pays that branch
-        // whenever any lane takes it (veach-mis: in 71 % of its iterations, for 6.8 lanes); the wavefront kernel's material-sorted SHADE
-        // passes run it at ~57 lanes: veach-mis 18.30 -> 16.75 ms at 256 spp.  Cheap mixtures (Lambert + metal + dielectric + plastic)
-        // measured 3-7 % FASTER in lockstep (tools/ab_fuzz_scene.py), and so stay there.
-        const bool rough = (scene_mats & MATS_ROUGH) != 0u, other_scatter = (scene_mats & ~(MATS_ROUGH | MATS_TERMINAL)) != 0u;
-        ctx->variant = covers(KERNEL_LOCKSTEP_SIMPLE) ? (kinds_covered(KERNEL_LOCKSTEP_SIMPLE_QC) ? KERNEL_LOCKSTEP_SIMPLE_QC : KERNEL_LOCKSTEP_SIMPLE)   // (... pruned to quads and cubes where the list holds nothing else: cornell)
-                     : (rough && other_scatter && covers(KERNEL_WAVEFRONT_MESHFREE)) ? KERNEL_WAVEFRONT_MESHFREE
-                     : covers(KERNEL_LOCKSTEP_NOSPEC) ? KERNEL_LOCKSTEP_NOSPEC : KERNEL_LOCKSTEP;
-    }
-    if (ctx->forced_variant >= 0) {
-        const uint32_t v = (uint32_t)ctx->forced_variant;
-        const bool ok = render_ctr_variant_built(v) && VARIANT_TABLE[v].forceable && covers(v) && kinds_covered(v) &&
-                        !(VARIANT_TABLE[v].identity_meshes && !(has_mesh && all_meshes_identity));
-        if (ok) ctx->variant = v;
-    }
-    // Root-box test right at mesh set-up (reference build's state machine): when several meshes share the list (teapot +5..12 %; a single
-    // mesh loses 5-10 %).
-    ctx->inline_steps = ctx->knob_inline_steps >= 0 ? (uint32_t)ctx->knob_inline_steps : (n_mesh_prims >= 2 ? 1u : 0u);
+    ctx->has_mesh = s.n_mesh_prims != 0;
+    ctx->variant = choose_variant(s, ctx->forced_variant, built_variants());
+    ctx->inline_steps = choose_inline_steps(s, ctx->knob_inline_steps);
     return MI355RT_OK;
 }
 
@@ -555,7 +250,7 @@ int mi355rt_debug_set_knob(mi355rt_context* ctx, const char* name, int value) {
 // 1 when this library holds the counter-mode kernel `variant` (the retired mesh kernels exist in the reference build only)
 int mi355rt_debug_has_variant(uint32_t variant) { return render_ctr_variant_built(variant) ? 1 : 0; }
 
-const char* mi355rt_last_error(void) { return g_err.c_str(); }
+const char* mi355rt_last_error(void) { return last_error().c_str(); }
 uint32_t mi355rt_abi_version(void) { return MI355RT_ABI_VERSION; }
 
 int mi355rt_rows_selected(const mi355rt_settings* settings, const mi355rt_options* options, uint32_t* out_rows) {
@@ -1001,9 +696,9 @@ int mi355rt_trace_rays(const mi355rt_scene* scene, const mi355rt_ray* rays, uint
     if (!rc) rc = mi355rt_context_trace_rays(ctx, d_rays.p, n_rays, d_hits.p, nullptr);
     if (!rc && hipMemcpy(out_hits, d_hits.p, (size_t)n_rays * sizeof(mi355rt_hit), hipMemcpyDeviceToHost) != hipSuccess) rc = fail(MI355RT_ERR_HIP, "copy back hits");   // (waits for the query)
     d_rays.release(); d_hits.release();
-    std::string keep; keep.swap(g_err);                               // (destroy may overwrite the message of the failure being reported; swap never throws)
+    std::string keep; keep.swap(last_error());                               // (destroy may overwrite the message of the failure being reported; swap never throws)
     mi355rt_context_destroy(ctx);
-    g_err.swap(keep);
+    last_error().swap(keep);
     return rc;
     });
 }
@@ -1013,6 +708,27 @@ int mi355rt_debug_kernel_variant(mi355rt_context* ctx, uint32_t* out) {
     return guard([&]() -> int {
     if (!ctx || !out || !ctx->have_scene) return fail(MI355RT_ERR_INVALID, "context has no scene");
     *out = ctx->variant;
+    return MI355RT_OK;
+    });
+}
+
+// Diagnostic hook (not part of the public header): what set_scene would upload and choose for `scene`, without a device -- no HIP call, no
+// context.  forced_variant: the "kernel" knob, -1 = the automatic choice.  Two calls, as mi355rt_bvh_build: with the arrays null it only
+// counts; with an array given, its n_* holds the capacity on entry.  prims / nodes / tris: DevPrim / DevNode / DevTri records (rt_device.h).
+int mi355rt_debug_prepare_scene(const mi355rt_scene* scene, int forced_variant, uint32_t* out_variant, uint32_t* out_inline_steps,
+                                void* prims, uint32_t* n_prims, void* nodes, uint32_t* n_nodes, void* tris, uint32_t* n_tris) {
+    return guard([&]() -> int {
+    if (!out_variant || !out_inline_steps || !n_prims || !n_nodes || !n_tris) return fail(MI355RT_ERR_INVALID, "debug_prepare_scene: null");
+    if (forced_variant < -1 || forced_variant >= (int)KERNEL_VARIANTS) return fail(MI355RT_ERR_INVALID, "knob kernel");
+    PreparedScene s;
+    const int rc = prepare_scene(scene, s); if (rc) return rc;
+    if ((prims && *n_prims < s.prims.size()) || (nodes && *n_nodes < s.nodes.size()) || (tris && *n_tris < s.tris.size())) return fail(MI355RT_ERR_INVALID, "debug_prepare_scene: capacity");
+    if (prims && !s.prims.empty()) std::memcpy(prims, s.prims.data(), s.prims.size() * sizeof(DevPrim));
+    if (nodes && !s.nodes.empty()) std::memcpy(nodes, s.nodes.data(), s.nodes.size() * sizeof(DevNode));
+    if (tris && !s.tris.empty()) std::memcpy(tris, s.tris.data(), s.tris.size() * sizeof(DevTri));
+    *n_prims = (uint32_t)s.prims.size(); *n_nodes = (uint32_t)s.nodes.size(); *n_tris = (uint32_t)s.tris.size();
+    *out_variant = choose_variant(s, forced_variant, built_variants());
+    *out_inline_steps = choose_inline_steps(s, -1);
     return MI355RT_OK;
     });
 }
@@ -1149,9 +865,9 @@ int mi355rt_render(const mi355rt_scene* scene, const mi355rt_camera* camera, con
     }
     if (d_packed) (void)hipFree(d_packed);
     if (d_linear) (void)hipFree(d_linear);
-    std::string keep; keep.swap(g_err);                               // (destroy may overwrite the message of the failure being reported; swap never throws)
+    std::string keep; keep.swap(last_error());                               // (destroy may overwrite the message of the failure being reported; swap never throws)
     mi355rt_context_destroy(ctx);
-    g_err.swap(keep);
+    last_error().swap(keep);
     return rc;
     });
 }
@@ -1185,7 +901,7 @@ int mi355rt_render_multi(const mi355rt_scene* scene, const mi355rt_camera* camer
         Part& me = parts[d];
         mi355rt_options o = base; o.n_parts = n_devices; o.part = d;
         RowSel sel;
-        if ((me.rc = select_rows(*settings, &o, sel))) { me.err = g_err; return; }
+        if ((me.rc = select_rows(*settings, &o, sel))) { me.err = last_error(); return; }
         if (sel.rows.empty()) return;
         const size_t npix = sel.rows.size() * (size_t)W;
         std::vector<uint32_t> h_packed(npix); std::vector<float> h_linear(out_linear ? npix * 3 : 0);
@@ -1196,7 +912,7 @@ int mi355rt_render_multi(const mi355rt_scene* scene, const mi355rt_camera* camer
         if (!me.rc) me.rc = mi355rt_context_render(ctx, &o, d_packed, d_linear, nullptr, &me.st);
         if (!me.rc && hipMemcpy(h_packed.data(), d_packed, npix * 4, hipMemcpyDeviceToHost) != hipSuccess) me.rc = fail(MI355RT_ERR_HIP, "copy back packed");
         if (!me.rc && out_linear && hipMemcpy(h_linear.data(), d_linear, npix * 12, hipMemcpyDeviceToHost) != hipSuccess) me.rc = fail(MI355RT_ERR_HIP, "copy back linear");
-        if (me.rc) me.err = g_err;
+        if (me.rc) me.err = last_error();
         else for (size_t j = 0; j < sel.rows.size(); ++j) {                        // de-interleave: local row j is image row sel.rows[j]
             const size_t dst = (size_t)(sel.rows[j] - row0) * W;
             std::memcpy(out_packed + dst, h_packed.data() + j * W, (size_t)W * 4);
@@ -1208,7 +924,7 @@ int mi355rt_render_multi(const mi355rt_scene* scene, const mi355rt_camera* camer
     auto work = [&](uint32_t d) noexcept {
         mi355rt_context* ctx = nullptr; uint32_t* d_packed = nullptr; float* d_linear = nullptr;
         const int rc = guard([&]() -> int { work_body(d, ctx, d_packed, d_linear); return MI355RT_OK; });
-        if (rc != MI355RT_OK && parts[d].rc == MI355RT_OK) { parts[d].rc = rc; try { parts[d].err = g_err; } catch (...) {} }
+        if (rc != MI355RT_OK && parts[d].rc == MI355RT_OK) { parts[d].rc = rc; try { parts[d].err = last_error(); } catch (...) {} }
         if (d_packed) (void)hipFree(d_packed);
         if (d_linear) (void)hipFree(d_linear);
         if (ctx) mi355rt_context_destroy(ctx);
@@ -1288,9 +1004,9 @@ int mi355rt_render_progressive(const mi355rt_scene* scene, const mi355rt_camera*
     if (d_packed) (void)hipFree(d_packed);
     if (d_linear) (void)hipFree(d_linear);
     if (d_accum) (void)hipFree(d_accum);
-    std::string keep; keep.swap(g_err);                               // (destroy may overwrite the message of the failure being reported; swap never throws)
+    std::string keep; keep.swap(last_error());                               // (destroy may overwrite the message of the failure being reported; swap never throws)
     mi355rt_context_destroy(ctx);
-    g_err.swap(keep);
+    last_error().swap(keep);
     return rc;
     });
 }

@@ -85,7 +85,7 @@ DI bool hit_plane(cprim_t pr, uint32_t i, f3 ro, f3 rd, float t_min, Cand& c) {
 // predicate so the wave takes a single branch into the parallelogram test; the arithmetic is unchanged (the
 // division also runs for |denom| < EPS lanes, whose result is discarded).
 // FASTD: t by div_bounded() (rt_math.h).  t is used only where |denom| >= EPS, and |denom| <= |n||d| ~ 1 (the host refuses quads whose normal
-// is not of unit scale: rt_api.cpp build_device_scene), so the divisor is in range; a
+// is not of unit scale: rt_prepare.cpp prepare_scene), so the divisor is in range; a
 // numerator below 2^-100 gives a |t| below 2^-86 either way (rejected: t <= t_min), one of 2^100 or more sends the whole wave to the
 // compiler's division (ballot); infinities and NaN come out of v_div_fixup_f32 as they do there.
 template <bool FASTD = false>
@@ -140,7 +140,7 @@ template <class PrimPtr> DI f3 xform_normal(PrimPtr pr, f3 n) {               //
 }
 DI float glam_signum(float v) { if (v != v) return v; return copysignf(1.0f, v); }
 
-// Untransformed meshes (world_to_object == identity; the host checks it: rt_api.cpp xform_is_identity).  glam's Mat4 * Vec4 computes, per component,
+// Untransformed meshes (world_to_object == identity; the host checks it: rt_prepare.cpp xform_is_identity).  glam's Mat4 * Vec4 computes, per component,
 // ((1*x + (+-0)*y) + (+-0)*z) + (+-0): for finite y, z the middle terms are zeros, and x + (+-0) == x for every x != 0 -- the object-space ray IS the
 // world-space ray, bit for bit, unless a component is a zero (whose SIGN the sum could change) or not finite (0 * inf = NaN).  The kernels instantiated
 // for such scenes (MESH_IDENT) therefore skip the two matrix products of mesh_setup for waves whose rays all pass this test, and take the general
@@ -188,7 +188,7 @@ DI bool hit_cube(cprim_t pr, uint32_t i, f3 ro_w, f3 rd_w, float t_min, C& c) {
 }
 // The record of a cube hit.  The object-space normal is +-e_axis, normalize_or_zero() of such a vector is the vector
 // itself (1/sqrt(1) == 1), and the world normal normalized(w2o^T * (n, 0)) therefore takes one of 6 values per cube, which
-// the host precomputed with the same f32 operations (DevPrim.d[34..51], rt_api.cpp cube_normal_table).
+// the host precomputed with the same f32 operations (DevPrim.d[34..51], rt_prepare.cpp cube_normal_table).
 template <class PrimPtr>
 DI f3 cube_po(PrimPtr pr, const Cand& c, f3 ro_w, f3 rd_w) {                                // cube.rs:104, from the slab distance the candidate kept
     const f3 ro = xform_w2o_point(pr, ro_w), rd = xform_w2o_dir(pr, rd_w);

@@ -1,0 +1,346 @@
+// rt_prepare.cpp -- scene preparation and the other HIP-free host code of libmi355rt.so (rt_prepare.h): no HIP call, no context.
+// Compiled with the device sources' flags (-ffp-contract=off: cube_normal_table repeats the device's operation order).
+#include "rt_prepare.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <initializer_list>
+#include <limits>
+#include <utility>
+
+using namespace mi355rt;
+
+namespace {
+thread_local std::string g_err;
+}  // namespace
+
+namespace mi355rt {
+
+int fail(int code, const std::string& msg) { g_err = msg; return code; }
+int fail_noexcept(int code, const char* msg) noexcept { try { g_err.assign(msg); } catch (...) { g_err.clear(); } return code; }
+std::string& last_error() { return g_err; }
+
+// Options of ABI version 4 are accepted as well: version 5 added entry points (mi355rt_multi_context_*), no struct changed.
+int select_rows(const mi355rt_settings& st, const mi355rt_options* o, RowSel& sel) {
+    uint32_t rb = 0, re = st.height, strip = 1, parts = 1, part = 0;
+    if (o) {
+        if (o->abi_version != MI355RT_ABI_VERSION && o->abi_version != 4u) return fail(MI355RT_ERR_INVALID, "options.abi_version mismatch");
+        rb = o->row_begin; re = o->row_end ? o->row_end : st.height;
+        strip = o->strip_rows ? o->strip_rows : 1; parts = o->n_parts ? o->n_parts : 1; part = o->part;
+        if (o->rng_mode != MI355RT_RNG_CTR && o->rng_mode != MI355RT_RNG_REF) return fail(MI355RT_ERR_INVALID, "options.rng_mode");
+    }
+    if (re > st.height || rb > re || part >= parts) return fail(MI355RT_ERR_INVALID, "row selection out of range");
+    sel.rows.clear();
+    for (uint32_t y = rb; y < re; ++y) if ((y / strip) % parts == part) sel.rows.push_back(y);
+    return MI355RT_OK;
+}
+
+int check_settings(const mi355rt_settings* st) {
+    if (!st) return fail(MI355RT_ERR_INVALID, "settings is null");
+    if (st->width == 0 || st->height == 0 || st->samples_per_pixel == 0) return fail(MI355RT_ERR_INVALID, "width/height/spp must be > 0");
+    if ((uint64_t)st->width * st->height >= (1ull << 31)) return fail(MI355RT_ERR_INVALID, "image too large");
+    if (st->width >= (1u << 24) || st->height >= (1u << 24)) return fail(MI355RT_ERR_INVALID, "width/height must be < 2^24 (x as f32 is exact, renderer.rs:96)");
+    if (st->samples_per_pixel >= (1u << 30)) return fail(MI355RT_ERR_INVALID, "samples_per_pixel too large");
+    return MI355RT_OK;
+}
+
+}  // namespace mi355rt
+
+namespace {
+
+// Re-lay the meshes' BVHs (any node order, explicit child indices -- the shape of BVHNode, bvh.rs:7-12) into the
+// two-link form the kernels walk (rt_device.h, DevNode): every node carries where the walk goes when its box is hit
+// (inner: the left child, bvh.rs:142) and where it goes otherwise / afterwards (the "escape": the next node of the
+// reference's left-then-right recursion that is not below this one).  The links make the visit order independent of
+// the storage order, so nodes are stored LEVEL BY LEVEL (level 0 of every mesh, then level 1, ...): the levels every
+// ray touches come first and are the part the state-machine kernel keeps in LDS.  Triangles go into leaf-visit order.
+struct MeshFlat {
+    std::vector<uint32_t> order;                 // input node ids in BFS order
+    std::vector<uint32_t> level_begin;           // order[level_begin[L] .. level_begin[L+1]) = level L
+    std::vector<uint32_t> escape;                // per input node: input id of its escape node, NODE_END if none
+    std::vector<uint32_t> first_tri;             // per input leaf: index of its first triangle in out_tris
+    std::vector<uint32_t> global_id;             // per input node: index in the device array
+};
+
+int flatten_mesh(const mi355rt_scene* sc, const mi355rt_mesh& m, MeshFlat& f, std::vector<DevTri>& out_tris) {
+    if ((uint64_t)m.first_triangle + m.triangle_count > sc->n_triangles || m.triangle_count == 0) return fail(MI355RT_ERR_INVALID, "mesh triangle range");
+    if ((uint64_t)m.first_node + m.node_count > sc->n_nodes || m.node_count == 0) return fail(MI355RT_ERR_INVALID, "mesh node range (is the BVH missing? see mi355rt_bvh_build)");
+    if ((uint64_t)m.first_index + m.index_count > sc->n_tri_indices) return fail(MI355RT_ERR_INVALID, "mesh index range");
+    const mi355rt_bvh_node* nodes = sc->nodes + m.first_node;
+    const uint32_t* indices = sc->tri_indices + m.first_index;
+    const mi355rt_triangle* tris = sc->triangles + m.first_triangle;
+    f.escape.assign(m.node_count, NODE_END); f.first_tri.assign(m.node_count, 0u); f.global_id.assign(m.node_count, NODE_END);
+    // pre-order with an explicit stack (input depth is not trusted): escapes, leaf-order triangles, cycle check
+    std::vector<uint8_t> seen(m.node_count, 0);
+    std::vector<std::pair<uint32_t, uint32_t>> stack;   // (node, its escape)
+    stack.emplace_back(0u, NODE_END);
+    uint32_t visited = 0;
+    while (!stack.empty()) {
+        const auto [ni, esc] = stack.back(); stack.pop_back();
+        if (ni >= m.node_count) return fail(MI355RT_ERR_INVALID, "BVH child index out of range");
+        if (seen[ni] || ++visited > m.node_count) return fail(MI355RT_ERR_INVALID, "BVH has a cycle or shared nodes");
+        seen[ni] = 1;
+        f.escape[ni] = esc;
+        const mi355rt_bvh_node& n = nodes[ni];
+        if (n.index_count > 0) {
+            if ((uint64_t)n.first_index + n.index_count > m.index_count) return fail(MI355RT_ERR_INVALID, "BVH leaf index range");
+            f.first_tri[ni] = (uint32_t)out_tris.size();
+            for (uint32_t k = 0; k < n.index_count; ++k) {
+                const uint32_t id = indices[n.first_index + k];
+                if (id >= m.triangle_count) return fail(MI355RT_ERR_INVALID, "BVH leaf triangle id out of range");
+                const mi355rt_triangle& t = tris[id];
+                DevTri dt;
+                for (int c = 0; c < 3; ++c) { dt.v0[c] = t.v0[c]; dt.e1[c] = t.v1[c] - t.v0[c]; dt.e2[c] = t.v2[c] - t.v0[c]; dt.n[c] = t.normal[c]; }
+                out_tris.push_back(dt);
+            }
+        } else {
+            stack.emplace_back(n.right, esc);        // visited after the whole left subtree; it inherits the parent's escape
+            stack.emplace_back(n.left, n.right);     // a left child escapes to its sibling
+        }
+    }
+    // breadth-first order
+    f.order.clear(); f.level_begin.clear();
+    f.order.push_back(0u); f.level_begin.push_back(0u);
+    for (size_t lb = 0; lb < f.order.size();) {
+        const size_t le = f.order.size();
+        for (size_t i = lb; i < le; ++i) {
+            const mi355rt_bvh_node& n = nodes[f.order[i]];
+            if (n.index_count == 0) { f.order.push_back(n.left); f.order.push_back(n.right); }
+        }
+        lb = le;
+        if (f.order.size() > le) f.level_begin.push_back((uint32_t)le);
+    }
+    f.level_begin.push_back((uint32_t)f.order.size());
+    return MI355RT_OK;
+}
+
+int flatten_meshes(const mi355rt_scene* sc, std::vector<DevNode>& out_nodes, std::vector<DevTri>& out_tris, std::vector<uint32_t>& roots) {
+    std::vector<MeshFlat> flat(sc->n_meshes);
+    size_t max_levels = 0, total = 0;
+    for (uint32_t m = 0; m < sc->n_meshes; ++m) {
+        int rc = flatten_mesh(sc, sc->meshes[m], flat[m], out_tris);
+        if (rc) return rc;
+        max_levels = std::max(max_levels, flat[m].level_begin.size() - 1);
+        total += flat[m].order.size();
+    }
+    // the walk packs node indices into 26 bits (and addresses nodes / triangles with 32-bit byte offsets)
+    if (total >= NODE_END || out_tris.size() > (1u << 26)) return fail(MI355RT_ERR_INVALID, "more than 2^26 BVH nodes or triangles");
+    // Storage order: breadth-first, level by level across all meshes, until the LDS copy is full (LDS_NODE_CAP nodes: the
+    // levels every ray touches); every subtree hanging below that front then follows in depth-first pre-order, so that a
+    // walk through the global-memory part finds a node's left child right behind it (same or next cache line).
+    uint32_t next = 0;
+    for (size_t L = 0; L < max_levels && next < LDS_NODE_CAP; ++L)
+        for (uint32_t m = 0; m < sc->n_meshes && next < LDS_NODE_CAP; ++m) {
+            MeshFlat& f = flat[m];
+            if (L + 1 >= f.level_begin.size()) continue;
+            for (uint32_t i = f.level_begin[L]; i < f.level_begin[L + 1] && next < LDS_NODE_CAP; ++i) f.global_id[f.order[i]] = next++;
+        }
+    for (uint32_t m = 0; m < sc->n_meshes; ++m) {
+        MeshFlat& f = flat[m];
+        const mi355rt_bvh_node* nodes = sc->nodes + sc->meshes[m].first_node;
+        std::vector<uint32_t> stack;
+        for (uint32_t ni : f.order) {                                   // BFS order: parents before children
+            if (f.global_id[ni] != NODE_END) continue;
+            // ni is the root of an unplaced subtree (its parent was placed, or it is a mesh root beyond the cap)
+            stack.assign(1, ni);
+            while (!stack.empty()) {
+                const uint32_t x = stack.back(); stack.pop_back();
+                f.global_id[x] = next++;
+                if (nodes[x].index_count == 0) { stack.push_back(nodes[x].right); stack.push_back(nodes[x].left); }
+            }
+        }
+    }
+    out_nodes.assign(total, DevNode{});
+    roots.assign(sc->n_meshes, 0u);
+    for (uint32_t m = 0; m < sc->n_meshes; ++m) {
+        const MeshFlat& f = flat[m];
+        const mi355rt_bvh_node* nodes = sc->nodes + sc->meshes[m].first_node;
+        roots[m] = f.global_id[0];
+        for (uint32_t ni : f.order) {
+            const mi355rt_bvh_node& n = nodes[ni];
+            DevNode& d = out_nodes[f.global_id[ni]];
+            std::memcpy(d.bmin, n.bmin, 12); std::memcpy(d.bmax, n.bmax, 12);
+            const uint32_t esc = f.escape[ni] == NODE_END ? NODE_END : f.global_id[f.escape[ni]];
+            if (n.index_count == 0) { d.a = f.global_id[n.left]; d.b = esc; }
+            else if (n.index_count <= NODE_MAX_LEAF) { d.a = f.first_tri[ni]; d.b = esc | (n.index_count << NODE_LINK_BITS); }
+            else {
+                // A leaf with more triangles than the count field holds (BVHNode::new makes them only at depth 25, bvh.rs:31;
+                // a caller-built tree may have them anywhere): its box test stays where it is, as an inner node whose "left
+                // child" is a chain of chunk leaves with infinite bounds.  An infinite box is hit by every ray (the slab test
+                // leaves t_min / t_max untouched), so the chain only adds box tests that change nothing; a miss of the real
+                // box skips the whole chain.  The chunks live behind the level-ordered part of the array.
+                d.a = (uint32_t)out_nodes.size(); d.b = esc;
+                const float inf = std::numeric_limits<float>::infinity();
+                for (uint32_t k = 0; k < n.index_count; k += NODE_MAX_LEAF) {
+                    const uint32_t cnt = std::min(NODE_MAX_LEAF, n.index_count - k);
+                    const bool last = k + cnt == n.index_count;
+                    DevNode c;
+                    for (int x = 0; x < 3; ++x) { c.bmin[x] = -inf; c.bmax[x] = inf; }
+                    c.a = f.first_tri[ni] + k;
+                    c.b = (last ? esc : (uint32_t)out_nodes.size() + 1u) | (cnt << NODE_LINK_BITS);
+                    out_nodes.push_back(c);       // may reallocate: `d` is not used after this loop
+                }
+            }
+        }
+    }
+    if (out_nodes.size() >= NODE_END) return fail(MI355RT_ERR_INVALID, "more than 2^26 BVH nodes");
+    return MI355RT_OK;
+}
+
+// Is a mesh untransformed?  world_to_object (column-major, w2o[4 * column + row]) with a diagonal of exact ones, exact zeros (of either sign) off the
+// diagonal of the upper 3 x 3 and a zero translation: the case rt_intersect.h's ray_nonzero_finite() reasons about.
+bool xform_is_identity(const float* w2o) {
+    for (int k : {4, 8, 1, 9, 2, 6, 12, 13, 14}) if (w2o[k] != 0.0f) return false;            // (NaN != 0 too)
+    return w2o[0] == 1.0f && w2o[5] == 1.0f && w2o[10] == 1.0f;
+}
+
+// The 6 world normals a cube hit can produce (cube.rs:105-136): normalized(world_to_object^T * (+-e_k, 0)) with
+// exactly the device's operation order (xform_normal + normalized in rt_intersect.h / rt_math.h; this file is compiled
+// with -ffp-contract=off too), so the kernel can select instead of recomputing sqrt and divide per hit.
+void cube_normal_table(float* d) {
+    const float EPS = 1e-4f;
+    for (int k = 0; k < 3; ++k) for (int sgn = 0; sgn < 2; ++sgn) {
+        volatile float n[3] = {0.0f, 0.0f, 0.0f};
+        n[k] = sgn ? -1.0f : 1.0f;
+        float v[3];
+        for (int r = 0; r < 3; ++r) {
+            volatile float a = d[4 * r + 0] * n[0], b = d[4 * r + 1] * n[1], c = d[4 * r + 2] * n[2];
+            volatile float s1 = a + b; volatile float s2 = s1 + c; volatile float s3 = s2 + d[31 + r];
+            v[r] = s3;
+        }
+        volatile float xx = v[0] * v[0], yy = v[1] * v[1], zz = v[2] * v[2];
+        volatile float l2a = xx + yy; volatile float l2 = l2a + zz;
+        const float l = std::sqrt((float)l2);
+        float* out = d + 34 + 3 * (2 * k + sgn);
+        if (l < EPS) { out[0] = v[0]; out[1] = v[1]; out[2] = v[2]; }
+        else { volatile float inv = 1.0f / l; out[0] = v[0] * inv; out[1] = v[1] * inv; out[2] = v[2] * inv; }
+    }
+}
+
+}  // namespace
+
+namespace mi355rt {
+
+int prepare_scene(const mi355rt_scene* sc, PreparedScene& out) {
+    out = PreparedScene{};
+    if (!sc) return fail(MI355RT_ERR_INVALID, "scene is null");
+    const bool has_sky = sc->sky_rgb != nullptr;
+    if (has_sky != (sc->sky_width != 0 && sc->sky_height != 0) || (!has_sky && (sc->sky_width || sc->sky_height)))
+        return fail(MI355RT_ERR_INVALID, "sky_rgb / sky_width / sky_height are inconsistent");
+    if (has_sky && ((uint64_t)sc->sky_width * sc->sky_height > (1ull << 28) || sc->sky_width >= (1u << 24) || sc->sky_height >= (1u << 24)))
+        return fail(MI355RT_ERR_INVALID, "skybox too large");
+    if (sc->n_primitives && !sc->primitives) return fail(MI355RT_ERR_INVALID, "primitives is null");
+    if (sc->n_materials && !sc->materials) return fail(MI355RT_ERR_INVALID, "materials is null");
+    if (sc->n_textures && !sc->textures) return fail(MI355RT_ERR_INVALID, "textures is null");
+    for (uint32_t i = 0; i < sc->n_textures; ++i) {
+        const mi355rt_texture& t = sc->textures[i];
+        if (!t.rgba8 || t.width == 0 || t.height == 0 || t.width >= (1u << 24) || t.height >= (1u << 24)) return fail(MI355RT_ERR_INVALID, "texture: null image or bad size");
+        out.n_texels += (uint64_t)t.width * t.height;
+    }
+    if (out.n_texels > (1ull << 30)) return fail(MI355RT_ERR_INVALID, "textures larger than 2^30 texels in total");
+    for (uint32_t i = 0; i < sc->n_materials; ++i) {
+        if (sc->materials[i].kind >= MI355RT_MAT_KIND_COUNT) return fail(MI355RT_ERR_INVALID, "material kind");
+        if (sc->materials[i].kind == MI355RT_MAT_TEXTURE && sc->materials[i].texture >= sc->n_textures) return fail(MI355RT_ERR_INVALID, "material texture index");
+    }
+
+    if (sc->n_meshes && (!sc->meshes || !sc->nodes || !sc->triangles || (!sc->tri_indices && sc->n_tri_indices))) return fail(MI355RT_ERR_INVALID, "mesh arrays are null");
+    { int rc = flatten_meshes(sc, out.nodes, out.tris, out.mesh_roots); if (rc) return rc; }
+    std::vector<DevPrim>& prims = out.prims;
+    prims.resize(sc->n_primitives);
+    for (uint32_t i = 0; i < sc->n_primitives; ++i) {
+        const mi355rt_primitive& p = sc->primitives[i];
+        DevPrim& d = prims[i];
+        std::memset(&d, 0, sizeof d);
+        if (p.kind >= MI355RT_PRIM_KIND_COUNT) return fail(MI355RT_ERR_INVALID, "primitive kind");
+        if (p.material >= sc->n_materials) return fail(MI355RT_ERR_INVALID, "primitive material index");
+        d.kind = p.kind; d.material = p.material;
+        std::memcpy(d.mat0, &sc->materials[p.material], 16);      // kind + albedo, beside the geometry (rt_device.h)
+        // The reference cannot render a sphere of |radius| < 1e-4: sphere.rs:38 divides by the radius with `Vec3 / f32`, which panics
+        // below EPSILON (vec3.rs:120-122) the first time the sphere is hit.  Refused here rather than rendered.
+        if (p.kind == MI355RT_PRIM_SPHERE && std::fabs(p.data[3]) < 1e-4f)
+            return fail(MI355RT_ERR_INVALID, "sphere radius |r| < 1e-4: the reference panics on it (Vec3 / f32, vec3.rs:120-122 via sphere.rs:38)");
+        // The quad test divides by dot(normal, direction) with the short division of rt_math.h (div_bounded), proven equal to `/` for divisors of
+        // magnitude <= 2^25.  The reference's constructor always stores a unit normal (quad.rs:26-79, n = normalize(e0 x e1)), so |divisor| <= ~1;
+        // a caller that hands in a scaled normal would leave the proven range while the reference semantics (IEEE division) go on: refused.
+        if (p.kind == MI355RT_PRIM_QUAD) {
+            bool ok = true;
+            for (int k = 9; k < 12; ++k) ok = ok && std::fabs(p.data[k]) <= 0x1p20f;                       // (false for NaN and infinities too)
+            if (!ok) return fail(MI355RT_ERR_INVALID, "quad normal (data[9..11]) is not finite or larger than 2^20: the reference stores a unit normal (quad.rs:26-79)");
+        }
+        if (p.kind == MI355RT_PRIM_CUBE || p.kind == MI355RT_PRIM_MESH) {
+            const float* o2w = p.data; const float* w2o = p.data + 16;
+            float t[52] = {};                                 // matrix-shaped staging: w2o[16] column-major, o2w[12], zd[3], zn[3], the cube's normal table
+            std::memcpy(t, w2o, 64);
+            for (int c = 0; c < 4; ++c) for (int r = 0; r < 3; ++r) t[16 + 3 * c + r] = o2w[4 * c + r];
+            volatile float zero = 0.0f;                       // keep the IEEE product (sign of zero, NaN) exactly
+            for (int r = 0; r < 3; ++r) t[28 + r] = w2o[12 + r] * zero;
+            for (int r = 0; r < 3; ++r) t[31 + r] = w2o[4 * r + 3] * zero;
+            if (p.kind == MI355RT_PRIM_CUBE) cube_normal_table(t);
+            // The record (rt_device.h): what the hit test reads -- the 3 x 3 part of w2o, its translation, zd -- as ONE run of 15 words, so that the
+            // wave-uniform walk fetches it with one scalar load instead of ten pieces picked out of a 4 x 4 matrix.
+            for (int c = 0; c < 4; ++c) for (int r = 0; r < 3; ++r) d.d[3 * c + r] = t[4 * c + r];
+            for (int r = 0; r < 3; ++r) d.d[12 + r] = t[28 + r];
+            for (int k = 16; k < 28; ++k) d.d[k] = t[k];
+            for (int k = 31; k < 52; ++k) d.d[k] = t[k];
+            if (p.kind == MI355RT_PRIM_MESH) {
+                if (p.mesh >= sc->n_meshes) return fail(MI355RT_ERR_INVALID, "primitive mesh index");
+                d.node_begin = out.mesh_roots[p.mesh];
+                out.all_meshes_identity = out.all_meshes_identity && xform_is_identity(w2o);
+                out.all_meshes_shallow = out.all_meshes_shallow && sc->meshes[p.mesh].node_count <= WF_SHALLOW_NODES;
+            }
+        } else if (p.kind == MI355RT_PRIM_QUAD) {               // normal and plane constant first (what every ray needs), then base, e0, e1, the two 1 / |e|^2
+            for (int k = 0; k < 4; ++k) d.d[k] = p.data[9 + k];
+            for (int k = 0; k < 9; ++k) d.d[4 + k] = p.data[k];
+            d.d[13] = p.data[13]; d.d[14] = p.data[14];
+        } else {
+            std::memcpy(d.d, p.data, 32 * sizeof(float));
+        }
+    }
+    for (uint32_t i = sc->n_primitives; i-- > 0;)               // runs of one kind: the list walk loops over a run without re-dispatching on the kind
+        prims[i].run_end = (i + 1 < sc->n_primitives && prims[i + 1].kind == prims[i].kind) ? prims[i + 1].run_end : i + 1;
+    for (const auto& pr : prims) out.n_mesh_prims += pr.kind == MI355RT_PRIM_MESH;
+    for (uint32_t i = 0; i < sc->n_primitives; ++i) { out.scene_mats |= MATBIT(sc->materials[sc->primitives[i].material].kind); out.scene_prim_kinds |= 1u << sc->primitives[i].kind; }
+    return MI355RT_OK;
+}
+
+uint32_t choose_variant(const PreparedScene& s, int forced_variant, uint32_t built_mask) {
+    const uint32_t scene_mats = s.scene_mats, scene_prim_kinds = s.scene_prim_kinds;
+    const bool has_mesh = s.n_mesh_prims != 0, all_meshes_identity = s.all_meshes_identity, all_meshes_shallow = s.all_meshes_shallow;
+    auto render_ctr_variant_built = [&](uint32_t variant) { return ((built_mask >> variant) & 1u) != 0u; };   // (what rt_kernels.hip says of this library, passed in)
+    auto covers = [&](uint32_t variant) { return (scene_mats & ~VARIANT_TABLE[variant].mats) == 0u; };
+    auto kinds_covered = [&](uint32_t variant) { return (scene_prim_kinds & ~VARIANT_TABLE[variant].prims) == 0u; };       // likewise for the primitive kinds of the list (a mesh among them)
+    uint32_t chosen;
+    // Scenes with meshes: the wavefront kernel (path state in LDS, stage queues).  No mesh: a lockstep kernel.  In both
+    // families the most pruned instantiation whose material set covers the scene's (rt_device.h, VARIANT_TABLE): the branches of
+    // the kinds a scene does not have are compiled out -- they set the register peak.  The library reads NO environment
+    // variables; the diagnostic hook mi355rt_debug_set_knob("kernel", v) may name another variant this library was built with.
+    // ... and, where the meshes are all untransformed (OBJ data in world space: teapot), the instantiation whose mesh_setup skips the matrix products.
+    // ... and, for transformed meshes whose trees are all small (semesterbild), the instantiation with the shorter WALK rounds (rt_wavefront.h).
+    if (has_mesh) chosen = covers(KERNEL_WAVEFRONT_NOMETAL) ? (all_meshes_identity ? KERNEL_WAVEFRONT_NOMETAL_IDENT : all_meshes_shallow ? KERNEL_WAVEFRONT_NOMETAL_SHALLOW : KERNEL_WAVEFRONT_NOMETAL)
+                                                                  : KERNEL_WAVEFRONT;
+    else {
+        // Mesh-free lists run on a lockstep kernel -- unless the shading step diverges EXPENSIVELY: a rough conductor (ln, atan, two
+        // sin_cos, the conductor's Fresnel term: ~400 instructions) next to another scattering material.  In lockstep a wave pays that branch
+        // whenever any lane takes it (veach-mis: in 71 % of its iterations, for 6.8 lanes); the wavefront kernel's material-sorted SHADE
+        // passes run it at ~57 lanes: veach-mis 18.30 -> 16.75 ms at 256 spp.  Cheap mixtures (Lambert + metal + dielectric + plastic)
+        // measured 3-7 % FASTER in lockstep (tools/ab_fuzz_scene.py), and so stay there.
+        const bool rough = (scene_mats & MATS_ROUGH) != 0u, other_scatter = (scene_mats & ~(MATS_ROUGH | MATS_TERMINAL)) != 0u;
+        chosen = covers(KERNEL_LOCKSTEP_SIMPLE) ? (kinds_covered(KERNEL_LOCKSTEP_SIMPLE_QC) ? KERNEL_LOCKSTEP_SIMPLE_QC : KERNEL_LOCKSTEP_SIMPLE)   // (... pruned to quads and cubes where the list holds nothing else: cornell)
+                     : (rough && other_scatter && covers(KERNEL_WAVEFRONT_MESHFREE)) ? KERNEL_WAVEFRONT_MESHFREE
+                     : covers(KERNEL_LOCKSTEP_NOSPEC) ? KERNEL_LOCKSTEP_NOSPEC : KERNEL_LOCKSTEP;
+    }
+    if (forced_variant >= 0) {
+        const uint32_t v = (uint32_t)forced_variant;
+        const bool ok = render_ctr_variant_built(v) && VARIANT_TABLE[v].forceable && covers(v) && kinds_covered(v) &&
+                        !(VARIANT_TABLE[v].identity_meshes && !(has_mesh && all_meshes_identity));
+        if (ok) chosen = v;
+    }
+    return chosen;
+}
+
+// Root-box test right at mesh set-up (reference build's state machine): when several meshes share the list (teapot +5..12 %; a single
+// mesh loses 5-10 %).
+uint32_t choose_inline_steps(const PreparedScene& s, int knob) { return knob >= 0 ? (uint32_t)knob : (s.n_mesh_prims >= 2 ? 1u : 0u); }
+
+}  // namespace mi355rt

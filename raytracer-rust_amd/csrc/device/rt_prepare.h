@@ -1,0 +1,66 @@
+// rt_prepare.h -- the HIP-free half of libmi355rt.so's host code (rt_prepare.cpp): everything that reads caller-supplied data before a
+// device is involved.  The thread-local last error and the exception barrier of every extern "C" entry point, the row-selection rule of
+// mi355rt_options, and scene preparation: validation, the BVH re-lay, the DevPrim records and the choice of the kernel variant.
+// Includes the public header, rt_device.h and the standard library only, so that it also compiles and runs without ROCm (the CPU tests
+// through mi355rt_debug_prepare_scene, the sanitizer driver directly).  Not part of the public header.
+#pragma once
+
+#include <cstdint>
+#include <new>
+#include <stdexcept>
+#include <string>
+#include <vector>
+
+#include "../../../include/mi355rt.h"
+#include "rt_device.h"
+
+namespace mi355rt {
+
+// Sets this thread's mi355rt_last_error() text and returns `code`.
+int fail(int code, const std::string& msg);
+int fail_noexcept(int code, const char* msg) noexcept;
+std::string& last_error();       // this thread's text: what mi355rt_last_error() returns
+
+// The exception barrier of every extern "C" entry point (mi355rt.h: "nothing aborts, nothing throws across the ABI"; the caller may
+// be a Rust frame -- src/renderer.rs:67 is called from src/main.rs:57 -- into which a C++ exception must not unwind):
+// std::bad_alloc / std::length_error -> MI355RT_ERR_OOM, anything else -> MI355RT_ERR_HIP with what() in mi355rt_last_error().
+template <class F> int guard(F&& f) noexcept {
+    try { return f(); }
+    catch (const std::bad_alloc&) { return fail_noexcept(MI355RT_ERR_OOM, "host allocation failed (std::bad_alloc)"); }
+    catch (const std::length_error&) { return fail_noexcept(MI355RT_ERR_OOM, "host allocation failed (std::length_error)"); }
+    catch (const std::exception& e) {
+        try { return fail(MI355RT_ERR_HIP, std::string("unexpected C++ exception: ") + e.what()); } catch (...) { return fail_noexcept(MI355RT_ERR_HIP, "unexpected C++ exception"); }
+    }
+    catch (...) { return fail_noexcept(MI355RT_ERR_HIP, "unexpected C++ exception"); }
+}
+
+struct RowSel { std::vector<uint32_t> rows; };
+
+// The rows `o` selects (mi355rt.h, mi355rt_options), ascending = the order of the output buffers.
+int select_rows(const mi355rt_settings& st, const mi355rt_options* o, RowSel& sel);
+int check_settings(const mi355rt_settings* st);
+
+// A validated scene in the form the device holds it (rt_device.h), still in host memory, and what the choice of the kernel reads.
+struct PreparedScene {
+    // DO NOT REORDER these four, and keep mesh_roots alive with them: they are freed last to first, behind the upload, exactly as build_device_scene's
+    // locals were.  Another order of frees changes what the allocator trims and maps again on every set_scene: with prims first, teapot's set_scene
+    // took 0.57 .. 0.59 ms instead of 0.41 in two processes of three; with mesh_roots freed early, up to 0.43 (profiles/bench_scene_prepare_vs_parent.txt).
+    std::vector<DevNode> nodes; std::vector<DevTri> tris;
+    std::vector<uint32_t> mesh_roots;                                // per mesh: its root in `nodes` (DevPrim::node_begin of the primitives that use it)
+    std::vector<DevPrim> prims;
+    uint64_t n_texels = 0;                                           // of all textures together
+    uint32_t scene_mats = 0u;                                        // which material kinds a ray can meet (bit k = MI355RT_MAT_k): those the primitives refer to
+    uint32_t scene_prim_kinds = 0u;                                  // ... and which primitive kinds the list holds (bit k = MI355RT_PRIM_k)
+    uint32_t n_mesh_prims = 0;
+    bool all_meshes_identity = true, all_meshes_shallow = true;
+};
+
+// Validates `sc` and builds `out` from it; MI355RT_ERR_INVALID (and the text) for anything a kernel could not be launched on.
+int prepare_scene(const mi355rt_scene* sc, PreparedScene& out);
+// The counter-mode kernel (KERNEL_* of rt_device.h) that serves the scene.  forced_variant: the diagnostic knob "kernel", -1 = none;
+// built_mask: bit v = this library holds variant v (rt_kernels.hip, render_ctr_variant_built).
+uint32_t choose_variant(const PreparedScene& s, int forced_variant, uint32_t built_mask);
+// RenderParams.inline_steps for the scene.  knob: the diagnostic knob "inline_steps", -1 = none.
+uint32_t choose_inline_steps(const PreparedScene& s, int knob);
+
+}  // namespace mi355rt

@@ -4,6 +4,7 @@ There is no CPU fallback: `lib()` raises if the HIP library has not been built, 
 raises if no GPU is visible.  torch is NOT needed here; callers that hold torch tensors pass
 `tensor.data_ptr()` and `torch.cuda.current_stream().cuda_stream`.
 """
+import collections
 import ctypes as C
 import os
 
@@ -181,6 +182,9 @@ def _bind(so):
         L.mi355rt_debug_set_knob.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
         L.mi355rt_debug_has_variant.restype = C.c_int
         L.mi355rt_debug_has_variant.argtypes = [C.c_uint32]
+        L.mi355rt_debug_prepare_scene.restype = C.c_int
+        L.mi355rt_debug_prepare_scene.argtypes = [C.POINTER(abi.Scene), C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                                  C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p, C.POINTER(C.c_uint32)]
         if L.mi355rt_abi_version() != abi.ABI_VERSION:
             raise RuntimeError("libmi355rt.so ABI version does not match abi.py")
     return L
@@ -207,6 +211,28 @@ def set_knob(name, value, library=None):
 def clear_knobs(library=None):
     L = library or lib()
     _check(L.mi355rt_debug_set_knob(None, None, 0), "mi355rt_debug_set_knob(clear)", L)
+
+
+# The device-resident records of rt_device.h (DevPrim, DevNode, DevTri), as prepare_scene() returns them.
+PRIM_DTYPE = np.dtype([("kind", "<u4"), ("material", "<u4"), ("node_begin", "<u4"), ("run_end", "<u4"), ("d", "<f4", 52), ("mat0", "<f4", 4)])
+NODE_DTYPE = np.dtype([("bmin", "<f4", 3), ("a", "<u4"), ("bmax", "<f4", 3), ("b", "<u4")])
+TRI_DTYPE = np.dtype([("v0", "<f4", 3), ("e1", "<f4", 3), ("e2", "<f4", 3), ("n", "<f4", 3)])
+Prepared = collections.namedtuple("Prepared", "variant inline_steps prims nodes tris")
+
+
+def prepare_scene(scene, forced_variant=-1, library=None):
+    """Diagnostic (mi355rt_debug_prepare_scene): what set_scene would upload and choose for `scene` -- validation, the re-laid BVH, the
+    primitive records, the kernel variant (forced_variant: the "kernel" knob) and inline_steps.  No GPU and no context are needed.
+    Returns Prepared(variant, inline_steps, prims [PRIM_DTYPE], nodes [NODE_DTYPE], tris [TRI_DTYPE]); raises RenderError on a refusal."""
+    L = library or lib()
+    sc = getattr(scene, "c", scene)
+    variant, inline_steps, n_prims, n_nodes, n_tris = (C.c_uint32() for _ in range(5))
+    _check(L.mi355rt_debug_prepare_scene(C.byref(sc), int(forced_variant), C.byref(variant), C.byref(inline_steps), None, C.byref(n_prims),
+                                         None, C.byref(n_nodes), None, C.byref(n_tris)), "mi355rt_debug_prepare_scene", L)
+    prims, nodes, tris = np.zeros(n_prims.value, PRIM_DTYPE), np.zeros(n_nodes.value, NODE_DTYPE), np.zeros(n_tris.value, TRI_DTYPE)
+    _check(L.mi355rt_debug_prepare_scene(C.byref(sc), int(forced_variant), C.byref(variant), C.byref(inline_steps), prims.ctypes.data, C.byref(n_prims),
+                                         nodes.ctypes.data, C.byref(n_nodes), tris.ctypes.data, C.byref(n_tris)), "mi355rt_debug_prepare_scene", L)
+    return Prepared(variant.value, inline_steps.value, prims, nodes, tris)
 
 
 def render(scene, camera, settings, options=None, want_linear=True, want_stats=True, library=None):

@@ -58,7 +58,8 @@ def test_every_entry_point_sits_behind_the_barrier():
     assert len(defs) >= 17
     bare = [n for n, first in defs if "return guard([&]() -> int {" not in first and n not in ("mi355rt_debug_has_variant",)]
     assert not bare, bare
-    assert api.count("catch") >= 5
+    prepare = open(os.path.join(ROOT, "raytracer-rust_amd/csrc/device/rt_prepare.cpp")).read()      # fail_noexcept lives with the last error
+    assert api.count("catch") + prepare.count("catch") >= 5
     png = open(os.path.join(ROOT, "raytracer-rust_amd/csrc/host/png_write.cpp")).read()
     assert png.count("return mi355rt_host::guard(") == 3
     # ... and EVERY `int mi355rt_*(...)` the host library defines, whichever file it lives in (bvh_build* and scene_load_json had

@@ -262,7 +262,7 @@ def test_texture_material_scene_matches_the_oracle(native, oracle_mod, abi):
 def test_caller_built_bvh_with_fat_leaves(kernel, native, oracle_mod, abi, knobs):
     """The BVH crosses the ABI in the reference's shape, so a caller may hand over any tree -- also leaves with more triangles than
     the device's 6-bit leaf count holds.  Such a leaf keeps its box test as an inner node in front of a chain of chunk leaves with
-    infinite bounds (rt_api.cpp, flatten_meshes).  One mesh of 150 triangles under (a) the tree the host builder makes, (b) ONE leaf
+    infinite bounds (rt_prepare.cpp, flatten_meshes).  One mesh of 150 triangles under (a) the tree the host builder makes, (b) ONE leaf
     holding all 150, (c) a root over a 100-triangle and a 50-triangle leaf: each must match the oracle walking the SAME tree, bit for
     bit, in every mesh kernel.  (The trees need not agree with each other: a tight child box can reject a grazing hit its parent
     box lets through, reference behaviour that both sides reproduce.)"""

@@ -1,5 +1,6 @@
 """The C ABI must reject malformed input with an error code -- never launch a kernel on it (a faulting kernel
-can reset the GPU).  These run on the GPU box because validation lives behind context creation."""
+can reset the GPU).  These go through context creation and the one-shot render; the same refusals are checked without a GPU, through
+scene preparation alone, in tests/test_scene_prepare.py."""
 import ctypes as C
 
 import numpy as np

@@ -1,6 +1,6 @@
 """Every counter-mode kernel variant on every scene feature it accepts.
 
-mi355rt_context_set_scene picks one of the render kernels from the scene's material kinds, primitive kinds and meshes (rt_api.cpp); the
+mi355rt_context_set_scene picks one of the render kernels from the scene's material kinds, primitive kinds and meshes (rt_prepare.cpp); the
 diagnostic knob "kernel" forces another where the scene allows it.  Each instantiation compiles a different subset of the branches, and several
 carry code of their own (run-based list walks, the QC kernel's stocked first hits, the wavefront kernels' sorted SHADE passes, the untransformed
 and shallow-tree forms).  The contract is one image: every variant that accepts a scene must render it bit for bit like every other one, and
@@ -186,10 +186,11 @@ def _source(path):
 def test_ledger_table_follows_the_librarys_variant_table():
     """The table restated from the library's own description of its variants (rt_device.h VARIANT_TABLE: materials, primitive kinds, the
     untransformed-mesh condition, forceability, the fixed-AABB form, the kernel name and workgroup), the kernel pointers rt_kernels.hip launches
-    by it, and set_scene's forced-variant check that reads it (rt_api.cpp)."""
+    by it, and set_scene's forced-variant check that reads it (rt_prepare.cpp; the flag form: rt_api.cpp)."""
     import importlib
     dev = _source("raytracer-rust_amd/csrc/device/rt_device.h")
     api = _source("raytracer-rust_amd/csrc/device/rt_api.cpp")
+    prep = _source("raytracer-rust_amd/csrc/device/rt_prepare.cpp")
     hip = _source("raytracer-rust_amd/csrc/device/rt_kernels.hip")
     num = {name: int(v) for name, v in re.findall(r"\b(KERNEL_\w+) = (\d+)", dev)}
     kinds = {"MAT_METAL": METAL, "MAT_DIELECTRIC": DIELECTRIC, "MAT_LAMBERT_SOLID": LAMBERT, "MAT_EMISSIVE": EMISSIVE, "MAT_NULL": NULL,
@@ -233,9 +234,9 @@ def test_ledger_table_follows_the_librarys_variant_table():
     expect = ["nullptr" if v in RETIRED else f"{'REFS_' if lib[v] == 'refs' else ''}KFN({t['kernel']})" for v, t in sorted(table.items())]
     assert re.findall(r"(?:REFS_)?KFN\(\w+\)|nullptr", fns) == expect, fns
     # set_scene's forced-variant check and render_samples' flag form read the table
-    assert "auto covers = [&](uint32_t variant) { return (scene_mats & ~VARIANT_TABLE[variant].mats) == 0u; };" in api
-    assert "auto kinds_covered = [&](uint32_t variant) { return (scene_prim_kinds & ~VARIANT_TABLE[variant].prims) == 0u; };" in api
-    ok = re.search(r"const bool ok = ([^;]+);", api).group(1)
+    assert "auto covers = [&](uint32_t variant) { return (scene_mats & ~VARIANT_TABLE[variant].mats) == 0u; };" in prep
+    assert "auto kinds_covered = [&](uint32_t variant) { return (scene_prim_kinds & ~VARIANT_TABLE[variant].prims) == 0u; };" in prep
+    ok = re.search(r"const bool ok = ([^;]+);", prep).group(1)
     assert ok == ("render_ctr_variant_built(v) && VARIANT_TABLE[v].forceable && covers(v) && kinds_covered(v) && "
                   "!(VARIANT_TABLE[v].identity_meshes && !(has_mesh && all_meshes_identity))"), ok
     assert "if (fixed_aabb && ctx->has_mesh) variant = VARIANT_TABLE[variant].fixed_aabb;" in api

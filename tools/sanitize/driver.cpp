@@ -1,5 +1,6 @@
 // Sanitizer driver for the CPU-side producers (libmi355rt_host: scene loader, JSON, OBJ / WO3 / HDR readers, BVH build,
-// PNG / PFM writers) and for the CPU oracle's entry points.  Built with -fsanitize=address,undefined by
+// PNG / PFM writers), for the CPU oracle's entry points and for scene preparation, the HIP-free half of the device library
+// (csrc/device/rt_prepare.cpp: validation, the BVH re-lay, the primitive records).  Built with -fsanitize=address,undefined by
 // tools/sanitize_host.py; every case must return (OK or an error code) without a sanitizer report.
 //   usage: driver <repo root> <scratch dir>
 #include <cmath>
@@ -11,6 +12,7 @@
 #include <vector>
 
 #include "../../include/mi355rt.h"
+#include "../../raytracer-rust_amd/csrc/device/rt_prepare.h"
 
 extern "C" int oracle_render(const mi355rt_scene*, const mi355rt_camera*, const mi355rt_settings*, const mi355rt_options*, int, int, uint32_t*, float*, void*);
 
@@ -41,6 +43,82 @@ static int load(const std::string& path, bool want_ok, uint32_t w = 16, uint32_t
     return rc;
 }
 
+// Scene preparation on a loaded scene: the four shipped scenes must prepare; on semesterbild (one mesh, a sphere) the caller-built
+// trees and records that must be refused -- with MI355RT_ERR_INVALID, never by reading outside the arrays -- and a fat leaf that must not.
+static void prepare(const std::string& path, bool skip_unknown, bool malformed) {
+    mi355rt_load_overrides ov{}; ov.width = 16; ov.height = 12; ov.samples_per_pixel = 1; ov.max_depth = 3; ov.skip_unknown_primitives = skip_unknown;
+    mi355rt_loaded_scene* ls = nullptr;
+    if (mi355rt_scene_load_json(path.c_str(), &ov, &ls) != MI355RT_OK) { expect(false, path + " should load for prepare_scene"); return; }
+    const mi355rt_scene base = *mi355rt_loaded_scene_get(ls);
+    mi355rt::PreparedScene ps;
+    expect(mi355rt::prepare_scene(&base, ps) == MI355RT_OK, path + " should prepare: " + mi355rt::last_error());
+    expect(ps.prims.size() == base.n_primitives && ps.nodes.size() >= base.n_nodes, path + ": prepared sizes");
+    if (malformed && base.n_meshes >= 1 && base.meshes[0].triangle_count > 2 * mi355rt::NODE_MAX_LEAF) {
+        // a private copy of everything a case changes, exactly as long as the scene says: a read past an end is a sanitizer report
+        std::vector<mi355rt_primitive> prims(base.primitives, base.primitives + base.n_primitives);
+        std::vector<mi355rt_material> mats(base.materials, base.materials + base.n_materials);
+        std::vector<mi355rt_mesh> meshes(base.meshes, base.meshes + base.n_meshes);
+        std::vector<mi355rt_bvh_node> nodes(base.nodes, base.nodes + base.n_nodes);
+        std::vector<uint32_t> idx(base.tri_indices, base.tri_indices + base.n_tri_indices);
+        auto attempt = [&](const char* what, int want, const mi355rt_scene* edited = nullptr) {
+            mi355rt_scene sc = edited ? *edited : base;
+            sc.primitives = prims.data(); sc.materials = mats.data(); sc.meshes = meshes.data(); sc.nodes = nodes.data(); sc.tri_indices = idx.data();
+            mi355rt::PreparedScene out;
+            const int rc = mi355rt::prepare_scene(&sc, out);
+            expect(rc == want, std::string("prepare_scene, ") + what + ": returned " + std::to_string(rc) + " (" + mi355rt::last_error() + ")");
+            return out.nodes.size();
+        };
+        const mi355rt_mesh mesh0 = meshes[0];
+        mi355rt_bvh_node& root = nodes[mesh0.first_node];
+        const mi355rt_bvh_node root0 = root;
+        size_t leaf = mesh0.first_node; while (nodes[leaf].index_count == 0) ++leaf;                     // (a tree has leaves)
+        const mi355rt_bvh_node leaf0 = nodes[leaf];
+        expect(root0.index_count == 0, "the shipped mesh has an inner root");
+        root.left = mesh0.node_count + 7;                  attempt("child index out of range", MI355RT_ERR_INVALID); root = root0;
+        root.left = 0xFFFFFFFFu;                           attempt("child index 2^32 - 1", MI355RT_ERR_INVALID); root = root0;
+        root.left = 0;                                     attempt("cycle", MI355RT_ERR_INVALID); root = root0;
+        root.right = root.left;                            attempt("shared child", MI355RT_ERR_INVALID); root = root0;
+        nodes[leaf].first_index = mesh0.index_count;       attempt("leaf index range past the mesh", MI355RT_ERR_INVALID); nodes[leaf] = leaf0;
+        nodes[leaf].first_index = 0xFFFFFFFFu;             attempt("leaf index range wraps", MI355RT_ERR_INVALID); nodes[leaf] = leaf0;
+        nodes[leaf].index_count = 0xFFFFFFFFu;             attempt("leaf count 2^32 - 1", MI355RT_ERR_INVALID); nodes[leaf] = leaf0;
+        { const uint32_t k = mesh0.first_index + leaf0.first_index, old = idx[k]; idx[k] = 1000000u; attempt("leaf triangle id", MI355RT_ERR_INVALID); idx[k] = old; }
+        meshes[0].node_count = 0;                          attempt("mesh with node_count 0", MI355RT_ERR_INVALID); meshes[0] = mesh0;
+        meshes[0].node_count = base.n_nodes + 5;           attempt("mesh node range", MI355RT_ERR_INVALID); meshes[0] = mesh0;
+        meshes[0].first_node = 0xFFFFFFFFu;                attempt("mesh node range wraps", MI355RT_ERR_INVALID); meshes[0] = mesh0;
+        meshes[0].triangle_count = base.n_triangles + 1;   attempt("mesh triangle range", MI355RT_ERR_INVALID); meshes[0] = mesh0;
+        meshes[0].index_count = base.n_tri_indices + 1;    attempt("mesh index range", MI355RT_ERR_INVALID); meshes[0] = mesh0;
+        int spheres = 0, mesh_prims = 0;
+        for (size_t i = 0; i < prims.size(); ++i) {
+            const mi355rt_primitive p0 = prims[i];
+            if (p0.kind == MI355RT_PRIM_SPHERE) { prims[i].data[3] = 9.9e-5f; attempt("sphere radius", MI355RT_ERR_INVALID); ++spheres; }
+            if (p0.kind == MI355RT_PRIM_MESH) { prims[i].mesh = base.n_meshes; attempt("primitive mesh index", MI355RT_ERR_INVALID); ++mesh_prims; }
+            prims[i] = p0;
+        }
+        expect(spheres >= 1 && mesh_prims >= 1, path + ": the sphere-radius and mesh-index cases need a sphere and a mesh primitive");
+        { const mi355rt_primitive p0 = prims[0];
+          prims[0].material = base.n_materials; attempt("primitive material index", MI355RT_ERR_INVALID); prims[0] = p0;
+          prims[0].kind = 17;                   attempt("primitive kind", MI355RT_ERR_INVALID); prims[0] = p0; }
+        { const mi355rt_material m0 = mats[0];
+          mats[0].kind = 99;                    attempt("material kind", MI355RT_ERR_INVALID); mats[0] = m0;
+          mats[0].kind = MI355RT_MAT_TEXTURE; mats[0].texture = base.n_textures; attempt("texture index", MI355RT_ERR_INVALID); mats[0] = m0; }
+        { mi355rt_scene sky = base; sky.sky_rgb = nullptr; sky.sky_width = 4; sky.sky_height = 2; attempt("sky size without pixels", MI355RT_ERR_INVALID, &sky); }
+        { const float px[24] = {}; mi355rt_scene sky = base; sky.sky_rgb = px; sky.sky_width = 4; sky.sky_height = 0; attempt("sky pixels with one dimension", MI355RT_ERR_INVALID, &sky); }
+        attempt("the restored scene", MI355RT_OK);                                                            // (everything restored: the scene prepares again)
+        expect(mi355rt::prepare_scene(nullptr, ps) == MI355RT_ERR_INVALID, "prepare_scene(null)");
+        // a fat leaf: the whole first mesh under one leaf -> a root and a chain of ceil(n / NODE_MAX_LEAF) chunk leaves
+        mi355rt_bvh_node fat = root0; fat.left = fat.right = 0; fat.first_index = 0; fat.index_count = mesh0.triangle_count;
+        nodes.push_back(fat);
+        meshes[0].first_node = (uint32_t)nodes.size() - 1; meshes[0].node_count = 1;
+        meshes[0].first_index = (uint32_t)idx.size(); meshes[0].index_count = mesh0.triangle_count;
+        for (uint32_t t = 0; t < mesh0.triangle_count; ++t) idx.push_back(t);
+        mi355rt_scene grown = base; grown.n_nodes = (uint32_t)nodes.size(); grown.n_tri_indices = (uint32_t)idx.size();
+        size_t others = 0; for (uint32_t m = 1; m < base.n_meshes; ++m) others += meshes[m].node_count;
+        const size_t n = attempt("fat leaf", MI355RT_OK, &grown);
+        expect(n == others + 1 + (mesh0.triangle_count + mi355rt::NODE_MAX_LEAF - 1) / mi355rt::NODE_MAX_LEAF, "fat leaf: a root and its chunk chain");
+    } else if (malformed) expect(false, path + ": no mesh to deform");
+    mi355rt_scene_free(ls);
+}
+
 static std::string scene_with(const std::string& prim) {
     return std::string("{\"bsdfs\":[{\"name\":\"m\",\"type\":\"lambert\",\"albedo\":[0.5,0.5,0.5]}],\"primitives\":[") + prim +
            "],\"camera\":{\"transform\":{\"position\":[0,0,5],\"look_at\":[0,0,0],\"up\":[0,1,0]},\"fov\":40,\"resolution\":[8,8]},\"renderer\":{\"spp\":1},\"integrator\":{\"max_bounces\":2}}";
@@ -58,6 +136,12 @@ int main(int argc, char** argv) {
     load(root + "/data/scenes/tungsten/teapot/scene.json", true, 16, 12, true);
     load(root + "/data/scenes/tungsten/teapot/scene.json", false);            // infinite_sphere: an unknown primitive type is a load error
     load(root + "/no/such/file.json", false);
+
+    // ---- scene preparation (what mi355rt_context_set_scene does before it touches a device) ----
+    prepare(root + "/data/scenes/tungsten/cornell-box/scene.json", false, false);
+    prepare(root + "/data/scenes/tungsten/veach-mis/scene.json", false, false);
+    prepare(root + "/data/scenes/tungsten/teapot/scene.json", true, false);
+    prepare(root + "/data/scenes/semesterbild.json", false, true);
 
     // ---- malformed JSON ----
     const char* bad_json[] = {"", "{", "[", "{\"a\":}", "{\"a\":1,}", "nul", "{\"a\":1} x", "\"\\u12", "\"abc", "{\"a\":01}", "{\"a\":1.}", "{\"a\":.5}",

@@ -4,7 +4,8 @@ of malformed inputs.  CPU only -- GPU s
 
   python tools/sanitize_host.py [--keep]
 
-Builds tools/sanitize/driver.cpp + csrc/host/*.cpp + oracle/rt_oracle.cpp into one instrumented executable under
+Builds tools/sanitize/driver.cpp + csrc/host/*.cpp + csrc/device/rt_prepare.cpp (scene preparation: the device library's HIP-free unit, compiled
+here by plain g++ with no ROCm include path) + oracle/rt_oracle.cpp into one instrumented executable under
 tools/sanitize/_build/, runs it in a scratch directory and fails on any sanitizer report or unexpected result."""
 import glob, os, shutil, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -16,9 +17,11 @@ FLAGS = ["-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer", "-ffp-contract=of
 def build():
     os.makedirs(OUT, exist_ok=True)
     exe = os.path.join(OUT, "sanitize_driver")
-    srcs = [os.path.join(ROOT, "tools", "sanitize", "driver.cpp"), os.path.join(ROOT, "oracle", "rt_oracle.cpp")] + \
+    device = os.path.join(ROOT, "raytracer-rust_amd", "csrc", "device")
+    srcs = [os.path.join(ROOT, "tools", "sanitize", "driver.cpp"), os.path.join(ROOT, "oracle", "rt_oracle.cpp"), os.path.join(device, "rt_prepare.cpp")] + \
         sorted(glob.glob(os.path.join(ROOT, "raytracer-rust_amd", "csrc", "host", "*.cpp")))
-    deps = srcs + glob.glob(os.path.join(ROOT, "raytracer-rust_amd", "csrc", "host", "*.hpp")) + [os.path.join(ROOT, "include", "mi355rt.h")]
+    deps = srcs + glob.glob(os.path.join(ROOT, "raytracer-rust_amd", "csrc", "host", "*.hpp")) + [os.path.join(ROOT, "include", "mi355rt.h")] + \
+        [os.path.join(device, "rt_prepare.h"), os.path.join(device, "rt_device.h")]
     if not os.path.exists(exe) or any(os.path.getmtime(d) > os.path.getmtime(exe) for d in deps):
         subprocess.check_call(["g++", *FLAGS, "-o", exe, *srcs, "-lz"])
     return exe
