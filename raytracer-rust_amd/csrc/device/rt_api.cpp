@@ -89,6 +89,12 @@ struct mi355rt_context {
     DevBuf<unsigned long long> wave_times; uint32_t wave_times_n = 0;   // diagnostics (MI355RT_WAVE_TIMES=1)
     std::vector<uint32_t> rows_host;     // the selected rows (absolute y, ascending = the order of the output buffer)
     std::vector<uint32_t> tables_host;   // source of the async upload of the three row tables (row_tables()); must outlive the copy
+    // Camera masks (rt_prepare.h build_camera_masks; k_render_ctr_simple_qc's camera pass).  cam_mask_abs: the table of the scene, the camera and the
+    // settings of set_scene, one word per pixel of the image (empty: none -- another kernel, more than 32 primitives, or the knob); cam_mask_host: its rows
+    // in the processing order of rows_host, rebuilt with the row tables and uploaded behind them into `rows` (same lifetime as tables_host); empty: the
+    // kernel gets no table.
+    std::vector<uint32_t> cam_mask_abs, cam_mask_host; uint32_t cam_mask_w = 0, cam_mask_h = 0;
+    int knob_cam_cull = -1;              // diagnostic knob "cam_cull": -1 / 1 on, 0 off (no table: the camera pass tests every primitive)
     bool rows_valid = false;             // ctx->rows already holds the tables of rows_host (same selection and grouping as the last call)
     // Processing order (an experiment of round 4, opt-in).  The persistent kernels hand out a band's samples front to back, and a
     // launch ends with the paths of the rows handed out LAST.  The idea: process the rows in order of DECREASING expected cost -- cheap rows
@@ -168,7 +174,7 @@ uint32_t built_variants() {
 }
 
 // The upload of a prepared scene (rt_prepare.h: validated and laid out without HIP) and what the context keeps of it.
-int build_device_scene(mi355rt_context* ctx, const mi355rt_scene* sc) {
+int build_device_scene(mi355rt_context* ctx, const mi355rt_scene* sc, const mi355rt_camera* camera, const mi355rt_settings* st) {
     PreparedScene s;
     int rc = prepare_scene(sc, s); if (rc) return rc;
     const bool has_sky = sc->sky_rgb != nullptr;
@@ -207,6 +213,13 @@ int build_device_scene(mi355rt_context* ctx, const mi355rt_scene* sc) {
     ctx->has_mesh = s.n_mesh_prims != 0;
     ctx->variant = choose_variant(s, ctx->forced_variant, built_variants());
     ctx->inline_steps = choose_inline_steps(s, ctx->knob_inline_steps);
+    ctx->cam_mask_abs.clear(); ctx->cam_mask_host.clear();                    // (clear keeps the allocations: the next table is written in place)
+    if (ctx->variant == KERNEL_LOCKSTEP_SIMPLE_QC && ctx->knob_cam_cull != 0) {
+        static_assert(sizeof(DevCamera) == sizeof(mi355rt_camera), "camera layout is shared with the ABI");
+        DevCamera cam; std::memcpy(&cam, camera, sizeof cam);
+        build_camera_masks(s, cam, st->width, st->height, ctx->cam_mask_abs);
+        ctx->cam_mask_w = st->width; ctx->cam_mask_h = st->height;
+    }
     return MI355RT_OK;
 }
 
@@ -223,6 +236,7 @@ int apply_knob(mi355rt_context* ctx, const std::string& name, int v) {
     else if (name == "spin_idle") { if (v < 1) return fail(MI355RT_ERR_INVALID, "knob spin_idle"); ctx->spin_limit_idle = (uint32_t)v; }
     else if (name == "spin_entry") { if (v < 1) return fail(MI355RT_ERR_INVALID, "knob spin_entry"); ctx->spin_limit_entry = (uint32_t)v; }
     else if (name == "wave_times") ctx->want_wave_times = v != 0;
+    else if (name == "cam_cull") { if (v < -1 || v > 1) return fail(MI355RT_ERR_INVALID, "knob cam_cull"); ctx->knob_cam_cull = v; }
     else if (name == "row_order") { if (v < -1 || v > 1) return fail(MI355RT_ERR_INVALID, "knob row_order"); ctx->knob_row_order = v; }
     else return fail(MI355RT_ERR_INVALID, "unknown knob " + name);
     return MI355RT_OK;
@@ -234,8 +248,8 @@ extern "C" {
 
 // Diagnostic hook (not part of the public header).  ctx != NULL: set one knob of that context (before set_scene).  ctx == NULL: a
 // process-wide default applied to every context created afterwards -- also those the one-shot calls create; name == NULL clears
-// all defaults.  Knobs: kernel (KERNEL_* of rt_device.h, -1 = automatic), guided_mult, spin_idle, spin_entry, wave_times, and for the
-// reference build's state machine inline_steps, trav_min.
+// all defaults.  Knobs: kernel (KERNEL_* of rt_device.h, -1 = automatic), guided_mult, spin_idle, spin_entry, wave_times, row_order,
+// cam_cull (0: k_render_ctr_simple_qc gets no camera masks), and for the reference build's state machine inline_steps, trav_min.
 int mi355rt_debug_set_knob(mi355rt_context* ctx, const char* name, int value) {
     return guard([&]() -> int {
     if (ctx) return name ? apply_knob(ctx, name, value) : fail(MI355RT_ERR_INVALID, "knob name is null");
@@ -320,7 +334,7 @@ int mi355rt_context_set_scene(mi355rt_context* ctx, const mi355rt_scene* scene, 
     HIP_TRY(hipSetDevice(ctx->device));
     ctx->have_scene = false; ctx->rows_valid = false;
     ctx->query_rows_release();                                       // (the tables belong to the old settings)
-    rc = build_device_scene(ctx, scene); if (rc) return rc;
+    rc = build_device_scene(ctx, scene, camera, settings); if (rc) return rc;
     static_assert(sizeof(DevCamera) == sizeof(mi355rt_camera), "camera layout is shared with the ABI");
     std::memcpy(&ctx->cam, camera, sizeof(DevCamera));
     ctx->settings = *settings;
@@ -422,6 +436,10 @@ static int render_samples(mi355rt_context* ctx, const mi355rt_options* opt, uint
         ctx->rows_host.swap(sel.rows);
         static const std::vector<float> no_cost;
         row_tables(ctx->rows_host, groups ? ctx->row_cost : no_cost, groups, ctx->tables_host);
+        // the camera masks of these rows, in processing order (set_scene's probes render with other settings: the table is not theirs)
+        ctx->cam_mask_host.clear();
+        if (!ctx->cam_mask_abs.empty() && ctx->cam_mask_w == st.width && ctx->cam_mask_h == st.height)
+            gather_camera_masks(ctx->cam_mask_abs, st.width, ctx->tables_host.data() + ctx->rows_host.size(), ctx->rows_host.size(), ctx->cam_mask_host);
         ctx->order_groups = groups;
         ctx->rows_valid = false;
     }
@@ -440,8 +458,10 @@ static int render_samples(mi355rt_context* ctx, const mi355rt_options* opt, uint
     if (n_rows == 0) return MI355RT_OK;
 
     if (!same_rows) {
-        if ((rc = ctx->rows.ensure(3 * (size_t)n_rows))) return rc;
+        if ((rc = ctx->rows.ensure(3 * (size_t)n_rows + ctx->cam_mask_host.size()))) return rc;
         HIP_TRY(hipMemcpyAsync(ctx->rows.p, ctx->tables_host.data(), 3 * (size_t)n_rows * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+        if (!ctx->cam_mask_host.empty())
+            HIP_TRY(hipMemcpyAsync(ctx->rows.p + 3 * (size_t)n_rows, ctx->cam_mask_host.data(), ctx->cam_mask_host.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
         ctx->rows_valid = true;
     }
     const uint32_t* d_rows_natural = ctx->rows.p;
@@ -512,6 +532,8 @@ static int render_samples(mi355rt_context* ctx, const mi355rt_options* opt, uint
         p.trav_min = ctx->trav_min; p.inline_steps = ctx->inline_steps;
         p.lds_nodes = (uint32_t)std::min<size_t>(ctx->n_nodes, LDS_NODE_CAP);    // (the wavefront kernel clamps to its own WF_LDS_NODES)
         p.err = ctx->errword.p; p.spin_limit_idle = ctx->spin_limit_idle; p.spin_limit_entry = ctx->spin_limit_entry;
+        // the masks lie behind the three row tables; p.rows is the second of them (n_rows * (1 + width) < 2^31 + 2^24 words)
+        p.cam_mask_off = (variant == KERNEL_LOCKSTEP_SIMPLE_QC && ctx->cam_mask_host.size() == (size_t)n_rows * st.width) ? 2u * n_rows : 0u;
         ResolveParams r{};
         r.radiance = ctx->radiance.p; r.out_packed = (uint32_t*)d_out_packed; r.out_linear = (float*)d_out_linear;
         r.spp = (uint32_t)spp; r.inv_spp = 1.0f / (float)s1;                             // renderer.rs:85
@@ -729,6 +751,34 @@ int mi355rt_debug_prepare_scene(const mi355rt_scene* scene, int forced_variant, 
     *n_prims = (uint32_t)s.prims.size(); *n_nodes = (uint32_t)s.nodes.size(); *n_tris = (uint32_t)s.tris.size();
     *out_variant = choose_variant(s, forced_variant, built_variants());
     *out_inline_steps = choose_inline_steps(s, -1);
+    return MI355RT_OK;
+    });
+}
+
+// Diagnostic hook (not part of the public header): the camera masks set_scene would build for `scene` under `camera` and `settings`, without a device.
+// options null: the absolute table, one word per pixel of the image; otherwise the table a render with those options reads, the selected rows in
+// processing order (image order: the processing-order experiment needs a device).  Two calls: with `out` null it only counts.  *n == 0: no table
+// (more than 32 primitives, or a scene that another kernel than forced_variant / the automatic choice's k_render_ctr_simple_qc serves).
+int mi355rt_debug_camera_masks(const mi355rt_scene* scene, const mi355rt_camera* camera, const mi355rt_settings* settings, const mi355rt_options* options,
+                               int forced_variant, uint32_t* out, uint64_t capacity, uint64_t* n) {
+    return guard([&]() -> int {
+    if (!camera || !n) return fail(MI355RT_ERR_INVALID, "debug_camera_masks: null");
+    if (forced_variant < -1 || forced_variant >= (int)KERNEL_VARIANTS) return fail(MI355RT_ERR_INVALID, "knob kernel");
+    int rc = check_settings(settings); if (rc) return rc;
+    PreparedScene s;
+    rc = prepare_scene(scene, s); if (rc) return rc;
+    std::vector<uint32_t> table, gathered;
+    if (choose_variant(s, forced_variant, built_variants()) == KERNEL_LOCKSTEP_SIMPLE_QC) {
+        DevCamera cam; std::memcpy(&cam, camera, sizeof cam);
+        build_camera_masks(s, cam, settings->width, settings->height, table);
+    }
+    if (options && !table.empty()) {
+        RowSel sel; rc = select_rows(*settings, options, sel); if (rc) return rc;
+        gather_camera_masks(table, settings->width, sel.rows.data(), sel.rows.size(), gathered);
+        table.swap(gathered);
+    }
+    *n = table.size();
+    if (out) { if (capacity < table.size()) return fail(MI355RT_ERR_INVALID, "debug_camera_masks: capacity"); if (!table.empty()) std::memcpy(out, table.data(), table.size() * sizeof(uint32_t)); }
     return MI355RT_OK;
     });
 }

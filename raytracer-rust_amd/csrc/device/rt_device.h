@@ -107,7 +107,13 @@ struct RenderParams {
     uint32_t lds_nodes;          // state-machine kernel (reference build): nodes [0, lds_nodes) are read from the workgroup's LDS copy (<= LDS_NODE_CAP)
     uint32_t spin_limit_idle;    // wavefront kernel: polls without progress before a wave gives up (SPIN_LIMIT_IDLE; a diagnostic hook lowers it)
     uint32_t spin_limit_entry;   // wavefront kernel: polls of one ring entry before a lane gives up (SPIN_LIMIT_ENTRY)
+    // (Last, in what were the struct's four bytes of tail padding: the size of the kernel argument and with it the offsets of the implicit arguments behind
+    //  it, which the wavefront kernels' scalar loads carry, stay what they were.  A pointer would have moved them.)
+    uint32_t cam_mask_off;       // k_render_ctr_simple_qc: the camera masks are the words rows[cam_mask_off + pixel], pixel = band_pixel0 + sample / spp, i.e. one word
+                                 // per pixel IN PROCESSING ORDER behind the row tables in the same allocation; bit i = a camera ray of the pixel may hit primitive i
+                                 // (rt_prepare.cpp build_camera_masks).  0 = no table: every primitive is tested
 };
+static_assert(sizeof(RenderParams) == 280, "RenderParams: the kernels' implicit arguments follow it (see cam_mask_off)");
 // The bounded waits a kernel can give up (RenderParams.err): an idle wave of the wavefront kernel that saw no progress in its workgroup; a lane
 // whose ring entry was never written (pop) or never emptied (push); a wave that left because another wave of its workgroup had given up.
 enum : uint32_t { WAIT_WF_IDLE = 1u, WAIT_WF_RING = 2u, WAIT_WF_FOLLOWED = 4u };

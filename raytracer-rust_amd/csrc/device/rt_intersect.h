@@ -407,8 +407,12 @@ DI void finish_hit(const DevPrim* __restrict__ prims, const DevTri* __restrict__
 DI uint32_t prim_material_kind(const RenderParams& P, uint32_t idx) { return __float_as_uint(P.prims[idx].mat0[0]); }   // one read, not two dependent ones
 
 // hittable.rs:45-58 -- HittableList::hit with t_min = EPSILON, t_max = INFINITY (renderer.rs:24)
+// pmask (wave-uniform): bit i clear = no ray of this wave can hit primitive i, so its test is skipped -- a scalar branch; the candidate is what the
+// test would have left.  All ones (the default, which folds away) everywhere but in the camera pass of k_render_ctr_simple_qc, whose rays leave one
+// origin through one or two pixels and take the pixels' words of RenderParams.cam_mask (rt_prepare.cpp build_camera_masks).  Lists longer than 32 get
+// no table (the host), so a shift by i >= 32 is never executed.
 template <bool HAS_MESH, uint32_t KINDS = PRIMS_ALL, class C>
-DI void walk_list(cprim_t prims, uint32_t n_prims, const DevNode* __restrict__ nodes, const DevTri* __restrict__ tris, f3 ro, f3 rd, C& c) {
+DI void walk_list(cprim_t prims, uint32_t n_prims, const DevNode* __restrict__ nodes, const DevTri* __restrict__ tris, f3 ro, f3 rd, C& c, uint32_t pmask = ~0u) {
 #define MI_KIND(k) (((KINDS >> (k)) & 1u) != 0u)
     // Same order as the list, but the dispatch on the kind (wave-uniform: a scalar branch) is taken once per RUN of equal kinds
     // (DevPrim.run_end, host-computed) and each kind has its own tight loop: the structurised switch inside one loop carried the
@@ -419,7 +423,7 @@ DI void walk_list(cprim_t prims, uint32_t n_prims, const DevNode* __restrict__ n
     // kinds: cornell +2.8 %, profiles/r05/ab_scalar_diet.txt.)
     uint32_t i = 0;
     while (i < n_prims) {
-#define MI_RUN(KIND, CALL) if (i < n_prims && prims[i].kind == (KIND)) { const uint32_t end = min(prims[i].run_end, n_prims); do { CALL; } while (++i < end); }
+#define MI_RUN(KIND, CALL) if (i < n_prims && prims[i].kind == (KIND)) { const uint32_t end = min(prims[i].run_end, n_prims); do { if ((pmask >> i) & 1u) { CALL; } } while (++i < end); }
         if (MI_KIND(MI355RT_PRIM_QUAD)) { MI_RUN(MI355RT_PRIM_QUAD,   hit_quad<!HAS_MESH>(prims + i, i, ro, rd, EPS, c)) }
         if (MI_KIND(MI355RT_PRIM_CUBE)) { MI_RUN(MI355RT_PRIM_CUBE,   hit_cube<!HAS_MESH>(prims + i, i, ro, rd, EPS, c)) }
         if (MI_KIND(MI355RT_PRIM_SPHERE)) { MI_RUN(MI355RT_PRIM_SPHERE, hit_sphere(prims + i, i, ro, rd, EPS, c)) }
@@ -436,9 +440,9 @@ DI void walk_list(cprim_t prims, uint32_t n_prims, const DevNode* __restrict__ n
 // spills, -2.6 % at 80; see MI355RT_OCC_LOCKSTEP).
 template <bool HAS_MESH, bool CARRY_PO = false, uint32_t KINDS = PRIMS_ALL>
 DI bool hit_scene(cprim_t prims, uint32_t n_prims, const DevNode* __restrict__ nodes, const DevTri* __restrict__ tris,
-                  f3 ro, f3 rd, Hit& best) {
+                  f3 ro, f3 rd, Hit& best, uint32_t pmask = ~0u) {
     typename std::conditional<CARRY_PO && !HAS_MESH, CandP, Cand>::type c; cand_reset(c);
-    walk_list<HAS_MESH, KINDS>(prims, n_prims, nodes, tris, ro, rd, c);
+    walk_list<HAS_MESH, KINDS>(prims, n_prims, nodes, tris, ro, rd, c, pmask);
     if (c.idx == CAND_NONE) return false;
     finish_hit<HAS_MESH, !HAS_MESH, !HAS_MESH, KINDS>((const DevPrim*)prims, tris, c, ro, rd, best);          // (the lockstep kernels' entry: q0 rides along when there is no mesh)
     return true;

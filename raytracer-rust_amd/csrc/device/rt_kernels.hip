@@ -18,6 +18,7 @@
 //                  Round 5: a wave keeps the camera rays of its next 64 samples IN STOCK (RayStock, LDS) and the mesh-free kernels
 //                  are instantiated per material set AND per primitive-kind set (k_render_ctr_simple_qc).  k_render_ctr_simple_qc
 //                  stocks the camera rays' first hits instead (HitStock), walked in refill passes of the loop.
+//                  Those passes test only the primitives their one or two pixels can see (RenderParams.cam_mask_off: per-pixel masks built by set_scene).
 //                  Output: three floats of radiance per path into the HBM workspace.
 //   k_resolve      per pixel, sums its spp radiance values IN SAMPLE ORDER (renderer.rs:100), scales by
 //                  1/spp (:103), sqrt-gamma, clamp, pack 0x00RRGGBB (:112-120, color.rs:87-93).
@@ -570,15 +571,23 @@ DI void render_ctr_lockstep(const RenderParams& P) {
         //  profiles/r05/ab_scalar_diet.txt r05_q13.)
         __builtin_amdgcn_s_setprio(1);
         uint32_t n_cam = 0u;                               // PREHIT: camera rays walked in this iteration (a refill pass; wave-uniform)
+        uint32_t pmask = ~0u;                              // PREHIT: the primitives this walk tests (walk_list); all of them in a bounce iteration
         if constexpr (PREHIT) {
             n_cam = wc.template refill_size<MI355RT_PREHIT_LOW>(P, lane);
             if (n_cam != 0u) {                             // park the paths' rays; lane i takes the camera ray of sample next + i
+                // The pass's samples are consecutive: at spp >= 64 they belong to one pixel or to two neighbours in processing order, and the walk tests
+                // only what those pixels' camera rays can hit (two scalar loads; the table is indexed like the band's pixels).  More pixels: everything.
+                if (P.cam_mask_off != 0u) {
+                    const uint32_t pix0 = fastdiv(wc.next, P.spp_mul, P.spp_shift), pix1 = fastdiv(wc.next + n_cam - 1u, P.spp_mul, P.spp_shift);
+                    const __attribute__((address_space(4))) uint32_t* cm = (const __attribute__((address_space(4))) uint32_t*)(P.rows) + P.cam_mask_off + P.band_pixel0;
+                    if (pix1 - pix0 <= 1u) pmask = cm[pix0] | cm[pix1];
+                }
                 wave_lds_handoff();                        // (camera() writes into slots whose entries other lanes were dealt)
                 stock.park_a[lane] = make_float4(ps.ro.x, ps.ro.y, ps.ro.z, ps.rd.x); stock.park_b[lane] = make_float2(ps.rd.y, ps.rd.z);
                 if (lane < n_cam) stock.camera(P, wc.next + lane, (wc.ring_head + wc.ring_count + lane) & 63u, ps.ro, ps.rd);
             }
         }
-        if (n_cam != 0u ? lane < n_cam : live) hit = hit_scene<HAS_MESH, true, KINDS>(prims, P.n_prims, P.nodes, P.tris, ps.ro, ps.rd, h);     // renderer.rs:24
+        if (n_cam != 0u ? lane < n_cam : live) hit = hit_scene<HAS_MESH, true, KINDS>(prims, P.n_prims, P.nodes, P.tris, ps.ro, ps.rd, h, pmask);     // renderer.rs:24
         prof.mark(1);
         if constexpr (PREHIT) {
             if (n_cam != 0u) {                             // finish or stock the camera paths, take the parked rays back, and walk them next

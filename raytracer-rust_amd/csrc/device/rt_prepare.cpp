@@ -344,3 +344,127 @@ uint32_t choose_variant(const PreparedScene& s, int forced_variant, uint32_t bui
 uint32_t choose_inline_steps(const PreparedScene& s, int knob) { return knob >= 0 ? (uint32_t)knob : (s.n_mesh_prims >= 2 ? 1u : 0u); }
 
 }  // namespace mi355rt
+
+// ---- camera masks ----------------------------------------------------------------------------------------------------------------
+namespace {
+
+constexpr double MASK_INFLATE = 1e-3;       // in the primitive's own parameter space: ten times the tests' EPS (rt_math.h) of 1e-4
+constexpr double MASK_DILATE = 1.0;         // pixels, on every side of the footprint
+constexpr double MASK_TAN_MAX = 1e6;        // a corner further off the view axis than this many times its depth counts as reaching the camera plane
+
+struct V3 { double x, y, z; };
+V3 v3(const float* p) { return V3{(double)p[0], (double)p[1], (double)p[2]}; }
+double dot(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
+V3 cross(V3 a, V3 b) { return V3{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
+double maxabs(V3 a) { return std::max(std::fabs(a.x), std::max(std::fabs(a.y), std::fabs(a.z))); }
+
+// Rows r0, r1, r2 and a right-hand side: the x with r_k . x = b_k, by Cramer's rule.  false: not finite, or a determinant that is nothing but
+// rounding of its own terms (|det| <= 1e-12 |r0| |r1| |r2|).
+bool solve_rows(V3 r0, V3 r1, V3 r2, V3 b, V3& x) {
+    const V3 c12 = cross(r1, r2), c20 = cross(r2, r0), c01 = cross(r0, r1);
+    const double det = dot(r0, c12), scale = maxabs(r0) * maxabs(r1) * maxabs(r2);
+    if (!std::isfinite(det) || !std::isfinite(scale) || !(std::fabs(det) > 1e-12 * scale)) return false;
+    x = V3{(b.x * c12.x + b.y * c20.x + b.z * c01.x) / det, (b.x * c12.y + b.y * c20.y + b.z * c01.y) / det, (b.x * c12.z + b.y * c20.z + b.z * c01.z) / det};
+    return std::isfinite(x.x) && std::isfinite(x.y) && std::isfinite(x.z);
+}
+
+// The world-space corners of the region in which the kernel's test can accept a hit, inflated by MASK_INFLATE.  false: in doubt.
+// Quad (rt_intersect.h hit_quad): the hit point P lies in the plane n . P = d, and l0 = ((P - base) . e0) * inv0 and l1 = ((P - base) . e1) * inv1 lie in
+// [-EPS, 1 + EPS].  The corners are the P with l0, l1 in {-delta, 1 + delta} -- for the records the loader makes (e0 orthogonal to e1, inv = 1 / |e|^2, the
+// plane through base) these are base + s e0 + t e1; solving the three equations of the record itself also covers a record that is not of that form.
+int quad_corners(const mi355rt::DevPrim& p, V3* out) {
+    const V3 n = v3(p.d), base = v3(p.d + 4), e0 = v3(p.d + 7), e1 = v3(p.d + 10);
+    const double d = p.d[3], inv0 = p.d[13], inv1 = p.d[14];
+    const V3 r1 = V3{e0.x * inv0, e0.y * inv0, e0.z * inv0}, r2 = V3{e1.x * inv1, e1.y * inv1, e1.z * inv1};
+    int k = 0;
+    for (double a : {-MASK_INFLATE, 1.0 + MASK_INFLATE}) for (double b : {-MASK_INFLATE, 1.0 + MASK_INFLATE})
+        if (!solve_rows(n, r1, r2, V3{d, a + dot(base, r1), b + dot(base, r2)}, out[k++])) return 0;
+    return k;
+}
+// Cube (hit_cube): the object-space ray w2o * (ray) meets the box [-0.5, 0.5]^3, so the world ray meets the image of that box under the inverse of the
+// record's w2o (the record's own o2w only rejects more: it enters the second range check).  The corners: M x + c = (+-(0.5 + delta))^3.
+int cube_corners(const mi355rt::DevPrim& p, V3* out) {
+    const float* m = p.d;                                    // d[3 * column + row], column 3 = the translation
+    const V3 r0 = V3{m[0], m[3], m[6]}, r1 = V3{m[1], m[4], m[7]}, r2 = V3{m[2], m[5], m[8]}, c = v3(m + 9);
+    const double h = 0.5 + MASK_INFLATE;
+    int k = 0;
+    for (double x : {-h, h}) for (double y : {-h, h}) for (double z : {-h, h})
+        if (!solve_rows(r0, r1, r2, V3{x - c.x, y - c.y, z - c.z}, out[k++])) return 0;
+    return k;
+}
+
+}  // namespace
+
+namespace mi355rt {
+
+void build_camera_masks(const PreparedScene& s, const DevCamera& cam, uint32_t width, uint32_t height, std::vector<uint32_t>& out) {
+    out.clear();
+    const size_t n_prims = s.prims.size();
+    if (n_prims == 0 || n_prims > 32 || width == 0 || height == 0) return;
+    out.assign((size_t)width * height, 0u);
+    const uint32_t all = n_prims == 32 ? 0xFFFFFFFFu : (1u << n_prims) - 1u;
+    uint32_t keep = 0u;                                      // the primitives in doubt: their bits go into every pixel at the end
+    const V3 O = v3(cam.position), F = v3(cam.forward), R = v3(cam.right), U = v3(cam.true_up);
+    const double hw = cam.half_width, hh = cam.half_height, W = width, H = height;
+    // X - O = lambda (F + a R + b U): the rows of the system are the components, its columns F, R, U (no basis is assumed orthonormal).
+    const V3 row0 = V3{F.x, R.x, U.x}, row1 = V3{F.y, R.y, U.y}, row2 = V3{F.z, R.z, U.z};
+    const bool cam_ok = std::isfinite(hw) && std::isfinite(hh) && std::fabs(hw) > 0.0 && std::fabs(hh) > 0.0;
+    for (size_t i = 0; i < n_prims; ++i) {
+        const DevPrim& p = s.prims[i];
+        const uint32_t bit = 1u << i;
+        V3 corner[8];
+        const int n = !cam_ok ? 0 : p.kind == MI355RT_PRIM_QUAD ? quad_corners(p, corner) : p.kind == MI355RT_PRIM_CUBE ? cube_corners(p, corner) : 0;
+        if (n == 0) { keep |= bit; continue; }
+        double px[8], py[8];
+        int behind = 0; bool doubt = false;
+        for (int k = 0; k < n; ++k) {
+            V3 q;                                            // (lambda, lambda a, lambda b)
+            if (!solve_rows(row0, row1, row2, V3{corner[k].x - O.x, corner[k].y - O.y, corner[k].z - O.z}, q)) { doubt = true; break; }
+            const double off = std::fabs(q.y) + std::fabs(q.z);
+            if (q.x < 0.0 && -q.x * MASK_TAN_MAX > off) { ++behind; continue; }            // safely behind the camera plane
+            if (!(q.x > 0.0 && q.x * MASK_TAN_MAX > off)) { doubt = true; break; }         // in or near the camera plane
+            // camera_raw (rt_materials.h): a = (2 u - 1) half_width, b = (1 - 2 v) half_height; a pixel is [x, x + 1] x [y, y + 1] of (u W, v H)
+            px[k] = (q.y / q.x / hw + 1.0) * 0.5 * W; py[k] = (1.0 - q.z / q.x / hh) * 0.5 * H;
+            if (!std::isfinite(px[k]) || !std::isfinite(py[k])) { doubt = true; break; }
+        }
+        if (!doubt && behind == n) continue;                 // every corner, so the whole convex region, lies behind the camera: no ray reaches it
+        if (doubt || behind != 0) { keep |= bit; continue; } // it reaches the camera plane
+        // The footprint is the convex hull of the projected corners, and a convex set's extent in x within a band of rows is reached on a segment between
+        // two of its corners: per pixel row, the extent of all corner pairs' segments clipped to the dilated row, widened by the dilation.
+        double ymin = py[0], ymax = py[0];
+        for (int k = 1; k < n; ++k) { ymin = std::min(ymin, py[k]); ymax = std::max(ymax, py[k]); }
+        const double ylo = std::floor(ymin - MASK_DILATE), yhi = std::floor(ymax + MASK_DILATE);
+        if (yhi < 0.0 || ylo > H - 1.0) continue;
+        const uint32_t y0 = (uint32_t)std::max(ylo, 0.0), y1 = (uint32_t)std::min(yhi, H - 1.0);
+        for (uint32_t y = y0; y <= y1; ++y) {
+            const double lo = (double)y - MASK_DILATE, hi = (double)y + 1.0 + MASK_DILATE;
+            double xmin = std::numeric_limits<double>::infinity(), xmax = -xmin;
+            for (int a = 0; a < n; ++a) for (int b = a; b < n; ++b) {
+                double xa = px[a], ya = py[a], xb = px[b], yb = py[b];
+                if (ya > yb) { std::swap(xa, xb); std::swap(ya, yb); }
+                if (yb < lo || ya > hi) continue;
+                const double dy = yb - ya;
+                double x_lo = xa, x_hi = xb;                 // the segment's ends inside [lo, hi]
+                if (dy > 0.0) {
+                    if (ya < lo) x_lo = xa + (xb - xa) * ((lo - ya) / dy);
+                    if (yb > hi) x_hi = xa + (xb - xa) * ((hi - ya) / dy);
+                }
+                xmin = std::min(xmin, std::min(x_lo, x_hi)); xmax = std::max(xmax, std::max(x_lo, x_hi));
+            }
+            if (!(xmin <= xmax)) continue;
+            const double fx0 = std::floor(xmin - MASK_DILATE), fx1 = std::floor(xmax + MASK_DILATE);
+            if (fx1 < 0.0 || fx0 > W - 1.0) continue;
+            const uint32_t x0 = (uint32_t)std::max(fx0, 0.0), x1 = (uint32_t)std::min(fx1, W - 1.0);
+            uint32_t* row = out.data() + (size_t)y * width;
+            for (uint32_t x = x0; x <= x1; ++x) row[x] |= bit;
+        }
+    }
+    if (keep != 0u) for (uint32_t& w : out) w |= keep & all;
+}
+
+void gather_camera_masks(const std::vector<uint32_t>& absolute, uint32_t width, const uint32_t* rows_processing, size_t n_rows, std::vector<uint32_t>& out) {
+    out.resize(n_rows * (size_t)width);
+    for (size_t j = 0; j < n_rows; ++j) std::memcpy(out.data() + j * width, absolute.data() + (size_t)rows_processing[j] * width, (size_t)width * sizeof(uint32_t));
+}
+
+}  // namespace mi355rt

@@ -63,4 +63,13 @@ uint32_t choose_variant(const PreparedScene& s, int forced_variant, uint32_t bui
 // RenderParams.inline_steps for the scene.  knob: the diagnostic knob "inline_steps", -1 = none.
 uint32_t choose_inline_steps(const PreparedScene& s, int knob);
 
+// Camera masks (k_render_ctr_simple_qc's camera pass): one word per pixel in absolute order y * width + x, bit i set = a camera ray of
+// that pixel may hit primitive i.  A clear bit is a proof: the screen footprint of the region in which the kernel's test of that primitive can accept
+// a hit, inflated and dilated by far more than any rounding, does not reach the pixel's jitter square.  Whatever is in doubt -- a primitive that reaches the camera plane,
+// a record that is not finite, a degenerate matrix, a kind other than quad or cube -- keeps its bit in every pixel.  `out` is resized and filled in place
+// (a context calls this on every set_scene: its allocation is kept).  Lists of more than 32 primitives get no table: `out` comes back empty.
+void build_camera_masks(const PreparedScene& s, const DevCamera& cam, uint32_t width, uint32_t height, std::vector<uint32_t>& out);
+// The table the kernel reads: the rows `rows_processing` (absolute y, in the order they are processed) of the absolute table, back to back.
+void gather_camera_masks(const std::vector<uint32_t>& absolute, uint32_t width, const uint32_t* rows_processing, size_t n_rows, std::vector<uint32_t>& out);
+
 }  // namespace mi355rt

@@ -185,6 +185,9 @@ def _bind(so):
         L.mi355rt_debug_prepare_scene.restype = C.c_int
         L.mi355rt_debug_prepare_scene.argtypes = [C.POINTER(abi.Scene), C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
                                                   C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p, C.POINTER(C.c_uint32)]
+        L.mi355rt_debug_camera_masks.restype = C.c_int
+        L.mi355rt_debug_camera_masks.argtypes = [C.POINTER(abi.Scene), C.POINTER(abi.Camera), C.POINTER(abi.Settings), C.POINTER(abi.Options), C.c_int,
+                                                 C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
         if L.mi355rt_abi_version() != abi.ABI_VERSION:
             raise RuntimeError("libmi355rt.so ABI version does not match abi.py")
     return L
@@ -203,7 +206,7 @@ def _check(rc, what, library=None):
 
 def set_knob(name, value, library=None):
     """Diagnostic: process-wide default knob for every context created afterwards (also inside the one-shot calls).
-    Knobs: kernel, guided_mult, spin_idle, spin_entry, wave_times, row_order, inline_steps, trav_min (rt_api.cpp)."""
+    Knobs: kernel, guided_mult, spin_idle, spin_entry, wave_times, row_order, cam_cull, inline_steps, trav_min (rt_api.cpp)."""
     L = library or lib()
     _check(L.mi355rt_debug_set_knob(None, name.encode(), int(value)), f"mi355rt_debug_set_knob({name})", L)
 
@@ -233,6 +236,25 @@ def prepare_scene(scene, forced_variant=-1, library=None):
     _check(L.mi355rt_debug_prepare_scene(C.byref(sc), int(forced_variant), C.byref(variant), C.byref(inline_steps), prims.ctypes.data, C.byref(n_prims),
                                          nodes.ctypes.data, C.byref(n_nodes), tris.ctypes.data, C.byref(n_tris)), "mi355rt_debug_prepare_scene", L)
     return Prepared(variant.value, inline_steps.value, prims, nodes, tris)
+
+
+def camera_masks(scene, camera, settings, options=None, forced_variant=-1, library=None):
+    """Diagnostic (mi355rt_debug_camera_masks): the per-pixel primitive masks set_scene builds for the camera pass of k_render_ctr_simple_qc -- bit i
+    of a pixel's word set = a camera ray of that pixel may hit primitive i.  No GPU and no context are needed.  Without options: uint32
+    [height, width], the image's table; with options: uint32 [rows, width], the table a render with those options reads (its selected rows).
+    None when the scene gets no table (more than 32 primitives, or another kernel serves it)."""
+    L = library or lib()
+    sc = getattr(scene, "c", scene)
+    n = C.c_uint64()
+    opt = C.byref(options) if options is not None else None
+    _check(L.mi355rt_debug_camera_masks(C.byref(sc), C.byref(camera), C.byref(settings), opt, int(forced_variant), None, 0, C.byref(n)),
+           "mi355rt_debug_camera_masks", L)
+    if n.value == 0:
+        return None
+    out = np.zeros(n.value, np.uint32)
+    _check(L.mi355rt_debug_camera_masks(C.byref(sc), C.byref(camera), C.byref(settings), opt, int(forced_variant), out.ctypes.data, out.size, C.byref(n)),
+           "mi355rt_debug_camera_masks", L)
+    return out.reshape(-1, settings.width)
 
 
 def render(scene, camera, settings, options=None, want_linear=True, want_stats=True, library=None):

@@ -1,0 +1,109 @@
+// The camera-mask builder (csrc/device/rt_prepare.cpp build_camera_masks, gather_camera_masks) under AddressSanitizer + UndefinedBehaviorSanitizer:
+// a program of its own, built by tests/test_camera_masks.py from this file and rt_prepare.cpp with plain g++ (no ROCm).
+// A scene handed over in a file (the test writes cornell) at three sizes, its strip plans, and the records the builder must answer with "keep":
+// every case returns without a sanitizer report.
+//   usage: camera_masks_main <scene file>      the file: u32 n_primitives, u32 n_materials, the mi355rt_primitive and mi355rt_material records, a mi355rt_camera
+#include <cmath>
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+#include <limits>
+#include <string>
+#include <vector>
+
+#include "../../include/mi355rt.h"
+#include "../../raytracer-rust_amd/csrc/device/rt_prepare.h"
+
+using namespace mi355rt;
+
+static int g_fail = 0;
+static void expect(bool ok, const std::string& what) { if (!ok) { std::printf("UNEXPECTED: %s\n", what.c_str()); ++g_fail; } }
+
+static DevPrim quad(float cx, float cy, float cz, float half) {          // facing +z, centred at c
+    DevPrim p{}; p.kind = MI355RT_PRIM_QUAD; p.run_end = 1;
+    const float n[4] = {0.f, 0.f, 1.f, cz}, base[3] = {cx - half, cy - half, cz}, e0[3] = {2 * half, 0.f, 0.f}, e1[3] = {0.f, 2 * half, 0.f};
+    std::memcpy(p.d, n, 16); std::memcpy(p.d + 4, base, 12); std::memcpy(p.d + 7, e0, 12); std::memcpy(p.d + 10, e1, 12);
+    p.d[13] = p.d[14] = 1.0f / (4 * half * half);
+    return p;
+}
+static DevPrim cube(float cx, float cy, float cz, float sx, float sy, float sz) {      // axis-aligned; the builder reads w2o (d[0..11]) only
+    DevPrim p{}; p.kind = MI355RT_PRIM_CUBE; p.run_end = 1;
+    p.d[0] = 1.0f / sx; p.d[4] = 1.0f / sy; p.d[8] = 1.0f / sz; p.d[9] = -cx / sx; p.d[10] = -cy / sy; p.d[11] = -cz / sz;
+    return p;
+}
+static uint64_t count(const std::vector<uint32_t>& t, uint32_t bit) { uint64_t n = 0; for (uint32_t w : t) n += (w >> bit) & 1u; return n; }
+
+int main(int argc, char** argv) {
+    if (argc < 2) { std::printf("usage: camera_masks_main <scene file>\n"); return 2; }
+    std::vector<uint32_t> table, plan;
+    {
+        std::FILE* f = std::fopen(argv[1], "rb");
+        uint32_t head[2] = {0, 0};
+        if (!f || std::fread(head, 4, 2, f) != 2 || head[0] > 1024 || head[1] > 1024) { std::printf("UNEXPECTED: cannot read %s\n", argv[1]); return 2; }
+        std::vector<mi355rt_primitive> prims(head[0]); std::vector<mi355rt_material> mats(head[1]); mi355rt_camera camera{};
+        const bool ok = std::fread(prims.data(), sizeof(mi355rt_primitive), prims.size(), f) == prims.size() &&
+                        std::fread(mats.data(), sizeof(mi355rt_material), mats.size(), f) == mats.size() && std::fread(&camera, sizeof camera, 1, f) == 1;
+        std::fclose(f);
+        if (!ok) { std::printf("UNEXPECTED: %s is short\n", argv[1]); return 2; }
+        mi355rt_scene sc{}; sc.primitives = prims.data(); sc.n_primitives = head[0]; sc.materials = mats.data(); sc.n_materials = head[1];
+        PreparedScene ps;
+        expect(prepare_scene(&sc, ps) == MI355RT_OK, "the scene should prepare: " + last_error());
+        DevCamera cam; std::memcpy(&cam, &camera, sizeof cam);
+        for (uint32_t w : {80u, 800u, 97u}) {
+            const uint32_t h = w == 97u ? 1u : w * 3u / 4u;
+            build_camera_masks(ps, cam, w, h, table);
+            expect(table.size() == (size_t)w * h, "one word per pixel");
+            uint64_t bits = 0, empty = 0; bool small = true;
+            for (uint32_t m : table) { bits += (uint64_t)__builtin_popcount(m); empty += m == 0u; small = small && (head[0] >= 32 || m < (1u << head[0])); }
+            expect(small, "only bits of the list's primitives");
+            if (h > 1u) expect((double)bits <= 1.25 * (double)table.size() && 5 * empty >= table.size(), "cornell: the masks cull");
+            // the row plans of a render: strips of 4 over 3 parts, a window, one row, none
+            const mi355rt_settings st{w, h, 1, 3};
+            for (int k = 0; k < 4; ++k) {
+                mi355rt_options o{}; o.abi_version = MI355RT_ABI_VERSION; o.rng_mode = MI355RT_RNG_CTR;
+                if (k == 0) { o.strip_rows = 4; o.n_parts = 3; o.part = 1; } else if (k == 1) { o.row_begin = h / 3; o.row_end = h / 2; } else if (k == 2) { o.row_begin = h - 1; } else { o.row_begin = h / 2; o.row_end = h / 2; }
+                RowSel sel; expect(select_rows(st, &o, sel) == MI355RT_OK, "select_rows");
+                gather_camera_masks(table, w, sel.rows.data(), sel.rows.size(), plan);
+                expect(plan.size() == sel.rows.size() * (size_t)w, "gathered size");
+                for (size_t j = 0; j < sel.rows.size(); ++j) expect(std::memcmp(plan.data() + j * w, table.data() + (size_t)sel.rows[j] * w, (size_t)w * 4) == 0, "gathered row");
+            }
+        }
+    }
+    // hand-made lists; the camera looks down -z from (0, 0, 5)
+    DevCamera cam{}; cam.position[2] = 5.f; cam.forward[2] = -1.f; cam.right[0] = 1.f; cam.true_up[1] = 1.f; cam.half_width = 0.6f; cam.half_height = 0.45f;
+    const float nan = std::numeric_limits<float>::quiet_NaN(), inf = std::numeric_limits<float>::infinity();
+    PreparedScene ps;
+    ps.prims = {quad(0, 0, 0, 1), quad(0, 0, 9, 1), quad(0, 0, 0, 1e6f), quad(0.3f, 0.2f, 0, 1e-3f), quad(0, 0, 0, 1), quad(0, 0, 0, 1),
+                cube(0, 0, 0, 1, 1, 1), cube(0, 0, 4.5f, 2, 2, 2), cube(0, 0, 0, 1, 0, 1), cube(0, 0, 0, 1, 1, 1), cube(1e30f, 0, 0, 1e-30f, 1, 1), quad(5e4f, 0, 4.999f, 1e5f)};
+    ps.prims[4].d[5] = nan; ps.prims[5].d[13] = inf; ps.prims[9].d[3] = nan;
+    ps.prims[11].d[0] = 0.f; ps.prims[11].d[1] = 1.f; ps.prims[11].d[2] = 0.f; ps.prims[11].d[3] = 0.f;      // a plane through the camera, edge-on
+    const uint32_t W = 64, H = 48; const uint64_t N = (uint64_t)W * H;
+    build_camera_masks(ps, cam, W, H, table);
+    expect(table.size() == N, "hand-made: one word per pixel");
+    expect(count(table, 0) > 0 && count(table, 0) < N, "a quad in view is culled somewhere and kept somewhere");
+    expect(count(table, 1) == 0, "a quad behind the camera is culled everywhere");
+    expect(count(table, 2) == N, "a quad that reaches the camera plane or fills the view is kept everywhere");
+    expect(count(table, 3) >= 1 && count(table, 3) <= 16, "a quad smaller than a pixel keeps a few pixels");
+    expect(count(table, 4) == N && count(table, 5) == N && count(table, 9) == N, "records that are not finite are kept everywhere");
+    expect(count(table, 6) > 0 && count(table, 6) < N, "a cube in view");
+    expect(count(table, 7) == N, "the camera inside a cube: kept everywhere");
+    expect(count(table, 8) == N, "a cube of zero scale (infinite world_to_object): kept everywhere");
+    for (DevCamera c : {DevCamera{}, cam}) {                                  // a camera of zeros; one that is not finite
+        if (c.half_width != 0.f) { c.forward[0] = nan; }
+        build_camera_masks(ps, c, W, H, table);
+        bool all = true; for (uint32_t m : table) all = all && m == 0xFFFu;
+        expect(all, "a degenerate camera keeps everything");
+    }
+    build_camera_masks(ps, cam, 1, 1, table); expect(table.size() == 1, "1 x 1");
+    build_camera_masks(ps, cam, 3, 1 << 14, table); expect(table.size() == (size_t)3 << 14, "3 x 16384");
+    ps.prims.assign(33, quad(0, 0, 0, 1));
+    build_camera_masks(ps, cam, W, H, table); expect(table.empty(), "33 primitives: no table");
+    ps.prims.assign(32, quad(0, 0, 0, 1));
+    build_camera_masks(ps, cam, W, H, table); expect(table.size() == N && table[N / 2 + W / 2] == 0xFFFFFFFFu, "32 primitives: bit 31 is used");
+    ps.prims.clear();
+    build_camera_masks(ps, cam, W, H, table); expect(table.empty(), "an empty list: no table");
+    DevPrim sphere{}; sphere.kind = MI355RT_PRIM_SPHERE; ps.prims = {sphere, quad(0, 0, 0, 1)};
+    build_camera_masks(ps, cam, W, H, table); expect(count(table, 0) == N && count(table, 1) < N, "another kind keeps its bit");
+    if (g_fail == 0) std::printf("camera masks: all cases behaved\n");
+    return g_fail ? 1 : 0;
+}
