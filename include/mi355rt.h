@@ -39,7 +39,8 @@ extern "C" {
                                     5: mi355rt_multi_context_* exported.  No struct changed in 5: options.abi_version 4 is still accepted.
                                     Added within version 5 (no struct changed, the number stays): mi355rt_multi_context_render_progressive and
                                     mi355rt_render_progressive_multi -- a caller that needs them probes for the symbols (dlsym), not the number.
-                                    Likewise the ray queries: mi355rt_context_trace_rays, mi355rt_context_first_hits, mi355rt_trace_rays. */
+                                    Likewise the ray queries: mi355rt_context_trace_rays, mi355rt_context_first_hits, mi355rt_trace_rays;
+                                    and the denoiser: mi355rt_denoise_scratch_bytes, mi355rt_context_denoise, mi355rt_denoise. */
 
 /* ---- error codes ------------------------------------------------------------------------- */
 #define MI355RT_OK               0
@@ -327,6 +328,60 @@ int  mi355rt_context_first_hits(mi355rt_context* ctx, const mi355rt_options* opt
  * It pays mi355rt_context_set_scene in full on every call -- the scene upload and, for the scenes named there, its probe render -- so a caller
  * with more than one batch of rays keeps a context and calls mi355rt_context_trace_rays. */
 int  mi355rt_trace_rays(const mi355rt_scene* scene, const mi355rt_ray* rays, uint32_t n_rays, mi355rt_hit* out_hits);
+
+/* ---- denoising a preview: an edge-avoiding a-trous filter guided by first-hit records (added within ABI version 5: probe for the symbols) ----
+ * For the first chunks of a progressive render: the noisy linear image and the records of mi355rt_context_first_hits for the same rows go in,
+ * a filtered linear and / or packed image comes out.  Not part of the reference; an independent restatement of the definition below in
+ * float32 is bit-identical to the kernels (the library is built without FMA contraction).
+ *
+ * WINDOW.  `rows` is a CONTIGUOUS window of the image, `width` pixels wide: the filter has no meaning across the gaps of an interleaved strip
+ * selection.  Pass what mi355rt_rows_selected reports for {row_begin, row_end} with n_parts <= 1, and the buffers of that selection.
+ *
+ * THE FILTER.  All arithmetic is float32, one rounding per operation, in the order written, IEEE division.  c is the colour image of the
+ * previous level (level 0: the input), g the guide record of a pixel; a pixel is a MISS when g.primitive == MI355RT_NO_HIT.
+ *   Per level k = 0 .. levels-1: step s = 1 << k, sigma_k = sigma_color * 2^-k, a_k = 1.0f / (sigma_k * sigma_k)   (computed on the host, f32).
+ *   Taps of pixel p = (x, y), y local to the window: dy = -2 .. 2 (outer loop), dx = -2 .. 2 (inner loop); q = (x + dx*s, y + dy*s); a tap
+ *   outside [0, width) x [0, rows) is skipped.  h = K[|dy|] * K[|dx|], K = {3/8, 1/4, 1/16}.
+ *   Geometry weight G:  p a miss: G = 1 if q is a miss, else 0.   p a hit, q a miss: G = 0.   Otherwise
+ *       nd = (n_p.x*n_q.x + n_p.y*n_q.y) + n_p.z*n_q.z;   wn = nd > 0 ? nd : 0, then wn = wn*wn repeated normal_squarings times;
+ *       D = P_q - P_p;   d = |(n_p.x*D.x + n_p.y*D.y) + n_p.z*D.z|;   e = 1 - d / (sigma_plane * t_p);   wp = e > 0 ? e : 0;   G = wn * wp.
+ *   Colour weight:  dc = c_q - c_p;   d2 = (dc.r*dc.r + dc.g*dc.g) + dc.b*dc.b;   wc = 1 / (1 + d2 * a_k).
+ *   Accumulation:  w = (h * G) * wc.  A tap with !(w > 0) is SKIPPED, nothing is added.  Otherwise acc.ch += c_q.ch * w (r, g, b), ws += w.
+ *   Result of the level:  ws > 0 ? acc.ch / ws : c_p.ch   (one division per channel).
+ *   d_out_linear receives the last level's image, d_out_packed color_to_u32(sqrt(.)) of it -- the packing of every render call (NaN and negative
+ *   channels pack as 0, +inf as 255).  levels == 0 copies the input to the output (and packs it).
+ * CONSEQUENCES.  A NaN or infinite pixel passes through unchanged and contaminates no neighbour (its taps have a NaN or zero weight): as in
+ * mi355rt_scene, non-finite values propagate and nothing is validated.  NaN guides (t = NaN "hits", NaN normals) drop their taps.  A firefly
+ * keeps itself (its colour weight towards everything else is small): a luminance clamp is not part of this call.  sigma_color halves per level
+ * (the published rule), so levels past the third or fourth change little.
+ *
+ * THE CALL.  The context supplies the device only -- no scene is needed, nothing is allocated, no state is kept in the context: the call
+ * enqueues its kernels on hip_stream and returns.  It may run beside a render or a query of the same context on another stream, and cannot
+ * fail inside a kernel (no waits, no atomics, bounded loops).  A pending watchdog failure of an EARLIER render on the context is returned the
+ * way the ray queries return it.  Every argument check comes before any HIP call and returns MI355RT_ERR_INVALID with a text that names the
+ * argument: a null context, input, hits or scratch; both outputs null; d_hits or d_scratch not 16-byte aligned, a float or packed buffer not
+ * 4-byte aligned; width or rows 0, width * rows >= 2^31; params out of range or not finite.
+ * d_out_linear MAY ALIAS d_linear_in: the first kernel copies the input into the scratch and nothing reads it afterwards.  Every word of every
+ * output record is written; nothing is written past the end of an output or of the scratch.  What the scratch holds afterwards is unspecified.
+ * One device only: the assembled image of a mi355rt_multi_context lives on hip_devices[0]; keep one mi355rt_context there for first_hits + denoise. */
+typedef struct mi355rt_denoise_params {   /* 16 bytes */
+    uint32_t levels;            /* a-trous passes, step 1, 2, 4, ...; 0 .. 8; 0 = copy (and pack) */
+    uint32_t normal_squarings;  /* normal weight = max(0, n_p . n_q) squared this many times; 0 .. 8 */
+    float    sigma_color;       /* > 0, finite; halved per level */
+    float    sigma_plane;       /* > 0, finite; plane distance relative to the centre's t */
+} mi355rt_denoise_params;
+/* params_or_null == NULL: {5, 5, 2.0f, 0.05f} */
+
+/* Bytes of d_scratch for a window of rows x width pixels (the layout is the library's own). */
+int  mi355rt_denoise_scratch_bytes(uint32_t width, uint32_t rows, uint64_t* out_bytes);
+/* DEVICE pointers: d_linear_in rows*width*3 floats in the layout of d_out_linear_rgb; d_hits rows*width mi355rt_hit, what
+ * mi355rt_context_first_hits wrote for the same window; d_scratch mi355rt_denoise_scratch_bytes; at least one of the outputs. */
+int  mi355rt_context_denoise(mi355rt_context* ctx, uint32_t width, uint32_t rows, const mi355rt_denoise_params* params_or_null,
+                             const void* d_linear_in, const void* d_hits, void* d_scratch,
+                             void* d_out_linear_or_null, void* d_out_packed_or_null, void* hip_stream);
+/* One-shot with HOST buffers on device 0 (upload, filter, copy back): what a host that owns no device memory calls. */
+int  mi355rt_denoise(uint32_t width, uint32_t rows, const mi355rt_denoise_params* params_or_null,
+                     const float* linear_in, const mi355rt_hit* hits, float* out_linear_or_null, uint32_t* out_packed_or_null);
 
 /* mi355rt_render over several GPUs from ONE host process (the reference's host is a single `main`):
  * row strips of options.strip_rows rows (0 -> 4) are dealt round-robin over `hip_devices`, each device

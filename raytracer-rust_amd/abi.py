@@ -102,6 +102,18 @@ HIT_DTYPE = np.dtype([("position", "<f4", 3), ("t", "<f4"), ("normal", "<f4", 3)
                       ("primitive", "<u4"), ("material", "<u4"), ("_pad", "<u4", 2)])
 
 
+class DenoiseParams(C.Structure):                         # mi355rt_denoise_params, 16 bytes
+    _fields_ = [("levels", u32), ("normal_squarings", u32), ("sigma_color", f32), ("sigma_plane", f32)]
+
+    @classmethod
+    def make(cls, levels=5, normal_squarings=5, sigma_color=2.0, sigma_plane=0.05):
+        """The defaults are what the calls use for a null pointer."""
+        return cls(levels, normal_squarings, sigma_color, sigma_plane)
+
+
+DENOISE_DEFAULTS = (5, 5, 2.0, 0.05)
+
+
 # mi355rt_progress_fn: int (*)(void* user, uint32_t samples_done, uint32_t samples_total, const uint32_t* packed_rgb)
 ProgressFn = C.CFUNCTYPE(C.c_int, C.c_void_p, u32, u32, C.POINTER(u32))
 

@@ -23,6 +23,7 @@
 #include "rt_device.h"
 #include "rt_host.h"
 #include "rt_query.h"
+#include "rt_denoise.h"
 
 using namespace mi355rt;
 
@@ -102,6 +103,7 @@ struct mi355rt_context {
     // sample, the resolve kernel writes each pixel where it belongs (ResolveParams.out_row).  `row_cost` = rays per path of each image
     // row, measured by set_scene with a small probe render of the same view; empty = natural order.
     std::vector<float> row_cost;
+    int knob_denoise_staged = 1;         // diagnostic knob "denoise_staged": 1 (the product) = the denoiser's levels with step 1 and 2 stage their tile in LDS; 0 = they gather like the later levels (the A/B of DESIGN.md 4.7)
     int knob_row_order = -1;             // diagnostic knob "row_order": 1 on; -1 / 0 off (NOT shipped as a default: no measured gain, see set_scene)
     uint32_t order_groups = 0;           // how many groups the cached tables were dealt over (work shards x bands)
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
@@ -237,6 +239,7 @@ int apply_knob(mi355rt_context* ctx, const std::string& name, int v) {
     else if (name == "spin_entry") { if (v < 1) return fail(MI355RT_ERR_INVALID, "knob spin_entry"); ctx->spin_limit_entry = (uint32_t)v; }
     else if (name == "wave_times") ctx->want_wave_times = v != 0;
     else if (name == "cam_cull") { if (v < -1 || v > 1) return fail(MI355RT_ERR_INVALID, "knob cam_cull"); ctx->knob_cam_cull = v; }
+    else if (name == "denoise_staged") { if (v < 0 || v > 1) return fail(MI355RT_ERR_INVALID, "knob denoise_staged"); ctx->knob_denoise_staged = v; }
     else if (name == "row_order") { if (v < -1 || v > 1) return fail(MI355RT_ERR_INVALID, "knob row_order"); ctx->knob_row_order = v; }
     else return fail(MI355RT_ERR_INVALID, "unknown knob " + name);
     return MI355RT_OK;
@@ -718,6 +721,62 @@ int mi355rt_trace_rays(const mi355rt_scene* scene, const mi355rt_ray* rays, uint
     if (!rc) rc = mi355rt_context_trace_rays(ctx, d_rays.p, n_rays, d_hits.p, nullptr);
     if (!rc && hipMemcpy(out_hits, d_hits.p, (size_t)n_rays * sizeof(mi355rt_hit), hipMemcpyDeviceToHost) != hipSuccess) rc = fail(MI355RT_ERR_HIP, "copy back hits");   // (waits for the query)
     d_rays.release(); d_hits.release();
+    std::string keep; keep.swap(last_error());                               // (destroy may overwrite the message of the failure being reported; swap never throws)
+    mi355rt_context_destroy(ctx);
+    last_error().swap(keep);
+    return rc;
+    });
+}
+
+// ---- the denoiser (rt_denoise.hip): an a-trous filter over a linear image, guided by first-hit records --------------------------------
+// The context names the device and carries the error word of its renders; nothing of it is read or written by the kernels, so the
+// call neither waits on `done` nor records it.  What is decided before a device is involved -- the arguments, the per-level constants -- is
+// rt_prepare.cpp's.
+int mi355rt_denoise_scratch_bytes(uint32_t width, uint32_t rows, uint64_t* out_bytes) {
+    return guard([&]() -> int { return denoise_scratch_bytes(width, rows, out_bytes); });
+}
+
+int mi355rt_context_denoise(mi355rt_context* ctx, uint32_t width, uint32_t rows, const mi355rt_denoise_params* params, const void* d_linear_in,
+                            const void* d_hits, void* d_scratch, void* d_out_linear, void* d_out_packed, void* hip_stream) {
+    return guard([&]() -> int {
+    static_assert(sizeof(mi355rt_hit) == 48 && sizeof(mi355rt_denoise_params) == 16, "the prepass reads a hit record as three 16-byte words");
+    if (!ctx) return fail(MI355RT_ERR_INVALID, "denoise: ctx is null");
+    DenoiseLaunch d{};
+    if (int rc = check_denoise_buffers(d_linear_in, d_hits, d_scratch, d_out_linear, d_out_packed)) return rc;
+    if (int rc = plan_denoise(width, rows, params, d.plan)) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (int erc = report_device_error(ctx)) return erc;              // an earlier asynchronous render on this context failed
+    d.in = (const float*)d_linear_in; d.hits = d_hits; d.scratch = d_scratch;
+    d.out_linear = (float*)d_out_linear; d.out_packed = (uint32_t*)d_out_packed; d.width = width; d.rows = rows; d.staged = ctx->knob_denoise_staged;
+    if (launch_denoise(d, hip_stream) != 0) return fail(MI355RT_ERR_HIP, "k_denoise launch failed");
+    return MI355RT_OK;
+    });
+}
+
+// Host buffers in, host buffers out: a context on device 0 (no scene), the image and the records uploaded, one call, the results copied back.
+int mi355rt_denoise(uint32_t width, uint32_t rows, const mi355rt_denoise_params* params, const float* linear_in, const mi355rt_hit* hits,
+                    float* out_linear, uint32_t* out_packed) {
+    return guard([&]() -> int {
+    DenoisePlan plan;
+    if (!linear_in) return fail(MI355RT_ERR_INVALID, "denoise: linear_in is null");
+    if (!hits) return fail(MI355RT_ERR_INVALID, "denoise: hits is null");
+    if (!out_linear && !out_packed) return fail(MI355RT_ERR_INVALID, "denoise: out_linear and out_packed are both null");
+    if (int rc = plan_denoise(width, rows, params, plan)) return rc;
+    const size_t n = (size_t)width * rows;
+    mi355rt_context* ctx = nullptr;
+    int rc = mi355rt_context_create(0, &ctx); if (rc) return rc;
+    DevBuf<float> d_in, d_lin; DevBuf<mi355rt_hit> d_hits; DevBuf<uint32_t> d_packed; DevBuf<unsigned char> d_scratch;
+    rc = d_in.ensure(n * 3);
+    if (!rc) rc = d_hits.ensure(n);
+    if (!rc) rc = d_scratch.ensure(n * DENOISE_SCRATCH_PER_PIXEL);
+    if (!rc && out_linear) rc = d_lin.ensure(n * 3);
+    if (!rc && out_packed) rc = d_packed.ensure(n);
+    if (!rc && hipMemcpy(d_in.p, linear_in, n * 12, hipMemcpyHostToDevice) != hipSuccess) rc = fail(MI355RT_ERR_HIP, "upload image");
+    if (!rc && hipMemcpy(d_hits.p, hits, n * sizeof(mi355rt_hit), hipMemcpyHostToDevice) != hipSuccess) rc = fail(MI355RT_ERR_HIP, "upload hits");
+    if (!rc) rc = mi355rt_context_denoise(ctx, width, rows, params, d_in.p, d_hits.p, d_scratch.p, out_linear ? d_lin.p : nullptr, out_packed ? d_packed.p : nullptr, nullptr);
+    if (!rc && out_linear && hipMemcpy(out_linear, d_lin.p, n * 12, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(MI355RT_ERR_HIP, "copy back linear");   // (waits for the kernels)
+    if (!rc && out_packed && hipMemcpy(out_packed, d_packed.p, n * 4, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(MI355RT_ERR_HIP, "copy back packed");
+    d_in.release(); d_lin.release(); d_hits.release(); d_packed.release(); d_scratch.release();
     std::string keep; keep.swap(last_error());                               // (destroy may overwrite the message of the failure being reported; swap never throws)
     mi355rt_context_destroy(ctx);
     last_error().swap(keep);

@@ -45,6 +45,51 @@ int check_settings(const mi355rt_settings* st) {
     return MI355RT_OK;
 }
 
+static int check_denoise_size(uint32_t width, uint32_t rows) {
+    if (width == 0) return fail(MI355RT_ERR_INVALID, "denoise: width is 0");
+    if (rows == 0) return fail(MI355RT_ERR_INVALID, "denoise: rows is 0");
+    if ((uint64_t)width * rows >= (1ull << 31)) return fail(MI355RT_ERR_INVALID, "denoise: width * rows must be below 2^31");
+    return MI355RT_OK;
+}
+
+int plan_denoise(uint32_t width, uint32_t rows, const mi355rt_denoise_params* params, DenoisePlan& plan) {
+    if (int rc = check_denoise_size(width, rows)) return rc;
+    const mi355rt_denoise_params defaults = {5u, 5u, 2.0f, 0.05f};
+    const mi355rt_denoise_params& p = params ? *params : defaults;
+    if (p.levels > DENOISE_MAX_LEVELS) return fail(MI355RT_ERR_INVALID, "denoise: params.levels must be 0 .. 8");
+    if (p.normal_squarings > DENOISE_MAX_SQUARINGS) return fail(MI355RT_ERR_INVALID, "denoise: params.normal_squarings must be 0 .. 8");
+    if (!(p.sigma_color > 0.0f) || !std::isfinite(p.sigma_color)) return fail(MI355RT_ERR_INVALID, "denoise: params.sigma_color must be positive and finite");
+    if (!(p.sigma_plane > 0.0f) || !std::isfinite(p.sigma_plane)) return fail(MI355RT_ERR_INVALID, "denoise: params.sigma_plane must be positive and finite");
+    plan.levels = p.levels; plan.normal_squarings = p.normal_squarings; plan.sigma_plane = p.sigma_plane;
+    for (uint32_t k = 0; k < DENOISE_MAX_LEVELS; ++k) {
+        const float sigma = p.sigma_color * std::ldexp(1.0f, -(int)k);   // 2^-k is exact: one rounding
+        const float sq = sigma * sigma;
+        plan.inv_sigma2[k] = 1.0f / sq;
+    }
+    return MI355RT_OK;
+}
+
+int check_denoise_buffers(const void* linear_in, const void* hits, const void* scratch, const void* out_linear, const void* out_packed) {
+    const auto misaligned = [](const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1u)) != 0u; };
+    if (!linear_in) return fail(MI355RT_ERR_INVALID, "denoise: d_linear_in is null");
+    if (!hits) return fail(MI355RT_ERR_INVALID, "denoise: d_hits is null");
+    if (!scratch) return fail(MI355RT_ERR_INVALID, "denoise: d_scratch is null");
+    if (!out_linear && !out_packed) return fail(MI355RT_ERR_INVALID, "denoise: d_out_linear and d_out_packed are both null");
+    if (misaligned(hits, 16)) return fail(MI355RT_ERR_INVALID, "denoise: d_hits must be 16-byte aligned");
+    if (misaligned(scratch, 16)) return fail(MI355RT_ERR_INVALID, "denoise: d_scratch must be 16-byte aligned");
+    if (misaligned(linear_in, 4)) return fail(MI355RT_ERR_INVALID, "denoise: d_linear_in must be 4-byte aligned");
+    if (misaligned(out_linear, 4)) return fail(MI355RT_ERR_INVALID, "denoise: d_out_linear must be 4-byte aligned");
+    if (misaligned(out_packed, 4)) return fail(MI355RT_ERR_INVALID, "denoise: d_out_packed must be 4-byte aligned");
+    return MI355RT_OK;
+}
+
+int denoise_scratch_bytes(uint32_t width, uint32_t rows, uint64_t* out_bytes) {
+    if (!out_bytes) return fail(MI355RT_ERR_INVALID, "denoise: out_bytes is null");
+    if (int rc = check_denoise_size(width, rows)) return rc;
+    *out_bytes = (uint64_t)width * rows * DENOISE_SCRATCH_PER_PIXEL;
+    return MI355RT_OK;
+}
+
 }  // namespace mi355rt
 
 namespace {

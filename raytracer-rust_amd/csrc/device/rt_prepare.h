@@ -40,6 +40,20 @@ struct RowSel { std::vector<uint32_t> rows; };
 int select_rows(const mi355rt_settings& st, const mi355rt_options* o, RowSel& sel);
 int check_settings(const mi355rt_settings* st);
 
+// The denoiser (mi355rt.h, mi355rt_context_denoise): what the host decides before a launch.
+constexpr uint32_t DENOISE_MAX_LEVELS = 8, DENOISE_MAX_SQUARINGS = 8;
+constexpr uint64_t DENOISE_SCRATCH_PER_PIXEL = 64;
+struct DenoisePlan {
+    uint32_t levels, normal_squarings;
+    float sigma_plane;
+    float inv_sigma2[DENOISE_MAX_LEVELS];                            // a_k = 1 / (sigma_k * sigma_k), sigma_k = sigma_color * 2^-k: f32, one rounding per operation
+};
+// width, rows and the parameters (null: the defaults) -> the plan; MI355RT_ERR_INVALID and a text that names the argument otherwise.
+int plan_denoise(uint32_t width, uint32_t rows, const mi355rt_denoise_params* params_or_null, DenoisePlan& plan);
+// The pointer rules of mi355rt_context_denoise: input, hits and scratch given, at least one output, hits and scratch 16-byte aligned, the rest 4-byte aligned.
+int check_denoise_buffers(const void* linear_in, const void* hits, const void* scratch, const void* out_linear, const void* out_packed);
+int denoise_scratch_bytes(uint32_t width, uint32_t rows, uint64_t* out_bytes);
+
 // A validated scene in the form the device holds it (rt_device.h), still in host memory, and what the choice of the kernel reads.
 struct PreparedScene {
     // DO NOT REORDER these four, and keep mesh_roots alive with them: they are freed last to first, behind the upload, exactly as build_device_scene's

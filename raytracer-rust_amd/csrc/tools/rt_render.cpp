@@ -4,10 +4,13 @@
 //
 //   rt_render <scene.json> [-o out.png] [--width W] [--height H] [--spp N] [--max-depth D]
 //             [--rng ctr|ref] [--seed S] [--skip-unknown] [--chunk N] [--pfm out.pfm] [--exr out.exr] [--gpus N | --devices a,b,..]
+//             [--denoise-out denoised.png]
 // --fix-aabb / --fix-wo3 switch on the two opt-in fixes (MI355RT_FLAG_FIXED_AABB, wo3_four_index_stride): not the reference's image.
 // --gpus N deals row strips over HIP devices 0..N-1 from this one process (mi355rt_render_multi); --devices a,b,... names them
 // (a device may repeat: the strip plan of N GPUs on a one-GPU machine).
 // --chunk N renders N samples per pixel at a time and rewrites the PNG after every chunk (a preview that refines).
+// --denoise-out PATH writes, besides -o, the final image filtered by mi355rt_context_denoise with its defaults, guided by the first hits of the
+// same view (a context on the first device: set_scene, first_hits, denoise).  Without it nothing the tool writes changes.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -15,11 +18,37 @@
 #include <string>
 #include <vector>
 
+#include <hip/hip_runtime_api.h>
+
 #include "../../../include/mi355rt.h"
 
+// The final linear image, filtered with the defaults and packed: out[width * height].  0, or 1 with the failure on stderr.
+static int denoise_image(int hip_device, const mi355rt_scene* sc, const mi355rt_camera* cam, const mi355rt_settings* st, const float* linear, uint32_t* out) {
+    const size_t n = (size_t)st->width * st->height;
+    uint64_t scratch_bytes = 0;
+    mi355rt_context* ctx = nullptr;
+    void *d_lin = nullptr, *d_hits = nullptr, *d_scratch = nullptr, *d_packed = nullptr;
+    const char* what = nullptr;
+    int rc = mi355rt_denoise_scratch_bytes(st->width, st->height, &scratch_bytes);
+    if (!rc && hipSetDevice(hip_device) != hipSuccess) what = "hipSetDevice";
+    if (!rc && !what) rc = mi355rt_context_create(hip_device, &ctx);
+    if (!rc && !what) rc = mi355rt_context_set_scene(ctx, sc, cam, st);
+    if (!rc && !what && (hipMalloc(&d_lin, n * 12) != hipSuccess || hipMalloc(&d_hits, n * sizeof(mi355rt_hit)) != hipSuccess ||
+                hipMalloc(&d_scratch, scratch_bytes) != hipSuccess || hipMalloc(&d_packed, n * 4) != hipSuccess)) what = "hipMalloc";
+    if (!rc && !what && hipMemcpy(d_lin, linear, n * 12, hipMemcpyHostToDevice) != hipSuccess) what = "upload";
+    if (!rc && !what) rc = mi355rt_context_first_hits(ctx, nullptr, d_hits, nullptr);
+    if (!rc && !what) rc = mi355rt_context_denoise(ctx, st->width, st->height, nullptr, d_lin, d_hits, d_scratch, nullptr, d_packed, nullptr);
+    if (!rc && !what && hipMemcpy(out, d_packed, n * 4, hipMemcpyDeviceToHost) != hipSuccess) what = "copy back";   // (waits for the kernels)
+    if (rc) std::fprintf(stderr, "denoise failed (%d): %s\n", rc, mi355rt_last_error());
+    else if (what) std::fprintf(stderr, "denoise failed: %s\n", what);
+    (void)hipFree(d_lin); (void)hipFree(d_hits); (void)hipFree(d_scratch); (void)hipFree(d_packed);
+    if (ctx) mi355rt_context_destroy(ctx);
+    return (rc || what) ? 1 : 0;
+}
+
 int main(int argc, char** argv) {
-    if (argc < 2) { std::fprintf(stderr, "usage: %s <scene.json> [-o out.png] [--width W] [--height H] [--spp N] [--max-depth D] [--rng ctr|ref] [--seed S] [--skip-unknown] [--chunk N] [--pfm out.pfm] [--exr out.exr] [--gpus N | --devices a,b,..] [--fix-aabb] [--fix-wo3]\n", argv[0]); return 2; }
-    std::string scene_path = argv[1], out_path = "render_pt.png", pfm_path, exr_path;
+    if (argc < 2) { std::fprintf(stderr, "usage: %s <scene.json> [-o out.png] [--width W] [--height H] [--spp N] [--max-depth D] [--rng ctr|ref] [--seed S] [--skip-unknown] [--chunk N] [--pfm out.pfm] [--exr out.exr] [--gpus N | --devices a,b,..] [--fix-aabb] [--fix-wo3] [--denoise-out denoised.png]\n", argv[0]); return 2; }
+    std::string scene_path = argv[1], out_path = "render_pt.png", pfm_path, exr_path, denoise_path;
     mi355rt_load_overrides ov{}; mi355rt_options opt{}; uint32_t chunk = 0, gpus = 1; std::vector<int> device_list;
     opt.abi_version = MI355RT_ABI_VERSION; opt.rng_mode = MI355RT_RNG_CTR; opt.strip_rows = 1; opt.n_parts = 1;
     for (int i = 2; i < argc; ++i) {
@@ -35,6 +64,7 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--chunk")) chunk = (uint32_t)std::atoi(next());
         else if (!std::strcmp(argv[i], "--pfm")) pfm_path = next();
         else if (!std::strcmp(argv[i], "--exr")) exr_path = next();
+        else if (!std::strcmp(argv[i], "--denoise-out")) denoise_path = next();
         else if (!std::strcmp(argv[i], "--gpus")) gpus = (uint32_t)std::atoi(next());
         else if (!std::strcmp(argv[i], "--devices")) {
             for (const char* q = next(); *q;) { char* e = nullptr; const long d = std::strtol(q, &e, 10); if (e == q) { std::fprintf(stderr, "--devices wants a comma-separated list of device numbers\n"); return 2; }
@@ -57,7 +87,7 @@ int main(int argc, char** argv) {
     std::printf("Scene loaded. Objects: %u. Image: %ux%u, Samples: %u, Max Depth: %u\n", sc->n_primitives, st->width, st->height,
                 st->samples_per_pixel, st->max_depth);
     std::vector<uint32_t> buffer((size_t)st->width * st->height);
-    std::vector<float> linear(pfm_path.empty() && exr_path.empty() ? 0 : (size_t)st->width * st->height * 3);
+    std::vector<float> linear(pfm_path.empty() && exr_path.empty() && denoise_path.empty() ? 0 : (size_t)st->width * st->height * 3);
     float* lin = linear.empty() ? nullptr : linear.data();
     mi355rt_stats stats{};
     std::printf("Rendering frame (%ux%u) with %u AA samples...\n", st->width, st->height, st->samples_per_pixel);
@@ -87,6 +117,12 @@ int main(int argc, char** argv) {
     std::printf("Image saved as '%s'\n", out_path.c_str());
     if (lin && !exr_path.empty() && mi355rt_write_exr(exr_path.c_str(), lin, st->width, st->height) != MI355RT_OK) { std::fprintf(stderr, "%s\n", mi355rt_host_last_error()); mi355rt_scene_free(ls); return 1; }
     if (lin && !pfm_path.empty() && mi355rt_write_pfm(pfm_path.c_str(), lin, st->width, st->height) != MI355RT_OK) { std::fprintf(stderr, "%s\n", mi355rt_host_last_error()); mi355rt_scene_free(ls); return 1; }
+    if (!denoise_path.empty()) {
+        std::vector<uint32_t> denoised(buffer.size());
+        if (denoise_image(devices[0], sc, mi355rt_loaded_scene_camera(ls), st, lin, denoised.data())) { mi355rt_scene_free(ls); return 1; }
+        if (mi355rt_write_png(denoise_path.c_str(), denoised.data(), st->width, st->height) != MI355RT_OK) { std::fprintf(stderr, "%s\n", mi355rt_host_last_error()); mi355rt_scene_free(ls); return 1; }
+        std::printf("Denoised image saved as '%s'\n", denoise_path.c_str());
+    }
     mi355rt_scene_free(ls);
     std::printf("Total %.3f s\n", std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
     return 0;

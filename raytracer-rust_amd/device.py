@@ -17,7 +17,8 @@ EXPORTS = ["mi355rt_render", "mi355rt_render_multi", "mi355rt_render_progressive
            "mi355rt_context_check", "mi355rt_context_set_share", "mi355rt_last_error", "mi355rt_abi_version",
            "mi355rt_multi_context_create", "mi355rt_multi_context_destroy", "mi355rt_multi_context_set_scene", "mi355rt_multi_context_render",
            "mi355rt_multi_context_check", "mi355rt_multi_context_render_progressive", "mi355rt_render_progressive_multi",
-           "mi355rt_context_trace_rays", "mi355rt_context_first_hits", "mi355rt_trace_rays"]
+           "mi355rt_context_trace_rays", "mi355rt_context_first_hits", "mi355rt_trace_rays",
+           "mi355rt_denoise_scratch_bytes", "mi355rt_context_denoise", "mi355rt_denoise"]
 
 _lib = None
 _extra = {}
@@ -176,6 +177,13 @@ def _bind(so):
         L.mi355rt_context_first_hits.argtypes = [C.c_void_p, C.POINTER(abi.Options), C.c_void_p, C.c_void_p]
         L.mi355rt_trace_rays.restype = C.c_int
         L.mi355rt_trace_rays.argtypes = [C.POINTER(abi.Scene), C.c_void_p, C.c_uint32, C.c_void_p]
+        L.mi355rt_denoise_scratch_bytes.restype = C.c_int
+        L.mi355rt_denoise_scratch_bytes.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]
+        L.mi355rt_context_denoise.restype = C.c_int
+        L.mi355rt_context_denoise.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(abi.DenoiseParams), C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_void_p, C.c_void_p]
+        L.mi355rt_denoise.restype = C.c_int
+        L.mi355rt_denoise.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(abi.DenoiseParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.mi355rt_debug_multi_part_ms.restype = C.c_int
         L.mi355rt_debug_multi_part_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_uint32, C.POINTER(C.c_uint32)]
         L.mi355rt_debug_set_knob.restype = C.c_int
@@ -333,6 +341,31 @@ def trace_rays(scene, rays, library=None):
     return hits
 
 
+def denoise_scratch_bytes(width, rows, library=None):
+    """mi355rt_denoise_scratch_bytes: the size of Context.denoise's d_scratch for a window of rows x width pixels."""
+    L = library or lib()
+    n = C.c_uint64()
+    _check(L.mi355rt_denoise_scratch_bytes(int(width), int(rows), C.byref(n)), "mi355rt_denoise_scratch_bytes", L)
+    return n.value
+
+
+def denoise(linear, hits, params=None, want_linear=True, want_packed=True, library=None):
+    """One-shot mi355rt_denoise with host buffers on device 0.  linear: float32 [rows, W, 3]; hits: abi.HIT_DTYPE [rows * W] (what first_hits
+    wrote for the same window); params: abi.DenoiseParams or None for the defaults.  Returns (linear f32 [rows, W, 3] or None, packed u32 [rows, W] or None)."""
+    L = library or lib()
+    linear = np.ascontiguousarray(linear, np.float32)
+    rows, W = linear.shape[0], linear.shape[1]
+    hits = np.ascontiguousarray(hits)
+    if hits.dtype != abi.HIT_DTYPE or hits.size != rows * W or linear.shape != (rows, W, 3):
+        raise ValueError("denoise: linear must be [rows, W, 3] and hits rows * W records of abi.HIT_DTYPE")
+    out_linear = np.zeros((rows, W, 3), np.float32) if want_linear else None
+    out_packed = np.zeros((rows, W), np.uint32) if want_packed else None
+    _check(L.mi355rt_denoise(W, rows, C.byref(params) if params is not None else None, C.c_void_p(linear.ctypes.data), C.c_void_p(hits.ctypes.data),
+                             C.c_void_p(out_linear.ctypes.data) if want_linear else None, C.c_void_p(out_packed.ctypes.data) if want_packed else None),
+           "mi355rt_denoise", L)
+    return out_linear, out_packed
+
+
 def debug_scatter(materials, records, hip_device=0, textures=None):
     """Diagnostic: one Material::scatter per record on the device.  materials: ctypes array of abi.Material;
     records: (material index, front_face, rd[3], p[3], n[3], (k0, k1, x, s, ray)).  Returns float32 [n, 10] rows
@@ -439,6 +472,14 @@ class Context:
         d_hits: device address of rows_selected(options) * width abi.Hit records, row-major over the selected rows."""
         _check(self._L.mi355rt_context_first_hits(self._h, C.byref(options) if options is not None else None, C.c_void_p(d_hits) if d_hits else None,
                                                   C.c_void_p(stream) if stream else None), "mi355rt_context_first_hits", self._L)
+
+    def denoise(self, width, rows, d_linear_in, d_hits, d_scratch, d_out_linear=None, d_out_packed=None, params=None, stream=None):
+        """mi355rt_context_denoise: the a-trous filter of mi355rt.h over a contiguous window of rows x width pixels, enqueued on `stream`.  Integer
+        device addresses: d_linear_in rows * width * 3 floats, d_hits what first_hits wrote for the window, d_scratch denoise_scratch_bytes(width, rows)
+        bytes; at least one of d_out_linear (may be d_linear_in) and d_out_packed.  params: abi.DenoiseParams or None for the defaults."""
+        p = lambda a: C.c_void_p(a) if a else None
+        _check(self._L.mi355rt_context_denoise(self._h, int(width), int(rows), C.byref(params) if params is not None else None, p(d_linear_in), p(d_hits),
+                                               p(d_scratch), p(d_out_linear), p(d_out_packed), p(stream)), "mi355rt_context_denoise", self._L)
 
     def kernel_variant(self):
         """Diagnostic: the counter-mode kernel chosen for the resident scene (0 lockstep, 1 lockstep+mesh, 2 state machine, 3 lockstep simple)."""
