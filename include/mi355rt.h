@@ -40,7 +40,8 @@ extern "C" {
                                     Added within version 5 (no struct changed, the number stays): mi355rt_multi_context_render_progressive and
                                     mi355rt_render_progressive_multi -- a caller that needs them probes for the symbols (dlsym), not the number.
                                     Likewise the ray queries: mi355rt_context_trace_rays, mi355rt_context_first_hits, mi355rt_trace_rays;
-                                    and the denoiser: mi355rt_denoise_scratch_bytes, mi355rt_context_denoise, mi355rt_denoise. */
+                                    and the denoiser: mi355rt_denoise_scratch_bytes, mi355rt_context_denoise, mi355rt_denoise;
+                                    and the occlusion queries: mi355rt_context_occluded, mi355rt_occluded, mi355rt_context_ambient_occlusion. */
 
 /* ---- error codes ------------------------------------------------------------------------- */
 #define MI355RT_OK               0
@@ -328,6 +329,66 @@ int  mi355rt_context_first_hits(mi355rt_context* ctx, const mi355rt_options* opt
  * It pays mi355rt_context_set_scene in full on every call -- the scene upload and, for the scenes named there, its probe render -- so a caller
  * with more than one batch of rays keeps a context and calls mi355rt_context_trace_rays. */
 int  mi355rt_trace_rays(const mi355rt_scene* scene, const mi355rt_ray* rays, uint32_t n_rays, mi355rt_hit* out_hits);
+
+/* ---- occlusion queries: does anything lie in front of t_max? (added within ABI version 5: probe for the symbols) --------------------------
+ * For visibility and shadow tests and for ambient-occlusion and lightmap baking: one word out per ray instead of a 48-byte record, no record
+ * is built, and the walk may stop early.
+ *
+ * DEFINITION.  Let h be the record mi355rt_context_trace_rays writes for the mi355rt_ray {origin, direction}.  Then
+ *       out[i] = (h.primitive != MI355RT_NO_HIT && h.t < t_max) ? 1 : 0,
+ * the comparison strict and in float32.  t_max is measured along the NORMALISED direction, the unit of mi355rt_hit.t.
+ * CONSEQUENCES.  A NaN t_max gives 0.  A NaN h.t gives 0 (the reference's negated comparisons accept such "hits": a zero direction against
+ * a sphere, an overflowing discriminant).  t_max = +inf asks for any hit with an ordered t.  t_max <= EPSILON (1e-4) gives 0: no hit is
+ * accepted at or below t_min = EPSILON.  Every output word is written, nothing is written past word n - 1, n == 0 is a no-op.
+ * THE WALK is the reference's (src/hittable.rs:45-58): closest_so_far starts at INFINITY and shrinks, whatever t_max is.  It does NOT start
+ * at t_max: Mesh::hit hands closest_so_far to its BVH as an object-space bound (sic), so a smaller start would prune other triangles and
+ * could change h.  Skipped is only this: once every ray of a wave holds an accepted candidate below its t_max, the rest of the LIST is not
+ * walked -- exact, because a later candidate is only accepted at or below the current one, so the final t is below t_max as well.  That
+ * argument needs every candidate's t to be ordered (after a NaN candidate the reference accepts anything).  The exit is therefore taken only
+ * where no test can produce a NaN: every number the tests read from the scene and every component of the ray's origin within +-65536, the
+ * normalised direction of a length in [1/2, 2] (any direction longer than 1e-4 that does not overflow).  Other rays, and every ray of other
+ * scenes, walk the whole list.  Inside a mesh's tree nothing is skipped: Mesh::hit rejects the whole mesh when the FINAL triangle's
+ * t_world lies below EPSILON, so a later, nearer triangle can turn a mesh that looked like a hit into a miss.
+ * The calls follow the protocol of the ray queries above: they only read the resident scene, may run on another stream beside a render of the
+ * same context, ignore mi355rt_context_set_share, cannot fail inside a kernel, and return a pending watchdog failure of an EARLIER render the
+ * way mi355rt_context_render returns it.  Every refusal is decided before any HIP call and is MI355RT_ERR_INVALID with a text that names the
+ * argument: a null context, no scene, a null or misaligned pointer (16 bytes for segments and hits, 4 for the outputs) when there is
+ * something to do, a bad abi_version or row selection, params out of range.  options.flags & MI355RT_FLAG_FIXED_AABB: MI355RT_ERR_UNSUPPORTED.
+ * One device only. */
+typedef struct mi355rt_segment {   /* 32 bytes; arrays 16-byte aligned; the layout of mi355rt_ray with the last pad read */
+    float origin[3];    float _pad0;     /* ignored */
+    float direction[3]; float t_max;     /* direction as in mi355rt_ray; t_max along the NORMALISED direction */
+} mi355rt_segment;
+/* n segments, DEVICE pointers; enqueues on hip_stream (NULL = default stream) and returns. */
+int  mi355rt_context_occluded(mi355rt_context* ctx, const void* d_segments, uint32_t n, void* d_out_u32, void* hip_stream);
+/* One-shot with HOST buffers (context on device 0, upload, query, copy back, destroy); it pays mi355rt_context_set_scene on every call. */
+int  mi355rt_occluded(const mi355rt_scene* scene, const mi355rt_segment* segments, uint32_t n, uint32_t* out);
+
+/* Ambient occlusion at the first hits: `samples` occlusion queries per selected pixel, made and counted on the device.
+ * d_hits is what mi355rt_context_first_hits wrote for the same row selection (rows selected, and their tables kept, exactly as that call does
+ * it); d_out_f32 (DEVICE, 4-byte aligned) holds one float per selected pixel, row-major over the selected rows.
+ *
+ * DEFINITION.  All arithmetic is float32, one rounding per operation, in the order written (the library is built without contraction).
+ * A pixel whose record is a miss (primitive == MI355RT_NO_HIT) gives 1.0f.  Otherwise, with P = hit.position, N = hit.normal, x the pixel's
+ * column and y its ABSOLUTE image row, for sample s = 0 .. samples-1:
+ *   Tries j = 0 .. 15:  w = pcg4d(x, y, s * 16 + j, seed)   (Jarzynski & Olano, JCGT 9(3) 2020: per word v = v * 1664525 + 1013904223; then
+ *       x += y*w, y += z*x, z += x*y, w += y*z; every word ^= itself >> 16; the four multiply-adds again; all in uint32),
+ *       c_k = (float)(w_k >> 8) * 2^-24 * 2 - 1 for k = 0, 1, 2 (every step exact: c_k = m * 2^-23 - 1 in [-1, 1)),
+ *       l2 = (c0*c0 + c1*c1) + c2*c2.   The first try with l2 < 1.0f gives v = c; if none of the 16 qualifies, v = (0, 0, 0).
+ *   Direction d = N + v, component by component.  The sample ray is the mi355rt_ray {P, d}: normalised once, as Ray::new does.
+ *   The sample is OCCLUDED exactly when mi355rt_context_occluded answers 1 for the segment {P, d, radius}.  The origin sits on the surface;
+ *   t_min = EPSILON is the only offset, as for the reference's bounce rays.
+ *   out = 1.0f - (float)count / (float)samples, count the INTEGER number of occluded samples: however the lanes are dealt and the counts
+ *   reduced, the result is the same bits. */
+typedef struct mi355rt_ao_params {   /* 16 bytes */
+    uint32_t samples;   /* 1, 2, 4, ... 256: a power of two */
+    uint32_t seed;
+    float    radius;    /* > 0 or +inf; NaN refused */
+    uint32_t _pad;      /* must be 0 */
+} mi355rt_ao_params;
+/* params_or_null == NULL: {16, 0, +inf, 0} */
+int  mi355rt_context_ambient_occlusion(mi355rt_context* ctx, const mi355rt_options* options_or_null, const mi355rt_ao_params* params_or_null,
+                                       const void* d_hits, void* d_out_f32, void* hip_stream);
 
 /* ---- denoising a preview: an edge-avoiding a-trous filter guided by first-hit records (added within ABI version 5: probe for the symbols) ----
  * For the first chunks of a progressive render: the noisy linear image and the records of mi355rt_context_first_hits for the same rows go in,

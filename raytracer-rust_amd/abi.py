@@ -102,6 +102,22 @@ HIT_DTYPE = np.dtype([("position", "<f4", 3), ("t", "<f4"), ("normal", "<f4", 3)
                       ("primitive", "<u4"), ("material", "<u4"), ("_pad", "<u4", 2)])
 
 
+class Segment(C.Structure):                               # mi355rt_segment, 32 bytes: a Ray whose last pad is read
+    _fields_ = [("origin", f32 * 3), ("_pad0", f32), ("direction", f32 * 3), ("t_max", f32)]
+
+
+SEGMENT_DTYPE = np.dtype([("origin", "<f4", 3), ("_pad0", "<f4"), ("direction", "<f4", 3), ("t_max", "<f4")])
+
+
+class AoParams(C.Structure):                              # mi355rt_ao_params, 16 bytes
+    _fields_ = [("samples", u32), ("seed", u32), ("radius", f32), ("_pad", u32)]
+
+    @classmethod
+    def make(cls, samples=16, seed=0, radius=float("inf")):
+        """The defaults are what the call uses for a null pointer."""
+        return cls(samples, seed, radius, 0)
+
+
 class DenoiseParams(C.Structure):                         # mi355rt_denoise_params, 16 bytes
     _fields_ = [("levels", u32), ("normal_squarings", u32), ("sigma_color", f32), ("sigma_plane", f32)]
 

@@ -24,6 +24,7 @@
 #include "rt_host.h"
 #include "rt_query.h"
 #include "rt_denoise.h"
+#include "rt_occlusion.h"
 
 using namespace mi355rt;
 
@@ -72,6 +73,7 @@ struct mi355rt_context {
     int blocks_per_cu[KERNEL_VARIANTS] = {}, vgprs[KERNEL_VARIANTS] = {}, sgprs = 0;
     uint32_t variant = KERNEL_LOCKSTEP;  // chosen per scene in set_scene
     bool has_mesh = false;
+    bool occlusion_may_exit = false;     // every number the hit tests read from the scene lies inside OCCLUSION_BOUND: the occlusion kernels may leave the list early (rt_prepare.h)
     uint32_t grid_div = 1;               // this context launches 1 / grid_div of the grid that fills the device: the caller keeps grid_div frames in flight, each on its own
                                          // context and stream, so that their persistent kernels are co-resident (see render_samples; mi355rt_context_set_share)
     uint32_t guided_mult = 16;           // run length = (left in shard) / (guided_mult * waves per shard); 16 measured best at 1/8-image launches
@@ -104,6 +106,7 @@ struct mi355rt_context {
     // row, measured by set_scene with a small probe render of the same view; empty = natural order.
     std::vector<float> row_cost;
     int knob_denoise_staged = 1;         // diagnostic knob "denoise_staged": 1 (the product) = the denoiser's levels with step 1 and 2 stage their tile in LDS; 0 = they gather like the later levels (the A/B of DESIGN.md 4.7)
+    int knob_ao_form = 0;                // diagnostic knob "ao_form": AO_FORM_* of rt_occlusion.h; 0 (the product) = a pixel's samples across the lanes of a wave, 1 = a pixel per lane (the A/B of DESIGN.md 4.8)
     int knob_row_order = -1;             // diagnostic knob "row_order": 1 on; -1 / 0 off (NOT shipped as a default: no measured gain, see set_scene)
     uint32_t order_groups = 0;           // how many groups the cached tables were dealt over (work shards x bands)
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
@@ -213,6 +216,7 @@ int build_device_scene(mi355rt_context* ctx, const mi355rt_scene* sc, const mi35
         HIP_TRY(hipMemcpy(ctx->textures.p, table.data(), table.size() * sizeof(DevTexture), hipMemcpyHostToDevice));
     }
     ctx->has_mesh = s.n_mesh_prims != 0;
+    ctx->occlusion_may_exit = scene_within_occlusion_bound(s);
     ctx->variant = choose_variant(s, ctx->forced_variant, built_variants());
     ctx->inline_steps = choose_inline_steps(s, ctx->knob_inline_steps);
     ctx->cam_mask_abs.clear(); ctx->cam_mask_host.clear();                    // (clear keeps the allocations: the next table is written in place)
@@ -240,6 +244,7 @@ int apply_knob(mi355rt_context* ctx, const std::string& name, int v) {
     else if (name == "wave_times") ctx->want_wave_times = v != 0;
     else if (name == "cam_cull") { if (v < -1 || v > 1) return fail(MI355RT_ERR_INVALID, "knob cam_cull"); ctx->knob_cam_cull = v; }
     else if (name == "denoise_staged") { if (v < 0 || v > 1) return fail(MI355RT_ERR_INVALID, "knob denoise_staged"); ctx->knob_denoise_staged = v; }
+    else if (name == "ao_form") { if (v < 0 || v > 1) return fail(MI355RT_ERR_INVALID, "knob ao_form"); ctx->knob_ao_form = v; }
     else if (name == "row_order") { if (v < -1 || v > 1) return fail(MI355RT_ERR_INVALID, "knob row_order"); ctx->knob_row_order = v; }
     else return fail(MI355RT_ERR_INVALID, "unknown knob " + name);
     return MI355RT_OK;
@@ -659,24 +664,10 @@ int mi355rt_context_trace_rays(mi355rt_context* ctx, const void* d_rays, uint32_
     });
 }
 
-int mi355rt_context_first_hits(mi355rt_context* ctx, const mi355rt_options* opt, void* d_hits, void* hip_stream) {
-    return guard([&]() -> int {
-    if (!ctx || !ctx->have_scene) return fail(MI355RT_ERR_INVALID, "context has no scene");
-    if (!d_hits) return fail(MI355RT_ERR_INVALID, "first_hits: d_hits is null");
-    if (!aligned16(d_hits)) return fail(MI355RT_ERR_INVALID, "first_hits: d_hits must be 16-byte aligned");
-    if (opt && (opt->flags & ~MI355RT_FLAG_FIXED_AABB) != 0u) return fail(MI355RT_ERR_INVALID, "options.flags has unknown bits");
-    const mi355rt_settings& st = ctx->settings;
-    RowSel sel;
-    {   mi355rt_options rows_only{};                                 // rng_mode, seed and workspace_bytes are not this call's business
-        if (opt) { rows_only = *opt; rows_only.rng_mode = MI355RT_RNG_CTR; }
-        const int rc = select_rows(st, opt ? &rows_only : nullptr, sel); if (rc) return rc; }
-    if (opt && (opt->flags & MI355RT_FLAG_FIXED_AABB) != 0u)
-        return fail(MI355RT_ERR_UNSUPPORTED, "first_hits: MI355RT_FLAG_FIXED_AABB is not built for ray queries (they answer as the reference does)");
-    if (sel.rows.empty()) return MI355RT_OK;
-    HIP_TRY(hipSetDevice(ctx->device));
-    if (int erc = report_device_error(ctx)) return erc;              // an earlier asynchronous render on this context failed
-    hipStream_t stream = (hipStream_t)hip_stream;
-    mi355rt_context::QueryRows* table = nullptr;
+// The device table (local output row -> absolute y) of a row selection, one per selection seen since set_scene; `sel.rows` is taken when a new one is made.
+// On return the table's upload is ordered before what is enqueued on `stream` next.
+static int query_row_table(mi355rt_context* ctx, RowSel& sel, hipStream_t stream, mi355rt_context::QueryRows*& table) {
+    table = nullptr;
     for (auto& t : ctx->query_rows) if (t.rows == sel.rows) { table = &t; break; }
     if (!table) {
         if (ctx->query_rows.size() >= 16) { HIP_TRY(hipDeviceSynchronize()); ctx->query_rows_release(); }   // a caller that keeps changing its selection: start over
@@ -694,6 +685,27 @@ int mi355rt_context_first_hits(mi355rt_context* ctx, const mi355rt_options* opt,
             return fail(MI355RT_ERR_HIP, "first_hits: row table upload failed");
         }
     } else if (table->stream != stream) HIP_TRY(hipStreamWaitEvent(stream, table->ready, 0));
+    return MI355RT_OK;
+}
+
+int mi355rt_context_first_hits(mi355rt_context* ctx, const mi355rt_options* opt, void* d_hits, void* hip_stream) {
+    return guard([&]() -> int {
+    if (!ctx || !ctx->have_scene) return fail(MI355RT_ERR_INVALID, "context has no scene");
+    if (!d_hits) return fail(MI355RT_ERR_INVALID, "first_hits: d_hits is null");
+    if (!aligned16(d_hits)) return fail(MI355RT_ERR_INVALID, "first_hits: d_hits must be 16-byte aligned");
+    if (opt && (opt->flags & ~MI355RT_FLAG_FIXED_AABB) != 0u) return fail(MI355RT_ERR_INVALID, "options.flags has unknown bits");
+    const mi355rt_settings& st = ctx->settings;
+    RowSel sel;
+    {   mi355rt_options rows_only{};                                 // rng_mode, seed and workspace_bytes are not this call's business
+        if (opt) { rows_only = *opt; rows_only.rng_mode = MI355RT_RNG_CTR; }
+        const int rc = select_rows(st, opt ? &rows_only : nullptr, sel); if (rc) return rc; }
+    if (opt && (opt->flags & MI355RT_FLAG_FIXED_AABB) != 0u)
+        return fail(MI355RT_ERR_UNSUPPORTED, "first_hits: MI355RT_FLAG_FIXED_AABB is not built for ray queries (they answer as the reference does)");
+    if (sel.rows.empty()) return MI355RT_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (int erc = report_device_error(ctx)) return erc;              // an earlier asynchronous render on this context failed
+    mi355rt_context::QueryRows* table = nullptr;
+    if (int rc = query_row_table(ctx, sel, (hipStream_t)hip_stream, table)) return rc;
     QueryParams q{};
     query_scene(ctx, q);
     q.rays = nullptr; q.hits = d_hits; q.rows = table->d; q.n = (uint32_t)(table->rows.size() * (size_t)st.width);   // (< 2^31: check_settings)
@@ -721,6 +733,73 @@ int mi355rt_trace_rays(const mi355rt_scene* scene, const mi355rt_ray* rays, uint
     if (!rc) rc = mi355rt_context_trace_rays(ctx, d_rays.p, n_rays, d_hits.p, nullptr);
     if (!rc && hipMemcpy(out_hits, d_hits.p, (size_t)n_rays * sizeof(mi355rt_hit), hipMemcpyDeviceToHost) != hipSuccess) rc = fail(MI355RT_ERR_HIP, "copy back hits");   // (waits for the query)
     d_rays.release(); d_hits.release();
+    std::string keep; keep.swap(last_error());                               // (destroy may overwrite the message of the failure being reported; swap never throws)
+    mi355rt_context_destroy(ctx);
+    last_error().swap(keep);
+    return rc;
+    });
+}
+
+// ---- occlusion queries (rt_occlusion.hip): does anything lie in front of t_max? -----------------------------------------------------------
+// The protocol of the ray queries: they read the scene arrays only, neither wait on `done` nor record it, and do not consult set_share.
+// Every refusal is rt_prepare.cpp's, before any HIP call.
+int mi355rt_context_occluded(mi355rt_context* ctx, const void* d_segments, uint32_t n, void* d_out, void* hip_stream) {
+    return guard([&]() -> int {
+    static_assert(sizeof(mi355rt_segment) == 32, "the kernel reads a segment as two 16-byte halves");
+    if (int rc = check_occluded_args(ctx != nullptr, ctx && ctx->have_scene, d_segments, n, d_out)) return rc;
+    if (n == 0) return MI355RT_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (int erc = report_device_error(ctx)) return erc;              // an earlier asynchronous render on this context failed
+    OcclusionParams q{};
+    q.prims = ctx->prims.p; q.nodes = ctx->nodes.p; q.tris = ctx->tris.p; q.n_prims = ctx->n_prims;
+    q.segments = d_segments; q.out = (uint32_t*)d_out; q.n = n; q.may_exit = ctx->occlusion_may_exit ? 1u : 0u;
+    if (launch_occluded(q, ctx->has_mesh, hip_stream) != 0) return fail(MI355RT_ERR_HIP, "k_occluded launch failed");
+    return MI355RT_OK;
+    });
+}
+
+int mi355rt_context_ambient_occlusion(mi355rt_context* ctx, const mi355rt_options* opt, const mi355rt_ao_params* params, const void* d_hits, void* d_out,
+                                      void* hip_stream) {
+    return guard([&]() -> int {
+    static_assert(sizeof(mi355rt_hit) == 48 && sizeof(mi355rt_ao_params) == 16, "the kernel reads a hit record as three 16-byte words");
+    RowSel sel; AoPlan plan{};
+    const mi355rt_settings no_settings{};
+    if (int rc = plan_ambient_occlusion(ctx != nullptr, ctx && ctx->have_scene, ctx ? ctx->settings : no_settings, opt, params, d_hits, d_out, sel, plan)) return rc;
+    if (sel.rows.empty()) return MI355RT_OK;
+    const mi355rt_settings& st = ctx->settings;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (int erc = report_device_error(ctx)) return erc;              // an earlier asynchronous render on this context failed
+    mi355rt_context::QueryRows* table = nullptr;
+    if (int rc = query_row_table(ctx, sel, (hipStream_t)hip_stream, table)) return rc;
+    AoLaunch a{};
+    a.prims = ctx->prims.p; a.nodes = ctx->nodes.p; a.tris = ctx->tris.p; a.n_prims = ctx->n_prims;
+    a.hits = d_hits; a.out = (float*)d_out; a.rows = table->d; a.n = (uint32_t)(table->rows.size() * (size_t)st.width);   // (< 2^31: check_settings)
+    a.width = st.width; magic_div(st.width, a.width_mul, a.width_shift);
+    a.samples = plan.samples; a.log2_samples = plan.log2_samples; a.seed = plan.seed; a.radius = plan.radius;
+    a.may_exit = ctx->occlusion_may_exit ? 1u : 0u; a.form = (uint32_t)ctx->knob_ao_form;
+    if (launch_ambient_occlusion(a, ctx->has_mesh, hip_stream) != 0) return fail(MI355RT_ERR_HIP, "k_ao launch failed");
+    return MI355RT_OK;
+    });
+}
+
+// Host buffers in, host buffers out: a context on device 0, the scene uploaded, one query, the words copied back.
+int mi355rt_occluded(const mi355rt_scene* scene, const mi355rt_segment* segments, uint32_t n, uint32_t* out) {
+    return guard([&]() -> int {
+    if (!scene) return fail(MI355RT_ERR_INVALID, "occluded: scene is null");
+    if (n && !segments) return fail(MI355RT_ERR_INVALID, "occluded: segments is null");
+    if (n && !out) return fail(MI355RT_ERR_INVALID, "occluded: out is null");
+    if (n == 0) return MI355RT_OK;
+    mi355rt_context* ctx = nullptr;
+    int rc = mi355rt_context_create(0, &ctx); if (rc) return rc;
+    const mi355rt_camera no_camera{}; const mi355rt_settings one_pixel{1, 1, 1, 1};      // set_scene wants a view; the query does not look at it
+    rc = mi355rt_context_set_scene(ctx, scene, &no_camera, &one_pixel);
+    DevBuf<mi355rt_segment> d_seg; DevBuf<uint32_t> d_out;
+    if (!rc) rc = d_seg.ensure(n);
+    if (!rc) rc = d_out.ensure(n);
+    if (!rc && hipMemcpy(d_seg.p, segments, (size_t)n * sizeof(mi355rt_segment), hipMemcpyHostToDevice) != hipSuccess) rc = fail(MI355RT_ERR_HIP, "upload segments");
+    if (!rc) rc = mi355rt_context_occluded(ctx, d_seg.p, n, d_out.p, nullptr);
+    if (!rc && hipMemcpy(out, d_out.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess) rc = fail(MI355RT_ERR_HIP, "copy back words");   // (waits for the query)
+    d_seg.release(); d_out.release();
     std::string keep; keep.swap(last_error());                               // (destroy may overwrite the message of the failure being reported; swap never throws)
     mi355rt_context_destroy(ctx);
     last_error().swap(keep);

@@ -1,6 +1,7 @@
 // rt_prepare.cpp -- scene preparation and the other HIP-free host code of libmi355rt.so (rt_prepare.h): no HIP call, no context.
 // Compiled with the device sources' flags (-ffp-contract=off: cube_normal_table repeats the device's operation order).
 #include "rt_prepare.h"
+#include "rt_occlusion.h"
 
 #include <algorithm>
 #include <cmath>
@@ -88,6 +89,61 @@ int denoise_scratch_bytes(uint32_t width, uint32_t rows, uint64_t* out_bytes) {
     if (int rc = check_denoise_size(width, rows)) return rc;
     *out_bytes = (uint64_t)width * rows * DENOISE_SCRATCH_PER_PIXEL;
     return MI355RT_OK;
+}
+
+static bool misaligned_to(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1u)) != 0u; }
+
+int check_occluded_args(bool have_ctx, bool have_scene, const void* segments, uint32_t n, const void* out) {
+    if (n != 0u) {
+        if (!segments) return fail(MI355RT_ERR_INVALID, "occluded: d_segments is null");
+        if (!out) return fail(MI355RT_ERR_INVALID, "occluded: d_out_u32 is null");
+        if (misaligned_to(segments, 16)) return fail(MI355RT_ERR_INVALID, "occluded: d_segments must be 16-byte aligned");
+        if (misaligned_to(out, 4)) return fail(MI355RT_ERR_INVALID, "occluded: d_out_u32 must be 4-byte aligned");
+    }
+    if (!have_ctx) return fail(MI355RT_ERR_INVALID, "occluded: ctx is null");
+    if (!have_scene) return fail(MI355RT_ERR_INVALID, "occluded: context has no scene");
+    return MI355RT_OK;
+}
+
+int plan_ambient_occlusion(bool have_ctx, bool have_scene, const mi355rt_settings& st, const mi355rt_options* opt, const mi355rt_ao_params* params,
+                           const void* hits, const void* out, RowSel& sel, AoPlan& plan) {
+    const mi355rt_ao_params defaults = {16u, 0u, std::numeric_limits<float>::infinity(), 0u};
+    const mi355rt_ao_params& p = params ? *params : defaults;
+    if (p.samples == 0u || p.samples > 256u || (p.samples & (p.samples - 1u)) != 0u) return fail(MI355RT_ERR_INVALID, "ambient_occlusion: params.samples must be a power of two, 1 .. 256");
+    if (!(p.radius > 0.0f)) return fail(MI355RT_ERR_INVALID, "ambient_occlusion: params.radius must be positive (or +inf), not NaN");
+    if (p._pad != 0u) return fail(MI355RT_ERR_INVALID, "ambient_occlusion: params._pad must be 0");
+    if (opt && opt->abi_version != MI355RT_ABI_VERSION && opt->abi_version != 4u) return fail(MI355RT_ERR_INVALID, "ambient_occlusion: options.abi_version mismatch");
+    if (opt && (opt->flags & ~MI355RT_FLAG_FIXED_AABB) != 0u) return fail(MI355RT_ERR_INVALID, "ambient_occlusion: options.flags has unknown bits");
+    if (!have_ctx) return fail(MI355RT_ERR_INVALID, "ambient_occlusion: ctx is null");
+    if (!have_scene) return fail(MI355RT_ERR_INVALID, "ambient_occlusion: context has no scene");
+    {   mi355rt_options rows_only{};                                 // rng_mode, seed and workspace_bytes are not this call's business
+        if (opt) { rows_only = *opt; rows_only.rng_mode = MI355RT_RNG_CTR; }
+        if (int rc = select_rows(st, opt ? &rows_only : nullptr, sel)) return rc; }
+    if (opt && (opt->flags & MI355RT_FLAG_FIXED_AABB) != 0u)
+        return fail(MI355RT_ERR_UNSUPPORTED, "ambient_occlusion: MI355RT_FLAG_FIXED_AABB is not built for ray queries (they answer as the reference does)");
+    if (!sel.rows.empty()) {
+        if (!hits) return fail(MI355RT_ERR_INVALID, "ambient_occlusion: d_hits is null");
+        if (!out) return fail(MI355RT_ERR_INVALID, "ambient_occlusion: d_out_f32 is null");
+        if (misaligned_to(hits, 16)) return fail(MI355RT_ERR_INVALID, "ambient_occlusion: d_hits must be 16-byte aligned");
+        if (misaligned_to(out, 4)) return fail(MI355RT_ERR_INVALID, "ambient_occlusion: d_out_f32 must be 4-byte aligned");
+    }
+    plan.samples = p.samples; plan.seed = p.seed; plan.radius = p.radius;
+    plan.log2_samples = 0u; while ((1u << plan.log2_samples) < p.samples) ++plan.log2_samples;
+    return MI355RT_OK;
+}
+
+bool scene_within_occlusion_bound(const PreparedScene& s) {
+    const auto inside = [](const float* v, size_t n) { for (size_t k = 0; k < n; ++k) if (!(std::fabs(v[k]) <= OCCLUSION_BOUND)) return false; return true; };
+    for (const DevPrim& p : s.prims) {
+        switch (p.kind) {                                            // the words the hit tests read (rt_device.h, DevPrim::d)
+        case MI355RT_PRIM_SPHERE: if (!inside(p.d, 4)) return false; break;
+        case MI355RT_PRIM_PLANE: if (!inside(p.d, 6)) return false; break;
+        case MI355RT_PRIM_QUAD: if (!inside(p.d, 15)) return false; break;
+        default: if (!inside(p.d, 15) || !inside(p.d + 16, 12)) return false; break;     // cube, mesh: w2o, zd, o2w
+        }
+    }
+    for (const DevTri& t : s.tris) if (!inside(t.v0, 3) || !inside(t.e1, 3) || !inside(t.e2, 3)) return false;
+    return true;
 }
 
 }  // namespace mi355rt

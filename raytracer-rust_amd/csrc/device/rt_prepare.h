@@ -54,6 +54,15 @@ int plan_denoise(uint32_t width, uint32_t rows, const mi355rt_denoise_params* pa
 int check_denoise_buffers(const void* linear_in, const void* hits, const void* scratch, const void* out_linear, const void* out_packed);
 int denoise_scratch_bytes(uint32_t width, uint32_t rows, uint64_t* out_bytes);
 
+// The occlusion queries (mi355rt.h, mi355rt_context_occluded / mi355rt_context_ambient_occlusion): every refusal, decided before any HIP call.
+// What does not depend on the context comes first -- pointers, parameters, the options' version and flags -- then the context and its scene, then what
+// needs the scene's settings: the row selection, MI355RT_FLAG_FIXED_AABB (MI355RT_ERR_UNSUPPORTED) and the buffers of a non-empty selection.
+int check_occluded_args(bool have_ctx, bool have_scene, const void* segments, uint32_t n, const void* out);
+struct AoPlan { uint32_t samples, log2_samples, seed; float radius; };
+// st: the settings of set_scene (read only when have_scene).  sel: the selected rows; empty = nothing to do.
+int plan_ambient_occlusion(bool have_ctx, bool have_scene, const mi355rt_settings& st, const mi355rt_options* options_or_null,
+                           const mi355rt_ao_params* params_or_null, const void* hits, const void* out, RowSel& sel, AoPlan& plan);
+
 // A validated scene in the form the device holds it (rt_device.h), still in host memory, and what the choice of the kernel reads.
 struct PreparedScene {
     // DO NOT REORDER these four, and keep mesh_roots alive with them: they are freed last to first, behind the upload, exactly as build_device_scene's
@@ -71,6 +80,9 @@ struct PreparedScene {
 
 // Validates `sc` and builds `out` from it; MI355RT_ERR_INVALID (and the text) for anything a kernel could not be launched on.
 int prepare_scene(const mi355rt_scene* sc, PreparedScene& out);
+// Every number the hit tests read from the scene -- the primitive records' test words, the triangles' vertices and edges -- is inside
+// +-OCCLUSION_BOUND (rt_occlusion.h; NaN is outside): the condition under which the occlusion kernels may leave the list early.
+bool scene_within_occlusion_bound(const PreparedScene& s);
 // The counter-mode kernel (KERNEL_* of rt_device.h) that serves the scene.  forced_variant: the diagnostic knob "kernel", -1 = none;
 // built_mask: bit v = this library holds variant v (rt_kernels.hip, render_ctr_variant_built).
 uint32_t choose_variant(const PreparedScene& s, int forced_variant, uint32_t built_mask);

@@ -18,7 +18,8 @@ EXPORTS = ["mi355rt_render", "mi355rt_render_multi", "mi355rt_render_progressive
            "mi355rt_multi_context_create", "mi355rt_multi_context_destroy", "mi355rt_multi_context_set_scene", "mi355rt_multi_context_render",
            "mi355rt_multi_context_check", "mi355rt_multi_context_render_progressive", "mi355rt_render_progressive_multi",
            "mi355rt_context_trace_rays", "mi355rt_context_first_hits", "mi355rt_trace_rays",
-           "mi355rt_denoise_scratch_bytes", "mi355rt_context_denoise", "mi355rt_denoise"]
+           "mi355rt_denoise_scratch_bytes", "mi355rt_context_denoise", "mi355rt_denoise",
+           "mi355rt_context_occluded", "mi355rt_occluded", "mi355rt_context_ambient_occlusion"]
 
 _lib = None
 _extra = {}
@@ -184,6 +185,12 @@ def _bind(so):
                                               C.c_void_p, C.c_void_p, C.c_void_p]
         L.mi355rt_denoise.restype = C.c_int
         L.mi355rt_denoise.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(abi.DenoiseParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.mi355rt_context_occluded.restype = C.c_int
+        L.mi355rt_context_occluded.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+        L.mi355rt_occluded.restype = C.c_int
+        L.mi355rt_occluded.argtypes = [C.POINTER(abi.Scene), C.c_void_p, C.c_uint32, C.c_void_p]
+        L.mi355rt_context_ambient_occlusion.restype = C.c_int
+        L.mi355rt_context_ambient_occlusion.argtypes = [C.c_void_p, C.POINTER(abi.Options), C.POINTER(abi.AoParams), C.c_void_p, C.c_void_p, C.c_void_p]
         L.mi355rt_debug_multi_part_ms.restype = C.c_int
         L.mi355rt_debug_multi_part_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_uint32, C.POINTER(C.c_uint32)]
         L.mi355rt_debug_set_knob.restype = C.c_int
@@ -214,7 +221,7 @@ def _check(rc, what, library=None):
 
 def set_knob(name, value, library=None):
     """Diagnostic: process-wide default knob for every context created afterwards (also inside the one-shot calls).
-    Knobs: kernel, guided_mult, spin_idle, spin_entry, wave_times, row_order, cam_cull, inline_steps, trav_min (rt_api.cpp)."""
+    Knobs: kernel, guided_mult, spin_idle, spin_entry, wave_times, row_order, cam_cull, denoise_staged, ao_form, inline_steps, trav_min (rt_api.cpp)."""
     L = library or lib()
     _check(L.mi355rt_debug_set_knob(None, name.encode(), int(value)), f"mi355rt_debug_set_knob({name})", L)
 
@@ -339,6 +346,19 @@ def trace_rays(scene, rays, library=None):
     hits = np.zeros(rays.size, abi.HIT_DTYPE)
     _check(L.mi355rt_trace_rays(C.byref(sc), C.c_void_p(rays.ctypes.data), rays.size, C.c_void_p(hits.ctypes.data)), "mi355rt_trace_rays", L)
     return hits
+
+
+def occluded(scene, segments, library=None):
+    """One-shot mi355rt_occluded with host buffers: 1 where the closest hit of a segment's ray lies strictly below its t_max, else 0.  segments: a
+    numpy array of abi.SEGMENT_DTYPE (or float32 [n, 8]: origin, pad, direction, t_max; the directions need not be unit).  Returns uint32 [n]."""
+    L = library or lib()
+    sc = getattr(scene, "c", scene)
+    segments = np.ascontiguousarray(segments)
+    if segments.dtype != abi.SEGMENT_DTYPE:
+        segments = np.ascontiguousarray(segments, np.float32).reshape(-1, 8).view(abi.SEGMENT_DTYPE).reshape(-1)
+    out = np.zeros(segments.size, np.uint32)
+    _check(L.mi355rt_occluded(C.byref(sc), C.c_void_p(segments.ctypes.data), segments.size, C.c_void_p(out.ctypes.data)), "mi355rt_occluded", L)
+    return out
 
 
 def denoise_scratch_bytes(width, rows, library=None):
@@ -472,6 +492,20 @@ class Context:
         d_hits: device address of rows_selected(options) * width abi.Hit records, row-major over the selected rows."""
         _check(self._L.mi355rt_context_first_hits(self._h, C.byref(options) if options is not None else None, C.c_void_p(d_hits) if d_hits else None,
                                                   C.c_void_p(stream) if stream else None), "mi355rt_context_first_hits", self._L)
+
+    def occluded(self, d_segments, n, d_out, stream=None):
+        """mi355rt_context_occluded: for n segments of the resident scene, 1 where the closest hit lies strictly below t_max, else 0, enqueued on
+        `stream`.  d_segments: integer device address (16-byte aligned) of n abi.Segment records; d_out: n uint32 words, every one written."""
+        _check(self._L.mi355rt_context_occluded(self._h, C.c_void_p(d_segments) if d_segments else None, int(n), C.c_void_p(d_out) if d_out else None,
+                                                C.c_void_p(stream) if stream else None), "mi355rt_context_occluded", self._L)
+
+    def ambient_occlusion(self, d_hits, d_out, params=None, options=None, stream=None):
+        """mi355rt_context_ambient_occlusion: one float per selected pixel, 1 - (occluded samples) / samples around the pixel's first hit.  d_hits:
+        what first_hits wrote for the same options; d_out: rows_selected(options) * width floats; params: abi.AoParams or None for the defaults."""
+        _check(self._L.mi355rt_context_ambient_occlusion(self._h, C.byref(options) if options is not None else None,
+                                                         C.byref(params) if params is not None else None, C.c_void_p(d_hits) if d_hits else None,
+                                                         C.c_void_p(d_out) if d_out else None, C.c_void_p(stream) if stream else None),
+               "mi355rt_context_ambient_occlusion", self._L)
 
     def denoise(self, width, rows, d_linear_in, d_hits, d_scratch, d_out_linear=None, d_out_packed=None, params=None, stream=None):
         """mi355rt_context_denoise: the a-trous filter of mi355rt.h over a contiguous window of rows x width pixels, enqueued on `stream`.  Integer
