@@ -78,7 +78,7 @@ def _code_only(text):
 
 def kernel_hash():
     """sha256 over everything that decides the device code AND how it is launched: the kernel source, every header of csrc/device, the
-    host half (rt_api.cpp: grid size, shard size, guided_div; rt_prepare.cpp: the scene records, the choice of the kernel variant) and the hipcc flags -- the CODE of those
+    host half (rt_api.cpp: the launches; rt_prepare.cpp: the scene records, the choice of the kernel variant, the plan of a render -- grid size, shard size, guided_div) and the hipcc flags -- the CODE of those
     files: comments and whitespace are stripped first, so that correcting a comment does not orphan the committed counters.
     profiles/pmc_counters.json records it, and bench.py refuses counters taken on another library."""
     import hashlib

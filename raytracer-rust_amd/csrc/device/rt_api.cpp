@@ -3,7 +3,8 @@
 // Replaces `render_scene(&scene, &camera, &render_settings) -> Vec<u32>` (src/renderer.rs:67,
 // called from src/main.rs:57).  There is NO CPU fallback in this library: without a HIP device every
 // render entry point returns MI355RT_ERR_NO_DEVICE.  What happens to a scene before a device is involved -- validation, the BVH re-lay, the
-// primitive records, the choice of the kernel variant -- is rt_prepare.cpp, which has no HIP in it; this file uploads and launches.
+// primitive records, the choice of the kernel variant -- and what a render call launches -- its refusals, the variant, the bands and their grids -- is
+// rt_prepare.cpp, which has no HIP in it; this file uploads and launches.
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -27,42 +28,6 @@
 #include "rt_occlusion.h"
 
 using namespace mi355rt;
-
-namespace {
-
-// The three row tables of one selection, n entries each: [0, n) natural = absolute y of local output row j; [n, 2n) processing = absolute y
-// of the row processed jp-th; [2n, 3n) out_row = the local output row that processing row jp is.  `cost` (per absolute image row, may be
-// empty) orders the processing: rows sorted by decreasing cost (stable: equal costs keep image order) and dealt round-robin over `groups`
-// consecutive ranges -- the launch's work shards (x bands) -- so that every range runs from its dearest rows to its cheapest.
-void row_tables(const std::vector<uint32_t>& rows, const std::vector<float>& cost, uint32_t groups, std::vector<uint32_t>& out) {
-    const size_t n = rows.size();
-    out.resize(3 * n);
-    std::vector<uint32_t> sorted(n);
-    for (size_t j = 0; j < n; ++j) sorted[j] = (uint32_t)j;
-    if (!cost.empty())
-        std::stable_sort(sorted.begin(), sorted.end(), [&](uint32_t a, uint32_t b) {
-            const float ca = rows[a] < cost.size() ? cost[rows[a]] : 0.f, cb = rows[b] < cost.size() ? cost[rows[b]] : 0.f;
-            return ca > cb; });
-    groups = std::max(1u, std::min<uint32_t>(groups, (uint32_t)std::max<size_t>(n, 1)));
-    size_t jp = 0;
-    for (uint32_t g = 0; g < groups && !cost.empty(); ++g)
-        for (size_t k = g; k < n; k += groups, ++jp) { out[n + jp] = rows[sorted[k]]; out[2 * n + jp] = sorted[k]; }
-    for (size_t j = 0; j < n; ++j) {
-        out[j] = rows[j];
-        if (cost.empty()) { out[n + j] = rows[j]; out[2 * n + j] = (uint32_t)j; }
-    }
-}
-
-// q = n / d for every n < 2^31 as umulhi(n, mul) >> shift (mul == 0 encodes d == 1).  s = ceil(log2 d),
-// mul = ceil(2^(31+s) / d) < 2^32, shift = s - 1.
-void magic_div(uint32_t d, uint32_t& mul, uint32_t& shift) {
-    if (d <= 1) { mul = 0; shift = 0; return; }
-    uint32_t s = 0; while ((1ull << s) < d) ++s;
-    const unsigned __int128 num = (unsigned __int128)1 << (31 + s);
-    mul = (uint32_t)((num + d - 1) / d); shift = s - 1;
-}
-
-}  // namespace
 
 struct mi355rt_context;
 static int report_device_error(mi355rt_context* ctx, bool this_render = false);
@@ -91,7 +56,7 @@ struct mi355rt_context {
     DevBuf<DevTexture> textures; DevBuf<uint32_t> texels;  // MI355RT_MAT_TEXTURE images: table + all texels in one buffer
     DevBuf<unsigned long long> wave_times; uint32_t wave_times_n = 0;   // diagnostics (MI355RT_WAVE_TIMES=1)
     std::vector<uint32_t> rows_host;     // the selected rows (absolute y, ascending = the order of the output buffer)
-    std::vector<uint32_t> tables_host;   // source of the async upload of the three row tables (row_tables()); must outlive the copy
+    std::vector<uint32_t> tables_host;   // source of the async upload of the three row tables (rt_prepare.h row_tables()); must outlive the copy
     // Camera masks (rt_prepare.h build_camera_masks; k_render_ctr_simple_qc's camera pass).  cam_mask_abs: the table of the scene, the camera and the
     // settings of set_scene, one word per pixel of the image (empty: none -- another kernel, more than 32 primitives, or the knob); cam_mask_host: its rows
     // in the processing order of rows_host, rebuilt with the row tables and uploaded behind them into `rows` (same lifetime as tables_host); empty: the
@@ -416,7 +381,9 @@ int mi355rt_context_set_scene(mi355rt_context* ctx, const mi355rt_scene* scene, 
     });
 }
 
-// Samples [s0, s1) of every selected pixel.  The classic call is (0, settings.spp, no accumulator).
+// Samples [s0, s1) of every selected pixel.  The classic call is (0, settings.spp, no accumulator).  What is launched -- every refusal, the variant,
+// the bands, each band's grid -- is plan_render's (rt_prepare.cpp, no HIP); this function enqueues it.  A refused call has touched neither the
+// stream nor the context's row tables.
 // d_row_counters (set_scene's row-cost probe only): one launch per selected ROW, each with its own block of device counters ({paths, rays, ...})
 // at d_row_counters + STATS_WORDS * row, nothing resolved, nothing waited for.
 static int render_samples(mi355rt_context* ctx, const mi355rt_options* opt, uint32_t s0, uint32_t s1, void* d_accum,
@@ -425,42 +392,30 @@ static int render_samples(mi355rt_context* ctx, const mi355rt_options* opt, uint
     if (!d_out_packed) return fail(MI355RT_ERR_INVALID, "d_out_packed is null");
     HIP_TRY(hipSetDevice(ctx->device));
     if (int erc = report_device_error(ctx)) return erc;              // an earlier asynchronous render on this context failed (no wait: what has finished so far)
-    hipStream_t stream = (hipStream_t)hip_stream;
     const mi355rt_settings& st = ctx->settings;
-    RowSel sel; int rc = select_rows(st, opt, sel); if (rc) return rc;
+    uint32_t block_slots[KERNEL_VARIANTS];
+    for (uint32_t v = 0; v < KERNEL_VARIANTS; ++v) block_slots[v] = (uint32_t)(ctx->cu_count * ctx->blocks_per_cu[v]);
+    const RenderPlanIn in{&st, opt, s0, s1, d_accum != nullptr, ctx->variant, ctx->has_mesh, ctx->n_prims, !ctx->row_cost.empty(), d_row_counters != nullptr,
+                          block_slots, ctx->grid_div, ctx->guided_mult};
+    RowSel sel; RenderPlan plan;
+    int rc = plan_render(in, sel, plan); if (rc) return rc;
+
+    hipStream_t stream = (hipStream_t)hip_stream;
     if (ctx->have_last && ctx->last_stream != stream) HIP_TRY(hipStreamWaitEvent(stream, ctx->done, 0));   // the previous render owned the workspaces
-    const uint32_t rng_mode = opt ? opt->rng_mode : (uint32_t)MI355RT_RNG_CTR;
-    // How many consecutive ranges the processing order is dealt over: the work shards of every band this launch will be cut into.
-    uint32_t groups = WORK_SHARDS;
-    {   const uint64_t spp_now = std::max<uint64_t>(1, (uint64_t)s1 - s0), pixels = (uint64_t)sel.rows.size() * st.width;
-        const uint64_t ws = (opt && opt->workspace_bytes) ? opt->workspace_bytes : (32ull << 30);
-        const uint64_t cap = std::max<uint64_t>(1, std::min<uint64_t>(ws / 12, (1ull << 31) - 16 * RUN_LIMIT) / spp_now);
-        const uint64_t band_pixels = std::max<uint64_t>(1, std::min(cap, pixels));                       // (the band plan below arrives at the same figure)
-        groups *= (uint32_t)std::min<uint64_t>(64, std::max<uint64_t>(1, (pixels + band_pixels - 1) / band_pixels)); }
-    if (ctx->row_cost.empty() || rng_mode != MI355RT_RNG_CTR) groups = 0;                  // natural order
-    const bool same_rows = ctx->rows_valid && sel.rows == ctx->rows_host && groups == ctx->order_groups;
+    const bool same_rows = ctx->rows_valid && sel.rows == ctx->rows_host && plan.order_groups == ctx->order_groups;
     if (!same_rows) {
         if (ctx->have_last) HIP_TRY(hipEventSynchronize(ctx->done));   // a previous call's row-table upload may still read tables_host
         ctx->rows_host.swap(sel.rows);
         static const std::vector<float> no_cost;
-        row_tables(ctx->rows_host, groups ? ctx->row_cost : no_cost, groups, ctx->tables_host);
+        row_tables(ctx->rows_host, plan.order_groups ? ctx->row_cost : no_cost, plan.order_groups, ctx->tables_host);
         // the camera masks of these rows, in processing order (set_scene's probes render with other settings: the table is not theirs)
         ctx->cam_mask_host.clear();
         if (!ctx->cam_mask_abs.empty() && ctx->cam_mask_w == st.width && ctx->cam_mask_h == st.height)
             gather_camera_masks(ctx->cam_mask_abs, st.width, ctx->tables_host.data() + ctx->rows_host.size(), ctx->rows_host.size(), ctx->cam_mask_host);
-        ctx->order_groups = groups;
+        ctx->order_groups = plan.order_groups;
         ctx->rows_valid = false;
     }
-    const bool fixed_aabb = opt && (opt->flags & MI355RT_FLAG_FIXED_AABB) != 0u;
-    if (opt && (opt->flags & ~MI355RT_FLAG_FIXED_AABB) != 0u) return fail(MI355RT_ERR_INVALID, "options.flags has unknown bits");
-    if (fixed_aabb && rng_mode != MI355RT_RNG_CTR) return fail(MI355RT_ERR_INVALID, "MI355RT_FLAG_FIXED_AABB needs MI355RT_RNG_CTR (the replay mode reproduces the reference as it is)");
-    uint32_t variant = ctx->variant;
-    if (fixed_aabb && ctx->has_mesh) variant = VARIANT_TABLE[variant].fixed_aabb;     // without a mesh the flag changes nothing
-    // The mesh-free lockstep kernels are compiled under the assumption that the list holds something and that a path may take a step (rt_kernels.hip,
-    // render_ctr_lockstep); the two degenerate renders -- every sample is the miss colour / BLACK -- go to the plain per-lane loop, which assumes nothing.
-    if ((ctx->n_prims == 0 || st.max_depth == 0) && VARIANT_TABLE[variant].family == FAMILY_LOCKSTEP && !(VARIANT_TABLE[variant].prims & (1u << MI355RT_PRIM_MESH)))
-        variant = KERNEL_LOCKSTEP_MESH;
-    const uint64_t seed = opt ? opt->seed : 0;
+    const uint32_t variant = plan.variant;
     const uint32_t n_rows = (uint32_t)ctx->rows_host.size();
     if (stats) { std::memset(stats, 0, sizeof *stats); stats->rows_rendered = n_rows; stats->kernel_vgprs = (uint32_t)ctx->vgprs[variant]; stats->kernel_sgprs = (uint32_t)ctx->sgprs; }
     if (n_rows == 0) return MI355RT_OK;
@@ -479,11 +434,9 @@ static int render_samples(mi355rt_context* ctx, const mi355rt_options* opt, uint
     HIP_TRY(hipMemsetAsync(ctx->stats.p, 0, STATS_WORDS * sizeof(unsigned long long), stream));
 
     double render_ms = 0, resolve_ms = 0, total_ms = 0;
-    uint32_t n_bands = 0, grid_blocks = 0, block_threads = 0;
+    uint32_t grid_blocks = 0;
 
-    if (rng_mode == MI355RT_RNG_REF) {
-        if (d_accum || s0 != 0 || s1 != st.samples_per_pixel)
-            return fail(MI355RT_ERR_INVALID, "progressive rendering needs MI355RT_RNG_CTR (the reference stream of a row is sequential over its pixels)");
+    if (plan.rng_mode == MI355RT_RNG_REF) {
         if ((rc = ctx->fold_stack.ensure((size_t)n_rows * std::max(st.max_depth, 1u) * 3))) return rc;
         RefParams rp{};
         rp.prims = ctx->prims.p; rp.mats = ctx->mats.p; rp.nodes = ctx->nodes.p; rp.tris = ctx->tris.p; rp.rows = d_rows_natural;
@@ -492,7 +445,7 @@ static int render_samples(mi355rt_context* ctx, const mi355rt_options* opt, uint
         rp.n_prims = ctx->n_prims; rp.n_mats = ctx->n_mats; rp.n_rows = n_rows;
         std::memcpy(rp.miss, ctx->miss, 12); rp.cam = ctx->cam;
         rp.width = st.width; rp.height = st.height; rp.spp = st.samples_per_pixel; rp.max_depth = st.max_depth;
-        rp.seed_lo = (uint32_t)seed; rp.seed_hi = (uint32_t)(seed >> 32);
+        rp.seed_lo = plan.seed_lo; rp.seed_hi = plan.seed_hi;
         if (stats) HIP_TRY(hipEventRecord(ctx->ev[0], stream));
         if (launch_render_ref(rp, stream) != 0) return fail(MI355RT_ERR_HIP, "k_render_ref launch failed");
         if (stats) {
@@ -501,30 +454,19 @@ static int render_samples(mi355rt_context* ctx, const mi355rt_options* opt, uint
             float ms = 0; HIP_TRY(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
             render_ms = total_ms = ms;
         }
-        n_bands = 1; grid_blocks = n_rows; block_threads = 64;
+        grid_blocks = n_rows;
     } else {
-        // ---- band plan: the radiance workspace holds band_pixels * spp float4 ----
-        const uint64_t spp = s1 - s0;                                 // samples per pixel in THIS launch
-        const uint64_t total_pixels = (uint64_t)n_rows * st.width;
-        uint64_t ws_cap = (opt && opt->workspace_bytes) ? opt->workspace_bytes : (32ull << 30);   // 288 GB of HBM: default = the 2^31-sample band limit; only what a band needs is allocated
-        uint64_t max_samples = std::min<uint64_t>(ws_cap / 12, (1ull << 31) - 16 * RUN_LIMIT);     // the shard counters overshoot by at most one run per claiming wave's last try; 32-bit headroom
-        if (max_samples < spp) return fail(MI355RT_ERR_INVALID, "workspace_bytes too small for one pixel (needs spp * 12 bytes)");
-        uint64_t band_pixels_max = std::min<uint64_t>(max_samples / spp, total_pixels);
-        if (d_row_counters) band_pixels_max = st.width;                  // the probe: a band = a row
         // Only what a band needs is allocated.  When even that does not fit (another tenant on the GPU, a small device),
         // halve the band and try again: more, smaller bands give the same image (tiling invariance), just more launches.
         for (;;) {
-            rc = ctx->radiance.ensure((size_t)(band_pixels_max * spp * 3));
-            // (the row probe's counter blocks are laid out one per ROW = per band: halving would make more bands than blocks -- it returns the OOM)
-            if (rc != MI355RT_ERR_OOM || band_pixels_max <= 1 || d_row_counters) break;
+            rc = ctx->radiance.ensure((size_t)(plan.band_pixels * plan.spp * 3));
+            if (rc != MI355RT_ERR_OOM || !halve_bands(plan)) break;
             (void)hipGetLastError();
-            band_pixels_max = (band_pixels_max + 1) / 2;
         }
         if (rc) return rc;
-        n_bands = (uint32_t)((total_pixels + band_pixels_max - 1) / band_pixels_max);
         const size_t ctr_words = (size_t)WORK_SHARDS * WORK_SHARD_STRIDE;            // per band
-        if ((rc = ctx->counters.ensure((size_t)n_bands * ctr_words))) return rc;
-        HIP_TRY(hipMemsetAsync(ctx->counters.p, 0, (size_t)n_bands * ctr_words * sizeof(uint32_t), stream));
+        if ((rc = ctx->counters.ensure((size_t)plan.n_bands * ctr_words))) return rc;
+        HIP_TRY(hipMemsetAsync(ctx->counters.p, 0, (size_t)plan.n_bands * ctr_words * sizeof(uint32_t), stream));
 
         RenderParams p{};
         p.prims = ctx->prims.p; p.mats = ctx->mats.p; p.nodes = ctx->nodes.p; p.tris = ctx->tris.p; p.rows = d_rows_processing;
@@ -532,11 +474,10 @@ static int render_samples(mi355rt_context* ctx, const mi355rt_options* opt, uint
         p.radiance = ctx->radiance.p; p.stats = ctx->stats.p;
         p.n_prims = ctx->n_prims; p.n_mats = ctx->n_mats;
         std::memcpy(p.miss, ctx->miss, 12); p.cam = ctx->cam;
-        p.width = st.width; p.height = st.height; p.spp = (uint32_t)spp; p.max_depth = st.max_depth;
-        p.width_f = (float)st.width; p.height_f = (float)st.height;                       // exact: both below 2^24
-        { volatile float one = 1.0f; p.inv_width_rn = one / p.width_f; p.inv_height_rn = one / p.height_f; }   // IEEE division on the host = RN(1/x), what recip_normal_range() returns on the device
-        p.seed_lo = (uint32_t)seed; p.seed_hi = (uint32_t)(seed >> 32); p.sample0 = s0;
-        magic_div((uint32_t)spp, p.spp_mul, p.spp_shift); magic_div(st.width, p.width_mul, p.width_shift);
+        p.width = st.width; p.height = st.height; p.spp = plan.spp; p.max_depth = st.max_depth;
+        p.width_f = plan.width_f; p.height_f = plan.height_f; p.inv_width_rn = plan.inv_width_rn; p.inv_height_rn = plan.inv_height_rn;
+        p.seed_lo = plan.seed_lo; p.seed_hi = plan.seed_hi; p.sample0 = plan.sample0;
+        p.spp_mul = plan.spp_mul; p.spp_shift = plan.spp_shift; p.width_mul = plan.width_mul; p.width_shift = plan.width_shift;
         p.trav_min = ctx->trav_min; p.inline_steps = ctx->inline_steps;
         p.lds_nodes = (uint32_t)std::min<size_t>(ctx->n_nodes, LDS_NODE_CAP);    // (the wavefront kernel clamps to its own WF_LDS_NODES)
         p.err = ctx->errword.p; p.spin_limit_idle = ctx->spin_limit_idle; p.spin_limit_entry = ctx->spin_limit_entry;
@@ -544,43 +485,28 @@ static int render_samples(mi355rt_context* ctx, const mi355rt_options* opt, uint
         p.cam_mask_off = (variant == KERNEL_LOCKSTEP_SIMPLE_QC && ctx->cam_mask_host.size() == (size_t)n_rows * st.width) ? 2u * n_rows : 0u;
         ResolveParams r{};
         r.radiance = ctx->radiance.p; r.out_packed = (uint32_t*)d_out_packed; r.out_linear = (float*)d_out_linear;
-        r.spp = (uint32_t)spp; r.inv_spp = 1.0f / (float)s1;                             // renderer.rs:85
-        r.accum = (float*)d_accum; r.accum_load = s0 != 0 ? 1u : 0u;
-        r.out_row = d_out_row; r.width = st.width; r.width_mul = p.width_mul; r.width_shift = p.width_shift;
-        // What fills the device, or this context's share of it: with F frames in flight (F contexts, F streams) each launch takes 1 / F of the wave slots,
-        // F launches are co-resident, and a frame whose last paths are draining shares every SIMD with frames in their steady state.  A full-size grid
-        // leaves the next frame's workgroups waiting for the draining frame's to retire one by one ("tail").
-        const uint32_t resident = std::max(1u, (uint32_t)(ctx->cu_count * ctx->blocks_per_cu[variant]) / ctx->grid_div);
-        block_threads = VARIANT_TABLE[variant].block_threads;
-        std::vector<float> band_ms;
-        for (uint32_t b = 0; b < n_bands; ++b) {
-            const uint64_t p0 = (uint64_t)b * band_pixels_max;
-            const uint64_t np = std::min<uint64_t>(band_pixels_max, total_pixels - p0);
-            p.band_pixel0 = (uint32_t)p0; p.band_samples = (uint32_t)(np * spp);
+        r.spp = plan.spp; r.inv_spp = plan.inv_spp;
+        r.accum = (float*)d_accum; r.accum_load = plan.accum_load;
+        r.out_row = d_out_row; r.width = st.width; r.width_mul = plan.width_mul; r.width_shift = plan.width_shift;
+        for (uint32_t b = 0; b < plan.n_bands; ++b) {
+            const RenderBand band = render_band(plan, b);
+            p.band_pixel0 = band.band_pixel0; p.band_samples = band.band_samples; p.shard_samples = band.shard_samples; p.guided_div = band.guided_div;
             p.batch_counter = ctx->counters.p + (size_t)b * ctr_words;
             if (d_row_counters) p.stats = d_row_counters + STATS_WORDS * (size_t)b;   // (a whole counter block per row: diagnostic builds write all of it)
-            const bool wf = VARIANT_TABLE[variant].family == FAMILY_WAVEFRONT;
-            const uint32_t run_min = wf ? RUN_WAVEFRONT_MIN : BATCH_MIN, run_max = wf ? RUN_WAVEFRONT : BATCH_MAX;   // what the kernel's WorkCursorT is compiled with
-            p.shard_samples = (p.band_samples + WORK_SHARDS - 1) / WORK_SHARDS;
-            p.shard_samples = (p.shard_samples + run_max - 1) / run_max * run_max;           // shards begin on run boundaries (fixed runs then stay aligned)
-            const uint32_t waves_per_block = block_threads / 64;
-            const uint32_t min_runs = (p.band_samples + run_min - 1) / run_min;               // never more waves than minimum-size runs
-            const uint32_t grid = std::max(1u, std::min(resident, (min_runs + waves_per_block - 1) / waves_per_block));
-            p.guided_div = std::max(1u, ctx->guided_mult * grid * waves_per_block / WORK_SHARDS);
             p.wave_times = nullptr;
             if (ctx->want_wave_times) {
-                ctx->wave_times_n = grid * waves_per_block;
+                ctx->wave_times_n = band.grid * (plan.block_threads / 64);
                 if ((rc = ctx->wave_times.ensure((size_t)ctx->wave_times_n * WAVE_TIME_WORDS))) return rc;
                 HIP_TRY(hipMemsetAsync(ctx->wave_times.p, 0, (size_t)ctx->wave_times_n * WAVE_TIME_WORDS * 8, stream));
                 p.wave_times = ctx->wave_times.p;
             }
-            grid_blocks = std::max(grid_blocks, grid);
-            r.band_pixel0 = (uint32_t)p0; r.band_pixels = (uint32_t)np;
+            grid_blocks = std::max(grid_blocks, band.grid);
+            r.band_pixel0 = band.band_pixel0; r.band_pixels = band.band_pixels;
             hipEvent_t pe0 = nullptr, pe1 = nullptr, pe2 = nullptr;
             if (ctx->timing && !stats) { pe0 = ctx->pool_get(); pe1 = ctx->pool_get(); pe2 = ctx->pool_get(); if (!pe0 || !pe1 || !pe2) return fail(MI355RT_ERR_HIP, "event pool"); }
             if (stats) HIP_TRY(hipEventRecord(ctx->ev[0], stream));
             if (pe0) HIP_TRY(hipEventRecord(pe0, stream));
-            if (launch_render_ctr(p, variant, grid, stream) != 0) return fail(MI355RT_ERR_HIP, "k_render_ctr launch failed");
+            if (launch_render_ctr(p, variant, band.grid, stream) != 0) return fail(MI355RT_ERR_HIP, "k_render_ctr launch failed");
             ctx->launched_variants |= 1u << variant;
             if (stats) HIP_TRY(hipEventRecord(ctx->ev[1], stream));
             if (pe1) HIP_TRY(hipEventRecord(pe1, stream));
@@ -607,7 +533,7 @@ static int render_samples(mi355rt_context* ctx, const mi355rt_options* opt, uint
         if (int erc = report_device_error(ctx, true)) return erc;    // a wave of THIS render gave up: the image is incomplete
         stats->render_kernel_ms = render_ms; stats->resolve_kernel_ms = resolve_ms; stats->total_ms = total_ms;
         stats->samples = h[0]; stats->rays = h[1];
-        stats->bands = n_bands; stats->grid_blocks = grid_blocks; stats->block_threads = block_threads;
+        stats->bands = plan.n_bands; stats->grid_blocks = grid_blocks; stats->block_threads = plan.block_threads;
     }
     return MI355RT_OK;
 }
@@ -921,6 +847,46 @@ int mi355rt_debug_camera_masks(const mi355rt_scene* scene, const mi355rt_camera*
     });
 }
 
+// Diagnostic hook (not part of the public header): what a render with these inputs would launch, without a device -- no HIP call, no context -- by the
+// plan_render, halve_bands, render_band and row_tables that render_samples calls.  args: the context's side of RenderPlanIn (device.PlanProbeArgs has
+// the same layout); row_cost: a per-image-row cost of the caller's (n_cost entries, 0 = none: image order).  `halvings` "the band did not fit" steps
+// are taken first; *halved = how many of them existed.  out_plan: a RenderPlan.  Two calls, as mi355rt_debug_prepare_scene: with bands / tables null
+// it only counts (*n_bands RenderBand records, 3 x *n_rows table entries); with an array given, its n_* holds the capacity on entry.
+struct PlanProbeArgs { uint32_t s0, s1, have_accum, variant, has_mesh, n_prims, row_probe, grid_div, guided_mult, block_slots[KERNEL_VARIANTS]; };
+int mi355rt_debug_plan_render(const mi355rt_settings* settings, const mi355rt_options* options, const void* args, const float* row_cost, uint32_t n_cost,
+                              uint32_t halvings, void* out_plan, uint32_t* halved, void* bands, uint32_t* n_bands, uint32_t* tables, uint32_t* n_rows) {
+    return guard([&]() -> int {
+    if (!args || !out_plan || !halved || !n_bands || !n_rows || (n_cost && !row_cost)) return fail(MI355RT_ERR_INVALID, "debug_plan_render: null");
+    int rc = check_settings(settings); if (rc) return rc;
+    const PlanProbeArgs a = *static_cast<const PlanProbeArgs*>(args);
+    if (a.variant >= KERNEL_VARIANTS) return fail(MI355RT_ERR_INVALID, "knob kernel");
+    if (a.s1 <= a.s0) return fail(MI355RT_ERR_INVALID, "sample_end must be greater than sample_begin");
+    if (a.grid_div < 1u || a.grid_div > 16u) return fail(MI355RT_ERR_INVALID, "share_of must be 1 .. 16");
+    if (a.guided_mult < 1u || a.guided_mult > 64u) return fail(MI355RT_ERR_INVALID, "knob guided_mult");
+    const RenderPlanIn in{settings, options, a.s0, a.s1, a.have_accum != 0u, a.variant, a.has_mesh != 0u, a.n_prims, n_cost != 0u, a.row_probe != 0u,
+                          a.block_slots, a.grid_div, a.guided_mult};
+    RowSel sel; RenderPlan plan;
+    rc = plan_render(in, sel, plan); if (rc) return rc;
+    for (*halved = 0; *halved < halvings && halve_bands(plan); ) ++*halved;
+    const bool counter_mode = plan.rng_mode == MI355RT_RNG_CTR;      // (the replay mode's one launch has no band record)
+    if (bands && counter_mode && plan.n_bands) {
+        if (*n_bands < plan.n_bands) return fail(MI355RT_ERR_INVALID, "debug_plan_render: capacity");
+        if (plan.block_threads == 0u) return fail(MI355RT_ERR_INVALID, "debug_plan_render: a retired variant has no launch");
+        for (uint32_t b = 0; b < plan.n_bands; ++b) static_cast<RenderBand*>(bands)[b] = render_band(plan, b);
+    }
+    *n_bands = counter_mode ? plan.n_bands : 0u;
+    if (tables) {
+        if (*n_rows < sel.rows.size()) return fail(MI355RT_ERR_INVALID, "debug_plan_render: capacity");
+        std::vector<uint32_t> t;
+        row_tables(sel.rows, plan.order_groups ? std::vector<float>(row_cost, row_cost + n_cost) : std::vector<float>(), plan.order_groups, t);
+        if (!t.empty()) std::memcpy(tables, t.data(), t.size() * sizeof(uint32_t));
+    }
+    *n_rows = (uint32_t)sel.rows.size();
+    std::memcpy(out_plan, &plan, sizeof plan);
+    return MI355RT_OK;
+    });
+}
+
 // Diagnostic hook (not part of the public header): the STATS_WORDS (40) raw device counters of the last render.
 int mi355rt_debug_read_counters(mi355rt_context* ctx, unsigned long long* out40) {
     return guard([&]() -> int {
@@ -932,7 +898,7 @@ int mi355rt_debug_read_counters(mi355rt_context* ctx, unsigned long long* out40)
 }
 
 // Diagnostic hook (not part of the public header): the row tables of the last render on this context -- 3 x n entries (natural, processing,
-// out_row; see row_tables()) -- and the per-image-row cost the processing order was built from (`cost`, `height` entries; may be null).
+// out_row; see rt_prepare.h row_tables()) -- and the per-image-row cost the processing order was built from (`cost`, `height` entries; may be null).
 int mi355rt_debug_read_row_tables(mi355rt_context* ctx, uint32_t* tables, uint32_t capacity_entries, uint32_t* n_rows, float* cost, uint32_t cost_capacity, uint32_t* n_cost) {
     return guard([&]() -> int {
     if (!ctx || !n_rows) return fail(MI355RT_ERR_INVALID, "null");

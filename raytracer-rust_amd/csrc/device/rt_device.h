@@ -151,7 +151,7 @@ struct ResolveParams {
     uint32_t accum_load;         // 1: start from accum[] (samples before this launch), 0: start from zero
     uint32_t band_pixel0, band_pixels, spp;
     float inv_spp;               // 1 / (samples accumulated so far including this launch)
-    const uint32_t* out_row;     // processing row -> local output row (rt_api.cpp row_tables()); null: the band's pixels are in output order
+    const uint32_t* out_row;     // processing row -> local output row (rt_prepare.cpp row_tables()); null: the band's pixels are in output order
     uint32_t width, width_mul, width_shift;   // image width and its magic pair (pixel -> processing row)
 };
 

@@ -132,6 +132,104 @@ int plan_ambient_occlusion(bool have_ctx, bool have_scene, const mi355rt_setting
     return MI355RT_OK;
 }
 
+// s = ceil(log2 d), mul = ceil(2^(31+s) / d) < 2^32, shift = s - 1.
+void magic_div(uint32_t d, uint32_t& mul, uint32_t& shift) {
+    if (d <= 1) { mul = 0; shift = 0; return; }
+    uint32_t s = 0; while ((1ull << s) < d) ++s;
+    const unsigned __int128 num = (unsigned __int128)1 << (31 + s);
+    mul = (uint32_t)((num + d - 1) / d); shift = s - 1;
+}
+
+void row_tables(const std::vector<uint32_t>& rows, const std::vector<float>& cost, uint32_t groups, std::vector<uint32_t>& out) {
+    const size_t n = rows.size();
+    out.resize(3 * n);
+    std::vector<uint32_t> sorted(n);
+    for (size_t j = 0; j < n; ++j) sorted[j] = (uint32_t)j;
+    if (!cost.empty())
+        std::stable_sort(sorted.begin(), sorted.end(), [&](uint32_t a, uint32_t b) {
+            const float ca = rows[a] < cost.size() ? cost[rows[a]] : 0.f, cb = rows[b] < cost.size() ? cost[rows[b]] : 0.f;
+            return ca > cb; });
+    groups = std::max(1u, std::min<uint32_t>(groups, (uint32_t)std::max<size_t>(n, 1)));
+    size_t jp = 0;
+    for (uint32_t g = 0; g < groups && !cost.empty(); ++g)
+        for (size_t k = g; k < n; k += groups, ++jp) { out[n + jp] = rows[sorted[k]]; out[2 * n + jp] = sorted[k]; }
+    for (size_t j = 0; j < n; ++j) {
+        out[j] = rows[j];
+        if (cost.empty()) { out[n + j] = rows[j]; out[2 * n + j] = (uint32_t)j; }
+    }
+}
+
+int plan_render(const RenderPlanIn& in, RowSel& sel, RenderPlan& plan) {
+    const mi355rt_settings& st = *in.settings;
+    const mi355rt_options* opt = in.options;
+    if (int rc = select_rows(st, opt, sel)) return rc;
+    const bool fixed_aabb = opt && (opt->flags & MI355RT_FLAG_FIXED_AABB) != 0u;
+    if (opt && (opt->flags & ~MI355RT_FLAG_FIXED_AABB) != 0u) return fail(MI355RT_ERR_INVALID, "options.flags has unknown bits");
+    plan = RenderPlan{};
+    plan.rng_mode = opt ? opt->rng_mode : (uint32_t)MI355RT_RNG_CTR;
+    if (fixed_aabb && plan.rng_mode != MI355RT_RNG_CTR) return fail(MI355RT_ERR_INVALID, "MI355RT_FLAG_FIXED_AABB needs MI355RT_RNG_CTR (the replay mode reproduces the reference as it is)");
+    uint32_t variant = in.variant;
+    if (fixed_aabb && in.has_mesh) variant = VARIANT_TABLE[variant].fixed_aabb;     // without a mesh the flag changes nothing
+    // The mesh-free lockstep kernels are compiled under the assumption that the list holds something and that a path may take a step (rt_kernels.hip,
+    // render_ctr_lockstep); the two degenerate renders -- every sample is the miss colour / BLACK -- go to the plain per-lane loop, which assumes nothing.
+    if ((in.n_prims == 0 || st.max_depth == 0) && VARIANT_TABLE[variant].family == FAMILY_LOCKSTEP && !(VARIANT_TABLE[variant].prims & (1u << MI355RT_PRIM_MESH)))
+        variant = KERNEL_LOCKSTEP_MESH;
+    plan.variant = variant; plan.fixed_aabb = fixed_aabb ? 1u : 0u;
+    plan.seed = opt ? opt->seed : 0; plan.seed_lo = (uint32_t)plan.seed; plan.seed_hi = (uint32_t)(plan.seed >> 32);
+    plan.spp = in.s1 - in.s0; plan.sample0 = in.s0; plan.accum_load = in.s0 != 0 ? 1u : 0u;
+    plan.inv_spp = 1.0f / (float)in.s1;                                               // renderer.rs:85
+    plan.width = st.width; plan.width_f = (float)st.width; plan.height_f = (float)st.height;   // exact: both below 2^24
+    { volatile float one = 1.0f; plan.inv_width_rn = one / plan.width_f; plan.inv_height_rn = one / plan.height_f; }   // IEEE division on the host = RN(1/x), what recip_normal_range() returns on the device
+    magic_div(plan.spp, plan.spp_mul, plan.spp_shift); magic_div(st.width, plan.width_mul, plan.width_shift);
+    plan.total_pixels = (uint64_t)sel.rows.size() * st.width;
+    plan.guided_mult = in.guided_mult; plan.row_probe = in.row_probe ? 1u : 0u;
+    // What fills the device, or this context's share of it: with F frames in flight (F contexts, F streams) each launch takes 1 / F of the wave slots,
+    // F launches are co-resident, and a frame whose last paths are draining shares every SIMD with frames in their steady state.  A full-size grid
+    // leaves the next frame's workgroups waiting for the draining frame's to retire one by one ("tail").
+    plan.resident = std::max(1u, in.block_slots[variant] / in.grid_div);
+    const bool ordered = in.have_row_cost && plan.rng_mode == MI355RT_RNG_CTR;      // otherwise: image order
+    if (sel.rows.empty()) { plan.order_groups = ordered ? WORK_SHARDS : 0u; return MI355RT_OK; }
+    if (plan.rng_mode == MI355RT_RNG_REF) {
+        if (in.have_accum || in.s0 != 0 || in.s1 != st.samples_per_pixel)
+            return fail(MI355RT_ERR_INVALID, "progressive rendering needs MI355RT_RNG_CTR (the reference stream of a row is sequential over its pixels)");
+        plan.band_pixels = plan.total_pixels; plan.n_bands = 1; plan.block_threads = 64;   // k_render_ref: one lane per row
+        return MI355RT_OK;
+    }
+    // ---- band plan: the radiance workspace holds band_pixels * spp float4 ----
+    const uint64_t ws_cap = (opt && opt->workspace_bytes) ? opt->workspace_bytes : (32ull << 30);   // 288 GB of HBM: default = the 2^31-sample band limit; only what a band needs is allocated
+    const uint64_t max_samples = std::min<uint64_t>(ws_cap / 12, (1ull << 31) - 16 * RUN_LIMIT);     // the shard counters overshoot by at most one run per claiming wave's last try; 32-bit headroom
+    if (max_samples < plan.spp) return fail(MI355RT_ERR_INVALID, "workspace_bytes too small for one pixel (needs spp * 12 bytes)");
+    plan.band_pixels = in.row_probe ? st.width : std::min<uint64_t>(max_samples / plan.spp, plan.total_pixels);   // the probe: a band = a row
+    plan.n_bands = (uint32_t)((plan.total_pixels + plan.band_pixels - 1) / plan.band_pixels);
+    plan.order_groups = ordered ? WORK_SHARDS * std::min(64u, plan.n_bands) : 0u;   // the work shards of every band this launch is cut into
+    plan.block_threads = VARIANT_TABLE[variant].block_threads;
+    return MI355RT_OK;
+}
+
+RenderBand render_band(const RenderPlan& plan, uint32_t b) {
+    RenderBand r;
+    const uint64_t p0 = (uint64_t)b * plan.band_pixels;
+    r.band_pixel0 = (uint32_t)p0; r.band_pixels = (uint32_t)std::min<uint64_t>(plan.band_pixels, plan.total_pixels - p0);
+    r.band_samples = (uint32_t)((uint64_t)r.band_pixels * plan.spp);
+    const bool wf = VARIANT_TABLE[plan.variant].family == FAMILY_WAVEFRONT;
+    const uint32_t run_min = wf ? RUN_WAVEFRONT_MIN : BATCH_MIN, run_max = wf ? RUN_WAVEFRONT : BATCH_MAX;   // what the kernel's WorkCursorT is compiled with
+    r.shard_samples = (r.band_samples + WORK_SHARDS - 1) / WORK_SHARDS;
+    r.shard_samples = (r.shard_samples + run_max - 1) / run_max * run_max;           // shards begin on run boundaries (fixed runs then stay aligned)
+    const uint32_t waves_per_block = plan.block_threads / 64;
+    const uint32_t min_runs = (r.band_samples + run_min - 1) / run_min;               // never more waves than minimum-size runs
+    r.grid = std::max(1u, std::min(plan.resident, (min_runs + waves_per_block - 1) / waves_per_block));
+    r.guided_div = std::max(1u, plan.guided_mult * r.grid * waves_per_block / WORK_SHARDS);
+    return r;
+}
+
+// (the row probe's counter blocks are laid out one per ROW = per band: halving would make more bands than blocks -- its caller returns the OOM)
+bool halve_bands(RenderPlan& plan) {
+    if (plan.band_pixels <= 1 || plan.row_probe) return false;
+    plan.band_pixels = (plan.band_pixels + 1) / 2;
+    plan.n_bands = (uint32_t)((plan.total_pixels + plan.band_pixels - 1) / plan.band_pixels);
+    return true;
+}
+
 bool scene_within_occlusion_bound(const PreparedScene& s) {
     const auto inside = [](const float* v, size_t n) { for (size_t k = 0; k < n; ++k) if (!(std::fabs(v[k]) <= OCCLUSION_BOUND)) return false; return true; };
     for (const DevPrim& p : s.prims) {

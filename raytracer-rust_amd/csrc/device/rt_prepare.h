@@ -1,6 +1,7 @@
 // rt_prepare.h -- the HIP-free half of libmi355rt.so's host code (rt_prepare.cpp): everything that reads caller-supplied data before a
 // device is involved.  The thread-local last error and the exception barrier of every extern "C" entry point, the row-selection rule of
-// mi355rt_options, and scene preparation: validation, the BVH re-lay, the DevPrim records and the choice of the kernel variant.
+// mi355rt_options, scene preparation -- validation, the BVH re-lay, the DevPrim records and the choice of the kernel variant -- and the plans of the
+// calls: what a render, the denoiser and the occlusion queries refuse and launch.
 // Includes the public header, rt_device.h and the standard library only, so that it also compiles and runs without ROCm (the CPU tests
 // through mi355rt_debug_prepare_scene, the sanitizer driver directly).  Not part of the public header.
 #pragma once
@@ -62,6 +63,45 @@ struct AoPlan { uint32_t samples, log2_samples, seed; float radius; };
 // st: the settings of set_scene (read only when have_scene).  sel: the selected rows; empty = nothing to do.
 int plan_ambient_occlusion(bool have_ctx, bool have_scene, const mi355rt_settings& st, const mi355rt_options* options_or_null,
                            const mi355rt_ao_params* params_or_null, const void* hits, const void* out, RowSel& sel, AoPlan& plan);
+
+// The render call (mi355rt_context_render / mi355rt_context_render_progressive): every refusal, the variant that is launched, the
+// bands the radiance workspace is cycled through and the geometry of each band's launch, decided before any HIP call.
+// q = n / d for every n < 2^31 as umulhi(n, mul) >> shift (mul == 0 encodes d == 1).
+void magic_div(uint32_t d, uint32_t& mul, uint32_t& shift);
+// The three row tables of one selection, n entries each: [0, n) natural = absolute y of local output row j; [n, 2n) processing = absolute y
+// of the row processed jp-th; [2n, 3n) out_row = the local output row that processing row jp is.  `cost` (per absolute image row, may be
+// empty) orders the processing: rows sorted by decreasing cost (stable: equal costs keep image order) and dealt round-robin over `groups`
+// consecutive ranges -- the launch's work shards (x bands) -- so that every range runs from its dearest rows to its cheapest.
+void row_tables(const std::vector<uint32_t>& rows, const std::vector<float>& cost, uint32_t groups, std::vector<uint32_t>& out);
+struct RenderPlanIn {                                                // what a render reads of its context and its caller
+    const mi355rt_settings* settings;                                // of set_scene (checked there)
+    const mi355rt_options* options;                                  // may be null
+    uint32_t s0, s1;                                                 // samples [s0, s1) of every selected pixel, s0 < s1
+    bool have_accum;                                                 // running sums were given (progressive rendering)
+    uint32_t variant; bool has_mesh; uint32_t n_prims;               // of the resident scene
+    bool have_row_cost;                                              // set_scene measured a cost per image row (the processing order)
+    bool row_probe;                                                  // set_scene's row-cost probe: a band = a row, no halving
+    const uint32_t* block_slots;                                     // per variant: workgroups the device holds at once (CUs x workgroups per CU)
+    uint32_t grid_div, guided_mult;                                  // mi355rt_context_set_share; the knob "guided_mult"
+};
+struct RenderPlan {                                                  // plain words (device.RenderPlan has the same layout)
+    uint64_t seed, total_pixels, band_pixels;                        // total_pixels: of the selection; band_pixels: of every band but the last
+    uint32_t rng_mode, fixed_aabb, variant;                          // variant: the one that is launched (the flag form; k_render_ctr_mesh for the two degenerate renders)
+    uint32_t order_groups;                                           // groups the processing order is dealt over: WORK_SHARDS x min(64, bands before any halving); 0 = image order
+    uint32_t spp, n_bands, block_threads;                            // spp: samples per pixel of THIS launch
+    float width_f, height_f, inv_width_rn, inv_height_rn, inv_spp;   // RenderParams / ResolveParams words that are arithmetic on the settings
+    uint32_t spp_mul, spp_shift, width_mul, width_shift, accum_load, sample0, seed_lo, seed_hi;
+    uint32_t width, resident, guided_mult, row_probe;                // what render_band cuts a band's launch with (resident: workgroups this context may launch)
+};
+static_assert(sizeof(RenderPlan) == 120, "RenderPlan is read as plain words by mi355rt_debug_plan_render's caller");
+struct RenderBand { uint32_t band_pixel0, band_pixels, band_samples, shard_samples, grid, guided_div; };   // RenderParams / ResolveParams words and the grid of band b
+// Refusals in this order (MI355RT_ERR_INVALID and today's texts): what select_rows refuses; unknown flag bits; MI355RT_FLAG_FIXED_AABB without
+// MI355RT_RNG_CTR; then an EMPTY selection is MI355RT_OK (sel.rows empty, n_bands 0: nothing to launch) whatever follows; with MI355RT_RNG_REF a
+// progressive call; with MI355RT_RNG_CTR a workspace below one pixel.  MI355RT_RNG_REF plans one "band" of one lane per row.
+int plan_render(const RenderPlanIn& in, RowSel& sel, RenderPlan& plan);
+RenderBand render_band(const RenderPlan& plan, uint32_t b);          // b < n_bands; MI355RT_RNG_CTR
+// The workspace of a band did not fit: bands of half the pixels (the same image: tiling invariance).  false = there is no smaller plan (one pixel; the row probe).
+bool halve_bands(RenderPlan& plan);
 
 // A validated scene in the form the device holds it (rt_device.h), still in host memory, and what the choice of the kernel reads.
 struct PreparedScene {

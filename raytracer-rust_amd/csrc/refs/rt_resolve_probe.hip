@@ -4,9 +4,8 @@
 //
 // Nothing is restated here: mi355rt_debug_resolve / mi355rt_debug_gather fill ResolveParams / GatherParams / GatherAccumParams from their
 // arguments and call the shipped launch_resolve / launch_gather_strips / launch_gather_accum (rt_kernels.hip), the launchers the renders
-// call.  The one exception is the magic pair of `width`: rt_api.cpp keeps magic_div in its unnamed namespace, and giving it a name would
-// change the product's kernel hash, so its five lines are repeated below; tests/test_gpu_resolve_stage.py holds the two texts against each
-// other and checks every pixel's place under a row table.
+// call, and the magic pair of `width` is the library's magic_div (rt_prepare.h); tests/test_gpu_resolve_stage.py checks every pixel's place under a
+// row table.
 // Every pointer is a DEVICE address of the current device and is used as it is: the caller sizes the buffers
 // (tests/test_gpu_resolve_stage.py states the extents next to each call).  Both calls wait for the kernel before they return.
 #include <hip/hip_runtime.h>
@@ -31,14 +30,6 @@ struct GatherProbeArgs {                                // 64 B; device.GatherPr
     uint32_t n_rows, width;
 };
 static_assert(sizeof(GatherProbeArgs) == 64, "GatherProbeArgs");
-
-// rt_api.cpp's magic_div, word for word (see above).
-static void magic_div(uint32_t d, uint32_t& mul, uint32_t& shift) {
-    if (d <= 1) { mul = 0; shift = 0; return; }
-    uint32_t s = 0; while ((1ull << s) < d) ++s;
-    const unsigned __int128 num = (unsigned __int128)1 << (31 + s);
-    mul = (uint32_t)((num + d - 1) / d); shift = s - 1;
-}
 
 }  // namespace mi355rt
 

@@ -203,6 +203,9 @@ def _bind(so):
         L.mi355rt_debug_camera_masks.restype = C.c_int
         L.mi355rt_debug_camera_masks.argtypes = [C.POINTER(abi.Scene), C.POINTER(abi.Camera), C.POINTER(abi.Settings), C.POINTER(abi.Options), C.c_int,
                                                  C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+        L.mi355rt_debug_plan_render.restype = C.c_int
+        L.mi355rt_debug_plan_render.argtypes = [C.POINTER(abi.Settings), C.POINTER(abi.Options), C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p,
+                                                C.POINTER(C.c_uint32), C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p, C.POINTER(C.c_uint32)]
         if L.mi355rt_abi_version() != abi.ABI_VERSION:
             raise RuntimeError("libmi355rt.so ABI version does not match abi.py")
     return L
@@ -270,6 +273,52 @@ def camera_masks(scene, camera, settings, options=None, forced_variant=-1, libra
     _check(L.mi355rt_debug_camera_masks(C.byref(sc), C.byref(camera), C.byref(settings), opt, int(forced_variant), out.ctypes.data, out.size, C.byref(n)),
            "mi355rt_debug_camera_masks", L)
     return out.reshape(-1, settings.width)
+
+
+KERNEL_VARIANTS, WORK_SHARDS = 15, 8                                  # rt_device.h
+
+
+class PlanProbeArgs(C.Structure):                                     # the context's side of a render's inputs (rt_api.cpp PlanProbeArgs)
+    _fields_ = [(n, C.c_uint32) for n in ("s0", "s1", "have_accum", "variant", "has_mesh", "n_prims", "row_probe", "grid_div", "guided_mult")] + \
+               [("block_slots", C.c_uint32 * KERNEL_VARIANTS)]
+
+
+class RenderPlan(C.Structure):                                        # rt_prepare.h RenderPlan
+    _fields_ = [(n, C.c_uint64) for n in ("seed", "total_pixels", "band_pixels")] + \
+               [(n, C.c_uint32) for n in ("rng_mode", "fixed_aabb", "variant", "order_groups", "spp", "n_bands", "block_threads")] + \
+               [(n, C.c_float) for n in ("width_f", "height_f", "inv_width_rn", "inv_height_rn", "inv_spp")] + \
+               [(n, C.c_uint32) for n in ("spp_mul", "spp_shift", "width_mul", "width_shift", "accum_load", "sample0", "seed_lo", "seed_hi",
+                                          "width", "resident", "guided_mult", "row_probe")]
+
+
+BAND_DTYPE = np.dtype([(n, "<u4") for n in ("band_pixel0", "band_pixels", "band_samples", "shard_samples", "grid", "guided_div")])   # rt_prepare.h RenderBand
+Planned = collections.namedtuple("Planned", "plan halved bands natural processing out_row")
+
+
+def plan_render(settings, options=None, s0=0, s1=None, have_accum=False, variant=0, has_mesh=False, n_prims=1, row_cost=None, row_probe=False,
+                block_slots=512, grid_div=1, guided_mult=16, halvings=0, library=None):
+    """Diagnostic (mi355rt_debug_plan_render): what Context.render / render_progressive with these inputs would launch -- the plan_render, halve_bands,
+    render_band and row_tables of the render call itself.  No GPU and no context are needed.  s1 None: settings.samples_per_pixel; block_slots: the
+    workgroups the device holds of each variant (one number for all, or KERNEL_VARIANTS of them); row_cost: a cost per image row (the processing
+    order); halvings: "the band did not fit" steps taken first.  Returns Planned(plan: RenderPlan, halved: steps that existed, bands [BAND_DTYPE],
+    natural, processing, out_row: the three row tables); raises RenderError on a refusal."""
+    L = library or lib()
+    slots = [int(block_slots)] * KERNEL_VARIANTS if np.isscalar(block_slots) else [int(v) for v in block_slots]
+    a = PlanProbeArgs(int(s0), int(settings.samples_per_pixel if s1 is None else s1), int(bool(have_accum)), int(variant), int(bool(has_mesh)), int(n_prims),
+                      int(bool(row_probe)), int(grid_div), int(guided_mult), (C.c_uint32 * KERNEL_VARIANTS)(*slots))
+    cost = np.zeros(0, np.float32) if row_cost is None else np.ascontiguousarray(row_cost, np.float32)
+    opt = C.byref(options) if options is not None else None
+    plan, halved, n_bands, n_rows = RenderPlan(), C.c_uint32(), C.c_uint32(), C.c_uint32()
+
+    def call(bands, tables):
+        _check(L.mi355rt_debug_plan_render(C.byref(settings), opt, C.addressof(a), cost.ctypes.data if cost.size else None, cost.size, int(halvings),
+                                           C.addressof(plan), C.byref(halved), bands, C.byref(n_bands), tables, C.byref(n_rows)), "mi355rt_debug_plan_render", L)
+
+    call(None, None)
+    bands, t = np.zeros(n_bands.value, BAND_DTYPE), np.zeros(3 * n_rows.value, np.uint32)
+    call(bands.ctypes.data, t.ctypes.data)
+    n = n_rows.value
+    return Planned(plan, halved.value, bands, t[:n], t[n:2 * n], t[2 * n:])
 
 
 def render(scene, camera, settings, options=None, want_linear=True, want_stats=True, library=None):

@@ -33,22 +33,35 @@ def _rgb(packed):
     return np.stack([(packed >> 16) & 255, (packed >> 8) & 255, packed & 255], axis=-1).astype(np.float64)
 
 
-def _band_plan(width, height, spp, workspace_bytes=32 << 30):
-    """rt_api.cpp render_samples' band plan for a whole image: (bands, rows that hold a band boundary, rows that hold a work-shard
-    boundary of the first band).  A band is band_pixels consecutive pixels (row-major), its samples are cut into WORK_SHARDS shards of
-    shard_samples (rounded up to whole runs); a boundary between sample s - 1 and s lies in the rows of both."""
-    pixels = width * height
-    max_samples = min(workspace_bytes // 12, (1 << 31) - 16 * RUN_LIMIT)
+def _band_model(pixels, spp, workspace_bytes=0, run_min=128, run_max=RUN_MAX, waves_per_block=4, resident=512, guided_mult=16):
+    """The band plan of a render (rt_prepare.cpp plan_render / render_band), restated: (band_pixels, [per band (band_pixel0, band_pixels, band_samples,
+    shard_samples, grid, guided_div)]).  A band is band_pixels consecutive pixels (row-major over the selected rows), its samples are cut into
+    WORK_SHARDS shards of shard_samples (rounded up to whole runs of run_max); the grid is what the device holds of the kernel (resident
+    workgroups), never more waves than runs of run_min.  workspace_bytes 0: the default, the 2^31-sample band limit."""
+    max_samples = min((workspace_bytes or 32 << 30) // 12, (1 << 31) - 16 * RUN_LIMIT)
     band_pixels = min(max_samples // spp, pixels)
-    bands = -(-pixels // band_pixels)
-    shard = -(-band_pixels * spp // WORK_SHARDS)
-    shard = -(-shard // RUN_MAX) * RUN_MAX
+    bands = []
+    for p0 in range(0, pixels, band_pixels):
+        samples = min(band_pixels, pixels - p0) * spp
+        shard = -(-(-(-samples // WORK_SHARDS)) // run_max) * run_max
+        grid = max(1, min(resident, -(-(-(-samples // run_min)) // waves_per_block)))
+        bands.append((p0, samples // spp, samples, shard, grid, max(1, guided_mult * grid * waves_per_block // WORK_SHARDS)))
+    return band_pixels, bands
 
+
+def _boundary_rows(width, spp, bands):
+    """(bands, rows that hold a band boundary, rows that hold a work-shard boundary of the first band) of per-band records as _band_model's; a
+    boundary between sample s - 1 and s lies in the rows of both."""
     def rows_of(samples):
         return sorted({y for s in samples for y in ((s - 1) // spp // width, s // spp // width)})
 
-    return (bands, rows_of([b * band_pixels * spp for b in range(1, bands)]),
-            rows_of([k * shard for k in range(1, WORK_SHARDS) if k * shard < band_pixels * spp]))
+    shard, first = int(bands[0][3]), int(bands[0][2])
+    return (len(bands), rows_of([int(b[0]) * spp for b in bands[1:]]), rows_of([k * shard for k in range(1, WORK_SHARDS) if k * shard < first]))
+
+
+def _band_plan(width, height, spp, workspace_bytes=0):
+    """The model's band plan for a whole image: (bands, rows that hold a band boundary, rows that hold a work-shard boundary of the first band)."""
+    return _boundary_rows(width, spp, _band_model(width * height, spp, workspace_bytes)[1])
 
 
 def _windows(rows):
@@ -138,12 +151,17 @@ def test_semesterbild_800x600x256_d30_matches_the_oracle(native, oracle_mod, abi
     assert_parity(gp, gl, op, ol, exact=False, gpu_rays=st.rays, oracle_rays=cnt.rays, ray_rel=1e-6)
 
 
-def test_band_plan_of_config_5():
-    """The rows test_semesterbild_1920x1080x4096... compares hold the boundaries the library's band plan really has."""
+def test_band_plan_of_config_5(native, abi):
+    """The rows test_semesterbild_1920x1080x4096... compares hold the boundaries the library's band plan really has: what plan_render and render_band
+    (rt_prepare.cpp, the functions the render call itself uses; through mi355rt_debug_plan_render) plan for the shape is what the model here plans."""
+    _, device = native
     bands, band_rows, shard_rows = _band_plan(1920, 1080, 4096)
     assert bands == 4 and band_rows == [273, 546, 819]
     assert shard_rows == [34, 68, 102, 136, 170, 204, 238]              # 65 535 pixels per shard
     assert _band_plan(800, 600, 256) == (1, [], [74, 75, 149, 150, 224, 225, 299, 300, 374, 375, 449, 450, 524, 525])   # shards end on row ends
+    for w, h, spp in ((1920, 1080, 4096), (800, 600, 256)):
+        lib = device.plan_render(abi.Settings(w, h, spp, 30), variant=13)                       # (semesterbild's kernel; the shard size is the same for all)
+        assert lib.plan.n_bands == len(lib.bands) and _boundary_rows(w, spp, lib.bands.tolist()) == _band_plan(w, h, spp), (w, h, spp)
 
 
 def _config5_rows():

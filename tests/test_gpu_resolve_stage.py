@@ -203,14 +203,18 @@ def test_pack_thresholds_agree_with_the_oracle(oracle_mod):
         assert L.oracle_color_to_u32(r, r, r) == want * 0x010101, hex(w)
 
 
-def test_the_probe_repeats_the_librarys_magic_div():
-    """rt_api.cpp keeps magic_div in its unnamed namespace; the probe's copy is the same text (and test_row_tables_place_every_pixel checks
-    what it computes)."""
-    def body(path):
-        s = open(os.path.join(ROOT, path)).read()
-        m = re.search(r"void magic_div\(uint32_t d, uint32_t& mul, uint32_t& shift\) \{(.*?)\n\}", s, re.S)
-        return re.sub(r"\s+", " ", m.group(1))
-    assert body("raytracer-rust_amd/csrc/refs/rt_resolve_probe.hip") == body("raytracer-rust_amd/csrc/device/rt_api.cpp")
+def test_the_probe_calls_the_librarys_magic_div():
+    """The probe's magic pair of `width` is the library's: it defines no magic_div of its own and calls the one definition, rt_prepare.cpp's (declared in
+    rt_prepare.h, which rt_host.h brings in), which the render, first_hits and ambient_occlusion call too.  test_row_tables_place_every_pixel checks
+    what the pair computes on the device, tests/test_render_plan.py on the CPU."""
+    read = lambda path: open(os.path.join(ROOT, "raytracer-rust_amd/csrc", path)).read()
+    definition = r"\bmagic_div\(uint32_t d, uint32_t& mul, uint32_t& shift\) \{"
+    probe, api, prep = read("refs/rt_resolve_probe.hip"), read("device/rt_api.cpp"), read("device/rt_prepare.cpp")
+    assert not re.search(definition, probe) and not re.search(definition, api) and len(re.findall(definition, prep)) == 1
+    assert "magic_div(a.width, r.width_mul, r.width_shift);" in probe and '#include "../device/rt_host.h"' in probe
+    assert "void magic_div(uint32_t d, uint32_t& mul, uint32_t& shift);" in read("device/rt_prepare.h")
+    for f in sorted(os.listdir(os.path.join(ROOT, "raytracer-rust_amd/csrc/device"))):
+        assert len(re.findall(definition, read(os.path.join("device", f)))) == (1 if f == "rt_prepare.cpp" else 0), f
 
 
 # ------------------------------------------------------------------------------------------------------------------ GPU: k_resolve

@@ -1,4 +1,4 @@
-"""Processing order (rt_api.cpp row_tables()): set_scene measures the cost of the image rows with a small probe render and the
+"""Processing order (rt_prepare.cpp row_tables(); its CPU twin: tests/test_render_plan.py): set_scene measures the cost of the image rows with a small probe render and the
 persistent kernels then process the dearest rows first, the cheapest (sky) last, so that a launch does not end on its longest paths.  The image
 must not change by a single bit -- draws are keyed by absolute row / x / sample and k_resolve writes every pixel where it belongs -- whatever
 the selection, the banding or the chunking.  The mechanism is opt-in (diagnostic knob "row_order" = 1): measured in round 4, it moves full

@@ -1,6 +1,6 @@
 // Sanitizer driver for the CPU-side producers (libmi355rt_host: scene loader, JSON, OBJ / WO3 / HDR readers, BVH build,
 // PNG / PFM writers), for the CPU oracle's entry points and for scene preparation, the HIP-free half of the device library
-// (csrc/device/rt_prepare.cpp: validation, the BVH re-lay, the primitive records).  Built with -fsanitize=address,undefined by
+// (csrc/device/rt_prepare.cpp: validation, the BVH re-lay, the primitive records; the plan of a render call).  Built with -fsanitize=address,undefined by
 // tools/sanitize_host.py; every case must return (OK or an error code) without a sanitizer report.
 //   usage: driver <repo root> <scratch dir>
 #include <cmath>
@@ -119,6 +119,76 @@ static void prepare(const std::string& path, bool skip_unknown, bool malformed) 
     mi355rt_scene_free(ls);
 }
 
+// The plan of a render call (rt_prepare.cpp plan_render, halve_bands, render_band, row_tables) at the ends of what check_settings admits: 64-bit
+// arithmetic with 32-bit results next to the 2^31 limits.  Every band of every plan is walked; the bands must tile the selection, a band's samples
+// stay below 2^31, its shards cover it and its grid stays within the slots.
+static void plan(const mi355rt_settings& st, const mi355rt_options* opt, uint32_t s0, uint32_t s1, uint32_t variant, uint32_t slots, const std::string& what) {
+    using namespace mi355rt;
+    expect(check_settings(&st) == MI355RT_OK, what + ": settings");
+    uint32_t block_slots[KERNEL_VARIANTS]; for (uint32_t& v : block_slots) v = slots;
+    for (int probe = 0; probe < (st.height > 100000u ? 1 : 2); ++probe) {                      // (16 M rows: the row probe's plan is skipped, a probe has 96 rows)
+        const RenderPlanIn in{&st, opt, s0, s1, s0 != 0, variant, true, 3u, true, probe != 0, block_slots, probe ? 16u : 1u, probe ? 64u : 1u};
+        RowSel sel; RenderPlan p;
+        const int rc = plan_render(in, sel, p);
+        const uint64_t ws = opt && opt->workspace_bytes ? opt->workspace_bytes : ~0ull;
+        expect(rc == (ws / 12 < (uint64_t)s1 - s0 && !sel.rows.empty() ? MI355RT_ERR_INVALID : MI355RT_OK), what + ": plan_render returned " + std::to_string(rc) + " (" + last_error() + ")");
+        if (rc != MI355RT_OK) continue;
+        expect(p.total_pixels == (uint64_t)sel.rows.size() * st.width && (p.n_bands == 0u) == sel.rows.empty(), what + ": pixels");
+        if (sel.rows.empty() || VARIANT_TABLE[p.variant].block_threads == 0u) continue;     // nothing to launch; a retired variant
+        if (!probe && sel.rows.size() <= 100000u) {
+            std::vector<float> cost(st.height); for (uint32_t y = 0; y < st.height; ++y) cost[y] = (float)(y % 7u);
+            std::vector<uint32_t> tables;
+            row_tables(sel.rows, cost, p.order_groups, tables);
+            expect(tables.size() == 3 * sel.rows.size(), what + ": tables");
+        }
+        for (int halvings = 0; ; ++halvings) {
+            // every band when they are few; otherwise the first and the last 100 000 (a one-pixel band of the largest image: 2^31 of them)
+            uint64_t next = 0; bool ok = p.n_bands >= 1 && p.band_pixels >= 1;
+            for (uint32_t b = 0; b < p.n_bands; ++b) {
+                if (p.n_bands > 200000u && b == 100000u) { b = p.n_bands - 100000u; next = (uint64_t)b * p.band_pixels; }
+                const RenderBand r = render_band(p, b);
+                ok = ok && r.band_pixel0 == next && r.band_pixels >= 1 && r.band_pixels <= p.band_pixels && 
+                     (probe || (r.band_samples == (uint64_t)r.band_pixels * p.spp && r.band_samples < (1u << 31))) && (uint64_t)WORK_SHARDS * r.shard_samples >= r.band_samples && r.grid >= 1 && r.grid <= p.resident && r.guided_div >= 1;
+                next += r.band_pixels;
+            }
+            expect(ok && next == p.total_pixels, what + ": bands after " + std::to_string(halvings) + " halvings" + (probe ? " (row probe)" : ""));
+            const uint64_t before = p.band_pixels;
+            if (!halve_bands(p)) { expect(probe || before == 1, what + ": halving ends at one pixel"); break; }
+            expect(!probe && p.band_pixels == (before + 1) / 2, what + ": halving");
+        }
+    }
+}
+
+static void plan_cases() {
+    using namespace mi355rt;
+    const uint32_t SPP_MAX = (1u << 30) - 1u, SIDE_MAX = (1u << 24) - 1u;
+    const mi355rt_settings sizes[] = {{1, 1, 1, 1}, {1, 1, SPP_MAX, 0}, {SIDE_MAX, 128, 1, 5}, {128, SIDE_MAX, SPP_MAX, 5}, {46340, 46340, 4096, 30}, {SIDE_MAX, 1, 7, 1}, {33, 35, 3, 6}};
+    for (const mi355rt_settings& st : sizes) {
+        const std::string size = std::to_string(st.width) + "x" + std::to_string(st.height) + "x" + std::to_string(st.samples_per_pixel);
+        for (uint64_t ws : {0ull, 1ull, 12ull, ~0ull}) {
+            mi355rt_options o{}; o.abi_version = MI355RT_ABI_VERSION; o.rng_mode = MI355RT_RNG_CTR; o.workspace_bytes = ws; o.seed = ~0ull;
+            for (uint32_t v = 0; v < KERNEL_VARIANTS; v += st.height > 100000u ? 13u : 1u) {   // (16 M rows: two variants, a lockstep and a wavefront kernel)
+                o.flags = v & 1u ? MI355RT_FLAG_FIXED_AABB : 0u;
+                plan(st, &o, 0, st.samples_per_pixel, v, v & 2u ? 0xFFFFFFFFu : 1u, "plan " + size + " ws " + std::to_string(ws) + " variant " + std::to_string(v));
+            }
+            plan(st, &o, SPP_MAX - 1u, SPP_MAX, KERNEL_LOCKSTEP_SIMPLE_QC, 1024u, "plan " + size + " ws " + std::to_string(ws) + ": one sample at a large s0");
+            mi355rt_options row = o; row.row_begin = st.height - 1u; row.row_end = st.height;
+            plan(st, &row, 0, st.samples_per_pixel, KERNEL_WAVEFRONT_MESHFREE, 512u, "plan " + size + " ws " + std::to_string(ws) + ": a window of one row");
+            mi355rt_options none = o; none.strip_rows = st.height; none.n_parts = 2; none.part = 1;
+            plan(st, &none, 0, st.samples_per_pixel, KERNEL_LOCKSTEP, 512u, "plan " + size + " ws " + std::to_string(ws) + ": a part that is dealt no strip");
+        }
+        plan(st, nullptr, 0, st.samples_per_pixel, KERNEL_WAVEFRONT_NOMETAL, 512u, "plan " + size + " without options");
+    }
+    const mi355rt_settings st{33, 35, 3, 6};
+    mi355rt_options o{}; o.abi_version = MI355RT_ABI_VERSION; o.rng_mode = MI355RT_RNG_REF;
+    uint32_t slots[KERNEL_VARIANTS] = {};
+    RowSel sel; RenderPlan p;
+    expect(plan_render(RenderPlanIn{&st, &o, 0, 3, false, KERNEL_LOCKSTEP, false, 0, true, false, slots, 1, 16}, sel, p) == MI355RT_OK && p.n_bands == 1 && p.order_groups == 0, "plan: the replay mode");
+    expect(plan_render(RenderPlanIn{&st, &o, 1, 3, true, KERNEL_LOCKSTEP, false, 0, true, false, slots, 1, 16}, sel, p) == MI355RT_ERR_INVALID, "plan: progressive in the replay mode");
+    o.flags = 2u; expect(plan_render(RenderPlanIn{&st, &o, 0, 3, false, KERNEL_LOCKSTEP, false, 0, true, false, slots, 1, 16}, sel, p) == MI355RT_ERR_INVALID, "plan: unknown flag bits");
+    for (uint32_t d : {1u, 2u, 3u, 255u, 256u, SIDE_MAX, SPP_MAX, 0x80000000u, 0xFFFFFFFFu}) { uint32_t mul = 1, shift = 1; magic_div(d, mul, shift); expect(shift < 32u && (d > 1u) == (mul != 0u), "magic_div " + std::to_string(d)); }
+}
+
 static std::string scene_with(const std::string& prim) {
     return std::string("{\"bsdfs\":[{\"name\":\"m\",\"type\":\"lambert\",\"albedo\":[0.5,0.5,0.5]}],\"primitives\":[") + prim +
            "],\"camera\":{\"transform\":{\"position\":[0,0,5],\"look_at\":[0,0,0],\"up\":[0,1,0]},\"fov\":40,\"resolution\":[8,8]},\"renderer\":{\"spp\":1},\"integrator\":{\"max_bounces\":2}}";
@@ -142,6 +212,9 @@ int main(int argc, char** argv) {
     prepare(root + "/data/scenes/tungsten/veach-mis/scene.json", false, false);
     prepare(root + "/data/scenes/tungsten/teapot/scene.json", true, false);
     prepare(root + "/data/scenes/semesterbild.json", false, true);
+
+    // ---- the plan of a render call (what mi355rt_context_render decides before it touches a device) ----
+    plan_cases();
 
     // ---- malformed JSON ----
     const char* bad_json[] = {"", "{", "[", "{\"a\":}", "{\"a\":1,}", "nul", "{\"a\":1} x", "\"\\u12", "\"abc", "{\"a\":01}", "{\"a\":1.}", "{\"a\":.5}",
