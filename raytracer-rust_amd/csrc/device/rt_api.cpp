@@ -4,7 +4,8 @@
 // called from src/main.rs:57).  There is NO CPU fallback in this library: without a HIP device every
 // render entry point returns MI355RT_ERR_NO_DEVICE.  What happens to a scene before a device is involved -- validation, the BVH re-lay, the
 // primitive records, the choice of the kernel variant -- and what a render call launches -- its refusals, the variant, the bands and their grids -- is
-// rt_prepare.cpp, which has no HIP in it; this file uploads and launches.
+// rt_prepare.cpp, which has no HIP in it; this file uploads and launches: the context, its renders, its queries and the debug hooks.  The
+// calls with host buffers (mi355rt_render and its kin) are clients of this file's public functions and live in rt_oneshot.cpp.
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -17,7 +18,6 @@
 #include <new>
 #include <stdexcept>
 #include <string>
-#include <thread>
 #include <vector>
 
 #include "../../../include/mi355rt.h"
@@ -642,30 +642,6 @@ int mi355rt_context_first_hits(mi355rt_context* ctx, const mi355rt_options* opt,
     });
 }
 
-// Host buffers in, host buffers out: a context on device 0, the scene uploaded, one query, the records copied back.
-int mi355rt_trace_rays(const mi355rt_scene* scene, const mi355rt_ray* rays, uint32_t n_rays, mi355rt_hit* out_hits) {
-    return guard([&]() -> int {
-    if (!scene) return fail(MI355RT_ERR_INVALID, "scene is null");
-    if (n_rays && (!rays || !out_hits)) return fail(MI355RT_ERR_INVALID, "trace_rays: rays / out_hits is null");
-    if (n_rays == 0) return MI355RT_OK;
-    mi355rt_context* ctx = nullptr;
-    int rc = mi355rt_context_create(0, &ctx); if (rc) return rc;
-    const mi355rt_camera no_camera{}; const mi355rt_settings one_pixel{1, 1, 1, 1};      // set_scene wants a view; the query does not look at it
-    rc = mi355rt_context_set_scene(ctx, scene, &no_camera, &one_pixel);
-    DevBuf<mi355rt_ray> d_rays; DevBuf<mi355rt_hit> d_hits;
-    if (!rc) rc = d_rays.ensure(n_rays);
-    if (!rc) rc = d_hits.ensure(n_rays);
-    if (!rc && hipMemcpy(d_rays.p, rays, (size_t)n_rays * sizeof(mi355rt_ray), hipMemcpyHostToDevice) != hipSuccess) rc = fail(MI355RT_ERR_HIP, "upload rays");
-    if (!rc) rc = mi355rt_context_trace_rays(ctx, d_rays.p, n_rays, d_hits.p, nullptr);
-    if (!rc && hipMemcpy(out_hits, d_hits.p, (size_t)n_rays * sizeof(mi355rt_hit), hipMemcpyDeviceToHost) != hipSuccess) rc = fail(MI355RT_ERR_HIP, "copy back hits");   // (waits for the query)
-    d_rays.release(); d_hits.release();
-    std::string keep; keep.swap(last_error());                               // (destroy may overwrite the message of the failure being reported; swap never throws)
-    mi355rt_context_destroy(ctx);
-    last_error().swap(keep);
-    return rc;
-    });
-}
-
 // ---- occlusion queries (rt_occlusion.hip): does anything lie in front of t_max? -----------------------------------------------------------
 // The protocol of the ray queries: they read the scene arrays only, neither wait on `done` nor record it, and do not consult set_share.
 // Every refusal is rt_prepare.cpp's, before any HIP call.
@@ -708,31 +684,6 @@ int mi355rt_context_ambient_occlusion(mi355rt_context* ctx, const mi355rt_option
     });
 }
 
-// Host buffers in, host buffers out: a context on device 0, the scene uploaded, one query, the words copied back.
-int mi355rt_occluded(const mi355rt_scene* scene, const mi355rt_segment* segments, uint32_t n, uint32_t* out) {
-    return guard([&]() -> int {
-    if (!scene) return fail(MI355RT_ERR_INVALID, "occluded: scene is null");
-    if (n && !segments) return fail(MI355RT_ERR_INVALID, "occluded: segments is null");
-    if (n && !out) return fail(MI355RT_ERR_INVALID, "occluded: out is null");
-    if (n == 0) return MI355RT_OK;
-    mi355rt_context* ctx = nullptr;
-    int rc = mi355rt_context_create(0, &ctx); if (rc) return rc;
-    const mi355rt_camera no_camera{}; const mi355rt_settings one_pixel{1, 1, 1, 1};      // set_scene wants a view; the query does not look at it
-    rc = mi355rt_context_set_scene(ctx, scene, &no_camera, &one_pixel);
-    DevBuf<mi355rt_segment> d_seg; DevBuf<uint32_t> d_out;
-    if (!rc) rc = d_seg.ensure(n);
-    if (!rc) rc = d_out.ensure(n);
-    if (!rc && hipMemcpy(d_seg.p, segments, (size_t)n * sizeof(mi355rt_segment), hipMemcpyHostToDevice) != hipSuccess) rc = fail(MI355RT_ERR_HIP, "upload segments");
-    if (!rc) rc = mi355rt_context_occluded(ctx, d_seg.p, n, d_out.p, nullptr);
-    if (!rc && hipMemcpy(out, d_out.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess) rc = fail(MI355RT_ERR_HIP, "copy back words");   // (waits for the query)
-    d_seg.release(); d_out.release();
-    std::string keep; keep.swap(last_error());                               // (destroy may overwrite the message of the failure being reported; swap never throws)
-    mi355rt_context_destroy(ctx);
-    last_error().swap(keep);
-    return rc;
-    });
-}
-
 // ---- the denoiser (rt_denoise.hip): an a-trous filter over a linear image, guided by first-hit records --------------------------------
 // The context names the device and carries the error word of its renders; nothing of it is read or written by the kernels, so the
 // call neither waits on `done` nor records it.  What is decided before a device is involved -- the arguments, the per-level constants -- is
@@ -755,37 +706,6 @@ int mi355rt_context_denoise(mi355rt_context* ctx, uint32_t width, uint32_t rows,
     d.out_linear = (float*)d_out_linear; d.out_packed = (uint32_t*)d_out_packed; d.width = width; d.rows = rows; d.staged = ctx->knob_denoise_staged;
     if (launch_denoise(d, hip_stream) != 0) return fail(MI355RT_ERR_HIP, "k_denoise launch failed");
     return MI355RT_OK;
-    });
-}
-
-// Host buffers in, host buffers out: a context on device 0 (no scene), the image and the records uploaded, one call, the results copied back.
-int mi355rt_denoise(uint32_t width, uint32_t rows, const mi355rt_denoise_params* params, const float* linear_in, const mi355rt_hit* hits,
-                    float* out_linear, uint32_t* out_packed) {
-    return guard([&]() -> int {
-    DenoisePlan plan;
-    if (!linear_in) return fail(MI355RT_ERR_INVALID, "denoise: linear_in is null");
-    if (!hits) return fail(MI355RT_ERR_INVALID, "denoise: hits is null");
-    if (!out_linear && !out_packed) return fail(MI355RT_ERR_INVALID, "denoise: out_linear and out_packed are both null");
-    if (int rc = plan_denoise(width, rows, params, plan)) return rc;
-    const size_t n = (size_t)width * rows;
-    mi355rt_context* ctx = nullptr;
-    int rc = mi355rt_context_create(0, &ctx); if (rc) return rc;
-    DevBuf<float> d_in, d_lin; DevBuf<mi355rt_hit> d_hits; DevBuf<uint32_t> d_packed; DevBuf<unsigned char> d_scratch;
-    rc = d_in.ensure(n * 3);
-    if (!rc) rc = d_hits.ensure(n);
-    if (!rc) rc = d_scratch.ensure(n * DENOISE_SCRATCH_PER_PIXEL);
-    if (!rc && out_linear) rc = d_lin.ensure(n * 3);
-    if (!rc && out_packed) rc = d_packed.ensure(n);
-    if (!rc && hipMemcpy(d_in.p, linear_in, n * 12, hipMemcpyHostToDevice) != hipSuccess) rc = fail(MI355RT_ERR_HIP, "upload image");
-    if (!rc && hipMemcpy(d_hits.p, hits, n * sizeof(mi355rt_hit), hipMemcpyHostToDevice) != hipSuccess) rc = fail(MI355RT_ERR_HIP, "upload hits");
-    if (!rc) rc = mi355rt_context_denoise(ctx, width, rows, params, d_in.p, d_hits.p, d_scratch.p, out_linear ? d_lin.p : nullptr, out_packed ? d_packed.p : nullptr, nullptr);
-    if (!rc && out_linear && hipMemcpy(out_linear, d_lin.p, n * 12, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(MI355RT_ERR_HIP, "copy back linear");   // (waits for the kernels)
-    if (!rc && out_packed && hipMemcpy(out_packed, d_packed.p, n * 4, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(MI355RT_ERR_HIP, "copy back packed");
-    d_in.release(); d_lin.release(); d_hits.release(); d_packed.release(); d_scratch.release();
-    std::string keep; keep.swap(last_error());                               // (destroy may overwrite the message of the failure being reported; swap never throws)
-    mi355rt_context_destroy(ctx);
-    last_error().swap(keep);
-    return rc;
     });
 }
 
@@ -992,176 +912,6 @@ int mi355rt_context_check(mi355rt_context* ctx) {
     HIP_TRY(hipSetDevice(ctx->device));
     if (ctx->have_last) HIP_TRY(hipEventSynchronize(ctx->done));     // every render enqueued so far has finished and left its error word
     return report_device_error(ctx);
-    });
-}
-
-int mi355rt_render(const mi355rt_scene* scene, const mi355rt_camera* camera, const mi355rt_settings* settings,
-                   const mi355rt_options* opt, uint32_t* out_packed, float* out_linear, mi355rt_stats* stats) {
-    return guard([&]() -> int {
-    if (!out_packed) return fail(MI355RT_ERR_INVALID, "out_packed_rgb is null");
-    int rc = check_settings(settings); if (rc) return rc;
-    uint32_t n_rows = 0;
-    rc = mi355rt_rows_selected(settings, opt, &n_rows); if (rc) return rc;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return fail(MI355RT_ERR_NO_DEVICE, "no HIP device visible (this library has no CPU path)");
-    mi355rt_context* ctx = nullptr;
-    rc = mi355rt_context_create(dev, &ctx); if (rc) return rc;
-    rc = mi355rt_context_set_scene(ctx, scene, camera, settings);
-    uint32_t* d_packed = nullptr; float* d_linear = nullptr;
-    const size_t npix = (size_t)n_rows * settings->width;
-    if (!rc && npix) {
-        if (hipMalloc((void**)&d_packed, npix * 4) != hipSuccess) rc = fail(MI355RT_ERR_OOM, "hipMalloc(out_packed)");
-        if (!rc && out_linear && hipMalloc((void**)&d_linear, npix * 12) != hipSuccess) rc = fail(MI355RT_ERR_OOM, "hipMalloc(out_linear)");
-        mi355rt_stats local{};
-        if (!rc) rc = mi355rt_context_render(ctx, opt, d_packed, d_linear, nullptr, stats ? stats : &local);
-        if (!rc && hipMemcpy(out_packed, d_packed, npix * 4, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(MI355RT_ERR_HIP, "copy back packed");
-        if (!rc && out_linear && hipMemcpy(out_linear, d_linear, npix * 12, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(MI355RT_ERR_HIP, "copy back linear");
-    }
-    if (d_packed) (void)hipFree(d_packed);
-    if (d_linear) (void)hipFree(d_linear);
-    std::string keep; keep.swap(last_error());                               // (destroy may overwrite the message of the failure being reported; swap never throws)
-    mi355rt_context_destroy(ctx);
-    last_error().swap(keep);
-    return rc;
-    });
-}
-
-// One host process, several GPUs (the shape of the reference's own host: a single `main`, src/main.rs:22-89).
-// Row strips are dealt round-robin over `hip_devices` exactly as the one-process-per-GPU path deals them over ranks
-// (options.strip_rows; 0 -> 4); every device gets the full scene, renders its strips on its own host thread and
-// copies them straight into the caller's row-major image -- the exchange step is the device-to-host copy, no
-// collective.  The image is bit-identical to the one-device image (draws are keyed by absolute row / x / sample).
-int mi355rt_render_multi(const mi355rt_scene* scene, const mi355rt_camera* camera, const mi355rt_settings* settings,
-                         const mi355rt_options* opt, const int* hip_devices, uint32_t n_devices,
-                         uint32_t* out_packed, float* out_linear, mi355rt_stats* stats) {
-    return guard([&]() -> int {
-    if (!out_packed) return fail(MI355RT_ERR_INVALID, "out_packed_rgb is null");
-    if (!hip_devices || n_devices == 0) return fail(MI355RT_ERR_INVALID, "hip_devices is empty");
-    int rc = check_settings(settings); if (rc) return rc;
-    mi355rt_options base{};
-    if (opt) base = *opt; else { base.abi_version = MI355RT_ABI_VERSION; base.rng_mode = MI355RT_RNG_CTR; }
-    if (base.n_parts > 1) return fail(MI355RT_ERR_INVALID, "render_multi deals the strips itself: leave options.n_parts / part at 0");
-    if (base.strip_rows == 0) base.strip_rows = 4;
-    RowSel all; rc = select_rows(*settings, &base, all); if (rc) return rc;       // the rows the caller's buffer holds (row window)
-    int visible = 0;
-    if (hipGetDeviceCount(&visible) != hipSuccess || visible == 0) return fail(MI355RT_ERR_NO_DEVICE, "no HIP device visible (this library has no CPU path)");
-    for (uint32_t d = 0; d < n_devices; ++d)
-        if (hip_devices[d] < 0 || hip_devices[d] >= visible) return fail(MI355RT_ERR_INVALID, "hip_devices entry out of range");
-    const uint32_t W = settings->width, row0 = all.rows.empty() ? 0u : all.rows.front();
-
-    struct Part { int rc = MI355RT_OK; std::string err; mi355rt_stats st{}; };
-    std::vector<Part> parts(n_devices);
-    auto work_body = [&](uint32_t d, mi355rt_context*& ctx, uint32_t*& d_packed, float*& d_linear) {
-        Part& me = parts[d];
-        mi355rt_options o = base; o.n_parts = n_devices; o.part = d;
-        RowSel sel;
-        if ((me.rc = select_rows(*settings, &o, sel))) { me.err = last_error(); return; }
-        if (sel.rows.empty()) return;
-        const size_t npix = sel.rows.size() * (size_t)W;
-        std::vector<uint32_t> h_packed(npix); std::vector<float> h_linear(out_linear ? npix * 3 : 0);
-        me.rc = mi355rt_context_create(hip_devices[d], &ctx);
-        if (!me.rc) me.rc = mi355rt_context_set_scene(ctx, scene, camera, settings);
-        if (!me.rc && hipMalloc((void**)&d_packed, npix * 4) != hipSuccess) me.rc = fail(MI355RT_ERR_OOM, "hipMalloc(out_packed)");
-        if (!me.rc && out_linear && hipMalloc((void**)&d_linear, npix * 12) != hipSuccess) me.rc = fail(MI355RT_ERR_OOM, "hipMalloc(out_linear)");
-        if (!me.rc) me.rc = mi355rt_context_render(ctx, &o, d_packed, d_linear, nullptr, &me.st);
-        if (!me.rc && hipMemcpy(h_packed.data(), d_packed, npix * 4, hipMemcpyDeviceToHost) != hipSuccess) me.rc = fail(MI355RT_ERR_HIP, "copy back packed");
-        if (!me.rc && out_linear && hipMemcpy(h_linear.data(), d_linear, npix * 12, hipMemcpyDeviceToHost) != hipSuccess) me.rc = fail(MI355RT_ERR_HIP, "copy back linear");
-        if (me.rc) me.err = last_error();
-        else for (size_t j = 0; j < sel.rows.size(); ++j) {                        // de-interleave: local row j is image row sel.rows[j]
-            const size_t dst = (size_t)(sel.rows[j] - row0) * W;
-            std::memcpy(out_packed + dst, h_packed.data() + j * W, (size_t)W * 4);
-            if (out_linear) std::memcpy(out_linear + dst * 3, h_linear.data() + j * W * 3, (size_t)W * 12);
-        }
-    };
-    // One part, on whatever thread runs it.  Nothing may leave this function by exception -- on a worker thread that would be
-    // std::terminate -- and the device buffers are released on every path.
-    auto work = [&](uint32_t d) noexcept {
-        mi355rt_context* ctx = nullptr; uint32_t* d_packed = nullptr; float* d_linear = nullptr;
-        const int rc = guard([&]() -> int { work_body(d, ctx, d_packed, d_linear); return MI355RT_OK; });
-        if (rc != MI355RT_OK && parts[d].rc == MI355RT_OK) { parts[d].rc = rc; try { parts[d].err = last_error(); } catch (...) {} }
-        if (d_packed) (void)hipFree(d_packed);
-        if (d_linear) (void)hipFree(d_linear);
-        if (ctx) mi355rt_context_destroy(ctx);
-    };
-    // One host thread per further device.  A thread that cannot be had (std::system_error: EAGAIN under a thread / process limit) is not
-    // an error: that part is rendered on the calling thread instead, after the threads that did start have been joined -- a joinable
-    // std::thread must never be destroyed (std::terminate).
-    std::vector<std::thread> threads;
-    std::vector<uint32_t> inline_parts;
-    try { threads.reserve(n_devices); } catch (...) {}
-    for (uint32_t d = 1; d < n_devices; ++d) {
-        try { threads.emplace_back(work, d); }
-        catch (...) { try { inline_parts.push_back(d); } catch (...) { for (auto& t : threads) t.join(); throw; } }
-    }
-    work(0);
-    for (auto& t : threads) t.join();
-    for (uint32_t d : inline_parts) work(d);
-
-    mi355rt_stats total{};
-    for (uint32_t d = 0; d < n_devices; ++d) {
-        if (parts[d].rc) return fail(parts[d].rc, "device " + std::to_string(hip_devices[d]) + ": " + parts[d].err);
-        const mi355rt_stats& s = parts[d].st;
-        total.render_kernel_ms = std::max(total.render_kernel_ms, s.render_kernel_ms);     // the devices run side by side
-        total.resolve_kernel_ms = std::max(total.resolve_kernel_ms, s.resolve_kernel_ms);
-        total.total_ms = std::max(total.total_ms, s.total_ms);
-        total.samples += s.samples; total.rays += s.rays; total.rows_rendered += s.rows_rendered; total.bands += s.bands;
-        total.grid_blocks = std::max(total.grid_blocks, s.grid_blocks); total.block_threads = s.block_threads ? s.block_threads : total.block_threads;
-        total.kernel_vgprs = s.kernel_vgprs ? s.kernel_vgprs : total.kernel_vgprs; total.kernel_sgprs = s.kernel_sgprs ? s.kernel_sgprs : total.kernel_sgprs;
-    }
-    if (stats) *stats = total;
-    return MI355RT_OK;
-    });
-}
-
-// Host-buffer progressive render: what a preview window (src/main.rs:60-75) would be fed from.
-int mi355rt_render_progressive(const mi355rt_scene* scene, const mi355rt_camera* camera, const mi355rt_settings* settings,
-                               const mi355rt_options* opt, uint32_t chunk_spp, mi355rt_progress_fn on_chunk, void* user,
-                               uint32_t* out_packed, float* out_linear, mi355rt_stats* stats) {
-    return guard([&]() -> int {
-    if (!out_packed) return fail(MI355RT_ERR_INVALID, "out_packed_rgb is null");
-    if (chunk_spp == 0) return fail(MI355RT_ERR_INVALID, "chunk_spp is 0");
-    int rc = check_settings(settings); if (rc) return rc;
-    uint32_t n_rows = 0;
-    rc = mi355rt_rows_selected(settings, opt, &n_rows); if (rc) return rc;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return fail(MI355RT_ERR_NO_DEVICE, "no HIP device visible (this library has no CPU path)");
-    mi355rt_context* ctx = nullptr;
-    rc = mi355rt_context_create(dev, &ctx); if (rc) return rc;
-    rc = mi355rt_context_set_scene(ctx, scene, camera, settings);
-    uint32_t* d_packed = nullptr; float* d_linear = nullptr; float* d_accum = nullptr;
-    const size_t npix = (size_t)n_rows * settings->width;
-    mi355rt_stats total{};
-    if (!rc && npix) {
-        if (hipMalloc((void**)&d_packed, npix * 4) != hipSuccess) rc = fail(MI355RT_ERR_OOM, "hipMalloc(out_packed)");
-        if (!rc && hipMalloc((void**)&d_accum, npix * 16) != hipSuccess) rc = fail(MI355RT_ERR_OOM, "hipMalloc(accum)");
-        if (!rc && out_linear && hipMalloc((void**)&d_linear, npix * 12) != hipSuccess) rc = fail(MI355RT_ERR_OOM, "hipMalloc(out_linear)");
-        const uint32_t spp = settings->samples_per_pixel;
-        for (uint32_t s0 = 0; !rc && s0 < spp; ) {
-            const uint32_t s1 = s0 + std::min(chunk_spp, spp - s0);
-            mi355rt_stats st{};
-            rc = mi355rt_context_render_progressive(ctx, opt, s0, s1, d_accum, d_packed, d_linear, nullptr, &st);
-            if (rc) break;
-            total.render_kernel_ms += st.render_kernel_ms; total.resolve_kernel_ms += st.resolve_kernel_ms; total.total_ms += st.total_ms;
-            total.samples += st.samples; total.rays += st.rays; total.bands += st.bands;
-            total.rows_rendered = st.rows_rendered; total.grid_blocks = st.grid_blocks; total.block_threads = st.block_threads;
-            total.kernel_vgprs = st.kernel_vgprs; total.kernel_sgprs = st.kernel_sgprs;
-            const bool last = s1 == spp;
-            if (on_chunk || last) {
-                if (hipMemcpy(out_packed, d_packed, npix * 4, hipMemcpyDeviceToHost) != hipSuccess) { rc = fail(MI355RT_ERR_HIP, "copy back packed"); break; }
-                if (out_linear && hipMemcpy(out_linear, d_linear, npix * 12, hipMemcpyDeviceToHost) != hipSuccess) { rc = fail(MI355RT_ERR_HIP, "copy back linear"); break; }
-            }
-            s0 = s1;
-            if (on_chunk && on_chunk(user, s1, spp, out_packed) != 0) break;            // the caller stops early: outputs hold s1 samples
-        }
-    }
-    if (stats) *stats = total;
-    if (d_packed) (void)hipFree(d_packed);
-    if (d_linear) (void)hipFree(d_linear);
-    if (d_accum) (void)hipFree(d_accum);
-    std::string keep; keep.swap(last_error());                               // (destroy may overwrite the message of the failure being reported; swap never throws)
-    mi355rt_context_destroy(ctx);
-    last_error().swap(keep);
-    return rc;
     });
 }
 

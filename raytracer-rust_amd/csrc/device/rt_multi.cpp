@@ -1,7 +1,7 @@
 // rt_multi.cpp -- the resident multi-device form of include/mi355rt.h (mi355rt_multi_context_*), part of libmi355rt.so.
 //
 // One host process drives several GPUs (the reference's host is a single `main`, src/main.rs:57) and keeps across calls what
-// mi355rt_render_multi rebuilds on every call.  Every entry of the device list is one PART: its own mi355rt_context (scene uploaded
+// mi355rt_render_multi (rt_oneshot.cpp) rebuilds on every call.  Every entry of the device list is one PART: its own mi355rt_context (scene uploaded
 // once), a non-blocking stream, a staging buffer for its rows (packed, and linear when asked for; it only grows) and a done-event.
 // The destination device (the first entry) keeps a staging area with every part's rows back to back and the row table of
 // k_gather_strips (src_row[r] = the staging row of output row r), uploaded only when the row selection changes.
@@ -23,14 +23,14 @@
 // of mi355rt_context_render; the sums stay on the part between chunks.  When the caller asks for the sums, step 3 adds one peer copy per part
 // straight from `accum` into a staging area of the destination (`stage_accum`, the same row order as the image staging) and step 4 one
 // k_gather_accum launch with the same row table.  The sequence (the sample_end and the options of the last chunk) is kept here, so that a
-// chunk that does not continue it is refused before anything is enqueued.
+// chunk that does not continue it is refused before anything is enqueued.  The one-shot form with host buffers,
+// mi355rt_render_progressive_multi, is a client of these entry points and lives in rt_oneshot.cpp.
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
 #include <chrono>
 #include <cstring>
 #include <string>
-#include <thread>
 #include <vector>
 
 #include "../../../include/mi355rt.h"
@@ -51,13 +51,6 @@ struct Part {
     DevBuf<uint32_t> packed; DevBuf<float> linear;    // this part's rows, on `device`
     DevBuf<float> accum;                              // this part's running sums of a progressive sequence: 4 floats per pixel of its rows, on `device`
     double kernel_ms = 0;                             // render + resolve kernel ms of the last render with stats (diagnostic hook below)
-};
-
-// The calling thread's current device, put back on every way out of an entry point.
-struct DeviceScope {
-    int dev = -1;
-    DeviceScope() { if (hipGetDevice(&dev) != hipSuccess) { dev = -1; (void)hipGetLastError(); } }
-    ~DeviceScope() { if (dev >= 0) (void)hipSetDevice(dev); }
 };
 
 std::string part_name(const Part& p, size_t i) { return "device " + std::to_string(p.device) + " (part " + std::to_string(i) + ")"; }
@@ -121,16 +114,6 @@ int enable_peer(int a, int b) {
     const hipError_t e = hipDeviceEnablePeerAccess(b, 0);
     if (e == hipErrorPeerAccessAlreadyEnabled) { (void)hipGetLastError(); return MI355RT_OK; }
     HIP_TRY(e);
-    return MI355RT_OK;
-}
-
-// The options every part passes through, made from the caller's: the strips are dealt here (n_parts / part must be left 0), strip_rows 0 -> 4.
-int base_options(const mi355rt_options* opt, const char* who, mi355rt_options& base) {
-    base = mi355rt_options{};
-    if (opt) base = *opt; else { base.abi_version = MI355RT_ABI_VERSION; base.rng_mode = MI355RT_RNG_CTR; }
-    if (base.n_parts > 1 || base.part != 0) return fail(MI355RT_ERR_INVALID, std::string(who) + " deals the strips itself: leave options.n_parts / part at 0");
-    if (base.strip_rows == 0) base.strip_rows = 4;
-    base.n_parts = 1; base.part = 0;
     return MI355RT_OK;
 }
 
@@ -320,7 +303,7 @@ int mi355rt_multi_context_set_scene(mi355rt_multi_context* m, const mi355rt_scen
     struct Result { int rc = MI355RT_OK; std::string err; };
     std::vector<Result> res(m->parts.size());
     // One part, on whatever thread runs it: nothing may leave by exception (on a worker thread that would be std::terminate).
-    auto work = [&](size_t i) noexcept {
+    run_parts(m->parts.size(), [&](size_t i) noexcept {               // (rt_host.h: a host thread per further part)
         const int rc = guard([&]() -> int {
             const int r = mi355rt_context_set_scene(m->parts[i].ctx, scene, camera, settings);
             if (r) res[i].err = mi355rt_last_error();
@@ -328,19 +311,7 @@ int mi355rt_multi_context_set_scene(mi355rt_multi_context* m, const mi355rt_scen
         });
         res[i].rc = rc;
         if (rc && res[i].err.empty()) { try { res[i].err = mi355rt_last_error(); } catch (...) {} }
-    };
-    // One host thread per further part; a thread that cannot be had (EAGAIN under a thread limit) is not an error: that part is uploaded
-    // on the calling thread after the others have been joined (as in mi355rt_render_multi).
-    std::vector<std::thread> threads;
-    std::vector<size_t> inline_parts;
-    try { threads.reserve(m->parts.size()); } catch (...) {}
-    for (size_t i = 1; i < m->parts.size(); ++i) {
-        try { threads.emplace_back(work, i); }
-        catch (...) { try { inline_parts.push_back(i); } catch (...) { for (auto& t : threads) t.join(); throw; } }
-    }
-    work(0);
-    for (auto& t : threads) t.join();
-    for (size_t i : inline_parts) work(i);
+    });
     for (size_t i = 0; i < m->parts.size(); ++i)
         if (res[i].rc) return fail(res[i].rc, part_name(m->parts[i], i) + ": " + res[i].err);
     m->settings = *settings;
@@ -415,59 +386,6 @@ int mi355rt_multi_context_check(mi355rt_multi_context* m) {
         return MI355RT_OK;
     }();
     if (rc) m->seq_on = false;                                         // the sums of a failed chunk are not to be continued
-    return rc;
-    });
-}
-
-// Host-buffer progressive render over several GPUs: mi355rt_render_progressive (rt_api.cpp) on a multi context -- what a preview window
-// (src/main.rs:60-75) over a node would be fed from.  The sums stay on the parts (no d_accum); every chunk waits (stats) and is copied back.
-int mi355rt_render_progressive_multi(const mi355rt_scene* scene, const mi355rt_camera* camera, const mi355rt_settings* settings,
-                                     const mi355rt_options* opt, const int* hip_devices, uint32_t n_devices, uint32_t chunk_spp,
-                                     mi355rt_progress_fn on_chunk, void* user, uint32_t* out_packed, float* out_linear, mi355rt_stats* stats) {
-    return guard([&]() -> int {
-    if (!out_packed) return fail(MI355RT_ERR_INVALID, "out_packed_rgb is null");
-    if (chunk_spp == 0) return fail(MI355RT_ERR_INVALID, "chunk_spp is 0");
-    if (!hip_devices || n_devices == 0) return fail(MI355RT_ERR_INVALID, "hip_devices is empty");
-    if (int rc = check_settings(settings)) return rc;
-    mi355rt_options base;
-    if (int rc = base_options(opt, "render_progressive_multi", base)) return rc;
-    RowSel all;
-    if (int rc = select_rows(*settings, &base, all)) return rc;
-    if (base.rng_mode != MI355RT_RNG_CTR)
-        return fail(MI355RT_ERR_INVALID, "progressive rendering needs MI355RT_RNG_CTR (the reference stream of a row is sequential over its pixels)");
-    DeviceScope scope;
-    mi355rt_multi_context* m = nullptr;
-    if (int rc = mi355rt_multi_context_create(hip_devices, n_devices, &m)) return rc;        // (no device: MI355RT_ERR_NO_DEVICE, no CPU path)
-    int rc = mi355rt_multi_context_set_scene(m, scene, camera, settings);
-    uint32_t* d_packed = nullptr; float* d_linear = nullptr;
-    const size_t npix = all.rows.size() * (size_t)settings->width;
-    mi355rt_stats total{};
-    if (!rc && npix) {
-        if (hipSetDevice(hip_devices[0]) != hipSuccess) rc = fail(MI355RT_ERR_HIP, "hipSetDevice(hip_devices[0])");
-        if (!rc && hipMalloc((void**)&d_packed, npix * 4) != hipSuccess) rc = fail(MI355RT_ERR_OOM, "hipMalloc(out_packed)");
-        if (!rc && out_linear && hipMalloc((void**)&d_linear, npix * 12) != hipSuccess) rc = fail(MI355RT_ERR_OOM, "hipMalloc(out_linear)");
-        const uint32_t spp = settings->samples_per_pixel;
-        for (uint32_t s0 = 0; !rc && s0 < spp; ) {
-            const uint32_t s1 = s0 + std::min(chunk_spp, spp - s0);
-            mi355rt_stats st{};
-            rc = mi355rt_multi_context_render_progressive(m, &base, s0, s1, nullptr, d_packed, d_linear, nullptr, &st);   // (waits: stats)
-            if (rc) break;
-            total.render_kernel_ms += st.render_kernel_ms; total.resolve_kernel_ms += st.resolve_kernel_ms; total.total_ms += st.total_ms;
-            total.samples += st.samples; total.rays += st.rays; total.bands += st.bands;
-            total.rows_rendered = st.rows_rendered;
-            const bool last = s1 == spp;
-            if (on_chunk || last) {
-                if (hipMemcpy(out_packed, d_packed, npix * 4, hipMemcpyDeviceToHost) != hipSuccess) { rc = fail(MI355RT_ERR_HIP, "copy back packed"); break; }
-                if (out_linear && hipMemcpy(out_linear, d_linear, npix * 12, hipMemcpyDeviceToHost) != hipSuccess) { rc = fail(MI355RT_ERR_HIP, "copy back linear"); break; }
-            }
-            s0 = s1;
-            if (on_chunk && on_chunk(user, s1, spp, out_packed) != 0) break;            // the caller stops early: outputs hold s1 samples
-        }
-    }
-    if (stats) *stats = total;
-    if (d_packed) (void)hipFree(d_packed);
-    if (d_linear) (void)hipFree(d_linear);
-    mi355rt_multi_context_destroy(m);                                  // (keeps the message of a failure being reported)
     return rc;
     });
 }
