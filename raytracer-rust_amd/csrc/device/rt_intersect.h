@@ -88,13 +88,20 @@ DI bool hit_plane(cprim_t pr, uint32_t i, f3 ro, f3 rd, float t_min, Cand& c) {
 // is not of unit scale: rt_prepare.cpp prepare_scene), so the divisor is in range; a
 // numerator below 2^-100 gives a |t| below 2^-86 either way (rejected: t <= t_min), one of 2^100 or more sends the whole wave to the
 // compiler's division (ballot); infinities and NaN come out of v_div_fixup_f32 as they do there.
-template <bool FASTD = false>
-DI bool hit_quad(cprim_t pr, uint32_t i, f3 ro, f3 rd, float t_min, Cand& c) {
+// BOUNDED (k_render_ctr_simple_qc, whose lists the host admits only with |d| <= 2^99 in every quad: rt_prepare.cpp, walk_bounded): the numerator's range
+// is decided ONCE per walk from the ray's origin (`wide`, wave-uniform: walk_origin_wide()).  In a wave that is not wide every |ro| component is below
+// 2^60 and every normal component at most 2^20 (the host refuses more; the argument holds up to 2^25), so each product of n . ro is below 2^85 and their
+// rounded sum at most 3 * 2^85 * (1 + 2^-21) < 2^87; with |d| <= 2^99 the computed |num| is at most 2^99 + 2^87 rounded, below 2^100: div_bounded()'s
+// proven range.  The small end and the divisor are as above.  So t = div_bounded() straight down, and a wide wave (an origin beyond 2^60, infinite or
+// NaN) overwrites it with the compiler's division.
+template <bool FASTD = false, bool BOUNDED = false>
+DI bool hit_quad(cprim_t pr, uint32_t i, f3 ro, f3 rd, float t_min, Cand& c, bool wide = false) {
     const rec16_t q = load_rec16(pr);                                                               // the whole record: ONE scalar load
     f3 n = mk(q[0], q[1], q[2]);
     float denom = dot(n, rd);
     const float num = q[3] - dot(n, ro);
     float t;
+    if constexpr (FASTD && BOUNDED) { t = div_bounded(num, denom); keep_computed(t); if (__builtin_expect(wide, 0)) t = num / denom; } else
     if (FASTD && __builtin_expect(__ballot(fabsf(num) >= 0x1p100f) == 0ull, 1)) t = div_bounded(num, denom); else
     t = num / denom;
     // Branch-free, and since round 5 also in the ISA: the predicate is built with `&` / `|` on the comparison results, not `&&` / `||`.  With the
@@ -159,14 +166,18 @@ DI uint32_t cube_axis(f3 po) {                                                  
     return (fabsf(ax - 0.5f) < tol) ? 0u : (fabsf(ay - 0.5f) < tol) ? 1u : (fabsf(az - 0.5f) < tol) ? 2u
          : (ax > ay && ax > az) ? 0u : (ay > az) ? 1u : 2u;
 }
-template <bool FASTR = false, class C>
+// BOUNDED (k_render_ctr_simple_qc; the host admits a list only with every entry of the 3 x 3 part of w2o and of zd at most 2^100 in magnitude): rd_w went through
+// normalized() twice (ray_direction), so it is a unit vector up to rounding, a vector shorter than 1e-4 passed through, or NaN; every component of the
+// object-space direction is then below 3 * 2^100 * (1 + 2^-21) < 2^126 or NaN -- or, where an entry of the record itself is NaN or infinite (the host lets those
+// through: a cube of zero scale on one axis), NaN or infinite, on which the short reciprocal is exact as well -- and recip3 only has to look for denormals.
+template <bool FASTR = false, bool BOUNDED = false, class C>
 DI bool hit_cube(cprim_t pr, uint32_t i, f3 ro_w, f3 rd_w, float t_min, C& c) {
     const rec16_t m = load_rec16(pr);                                                               // w2o (3 x 4) and zd: ONE scalar load
     f3 ro = mk(((m[0] * ro_w.x + m[3] * ro_w.y) + m[6] * ro_w.z) + m[9], ((m[1] * ro_w.x + m[4] * ro_w.y) + m[7] * ro_w.z) + m[10],
                ((m[2] * ro_w.x + m[5] * ro_w.y) + m[8] * ro_w.z) + m[11]);                             // xform_w2o_point
     f3 rd = mk(((m[0] * rd_w.x + m[3] * rd_w.y) + m[6] * rd_w.z) + m[12], ((m[1] * rd_w.x + m[4] * rd_w.y) + m[7] * rd_w.z) + m[13],
                ((m[2] * rd_w.x + m[5] * rd_w.y) + m[8] * rd_w.z) + m[14]);                             // xform_w2o_dir
-    float ix, iy, iz; recip3<FASTR>(rd.x, rd.y, rd.z, ix, iy, iz);                  // (FASTR: the kernels of mesh-free lists, like normalized<FASTN>)
+    float ix, iy, iz; recip3<FASTR, BOUNDED>(rd.x, rd.y, rd.z, ix, iy, iz);                  // (FASTR: the kernels of mesh-free lists, like normalized<FASTN>)
     float t1x = (-0.5f - ro.x) * ix, t2x = (0.5f - ro.x) * ix;
     float t1y = (-0.5f - ro.y) * iy, t2y = (0.5f - ro.y) * iy;
     float t1z = (-0.5f - ro.z) * iz, t2z = (0.5f - ro.z) * iz;
@@ -411,7 +422,9 @@ DI uint32_t prim_material_kind(const RenderParams& P, uint32_t idx) { return __f
 // test would have left.  All ones (the default, which folds away) everywhere but in the camera pass of k_render_ctr_simple_qc, whose rays leave one
 // origin through one or two pixels and take the pixels' words of RenderParams.cam_mask (rt_prepare.cpp build_camera_masks).  Lists longer than 32 get
 // no table (the host), so a shift by i >= 32 is never executed.
-template <bool HAS_MESH, uint32_t KINDS = PRIMS_ALL, class C>
+// BOUNDED: see hit_quad / hit_cube.  The one test of the walk: does any active lane's origin leave [0, 2^60)?  (`!(... < ...)`: a NaN or infinite origin counts.)
+DI bool walk_origin_wide(f3 ro) { return __ballot(!(fmaxf(fmaxf(fabsf(ro.x), fabsf(ro.y)), fabsf(ro.z)) < 0x1p60f)) != 0ull; }
+template <bool HAS_MESH, uint32_t KINDS = PRIMS_ALL, bool BOUNDED = false, class C>
 DI void walk_list(cprim_t prims, uint32_t n_prims, const DevNode* __restrict__ nodes, const DevTri* __restrict__ tris, f3 ro, f3 rd, C& c, uint32_t pmask = ~0u) {
 #define MI_KIND(k) (((KINDS >> (k)) & 1u) != 0u)
     // Same order as the list, but the dispatch on the kind (wave-uniform: a scalar branch) is taken once per RUN of equal kinds
@@ -421,11 +434,13 @@ DI void walk_list(cprim_t prims, uint32_t n_prims, const DevNode* __restrict__ n
     // structured control flow (a `switch` here is lowered to a chain of flow blocks, each with its own copies of the candidate).
     // (Round 5 measured the tidier form again -- ONE read of the run's header, kind and run_end together, and a wave-uniform `else if` chain over the
     // kinds: cornell +2.8 %, profiles/r05/ab_scalar_diet.txt.)
+    static_assert(!BOUNDED || !HAS_MESH, "BOUNDED belongs to the short forms of the mesh-free kernels");
+    const bool wide = BOUNDED && MI_KIND(MI355RT_PRIM_QUAD) && walk_origin_wide(ro);
     uint32_t i = 0;
     while (i < n_prims) {
-#define MI_RUN(KIND, CALL) if (i < n_prims && prims[i].kind == (KIND)) { const uint32_t end = min(prims[i].run_end, n_prims); do { if ((pmask >> i) & 1u) { CALL; } } while (++i < end); }
-        if (MI_KIND(MI355RT_PRIM_QUAD)) { MI_RUN(MI355RT_PRIM_QUAD,   hit_quad<!HAS_MESH>(prims + i, i, ro, rd, EPS, c)) }
-        if (MI_KIND(MI355RT_PRIM_CUBE)) { MI_RUN(MI355RT_PRIM_CUBE,   hit_cube<!HAS_MESH>(prims + i, i, ro, rd, EPS, c)) }
+#define MI_RUN(KIND, ...) if (i < n_prims && prims[i].kind == (KIND)) { const uint32_t end = min(prims[i].run_end, n_prims); do { if ((pmask >> i) & 1u) { __VA_ARGS__; } } while (++i < end); }
+        if (MI_KIND(MI355RT_PRIM_QUAD)) { MI_RUN(MI355RT_PRIM_QUAD,   hit_quad<!HAS_MESH, BOUNDED>(prims + i, i, ro, rd, EPS, c, wide)) }
+        if (MI_KIND(MI355RT_PRIM_CUBE)) { MI_RUN(MI355RT_PRIM_CUBE,   hit_cube<!HAS_MESH, BOUNDED>(prims + i, i, ro, rd, EPS, c)) }
         if (MI_KIND(MI355RT_PRIM_SPHERE)) { MI_RUN(MI355RT_PRIM_SPHERE, hit_sphere(prims + i, i, ro, rd, EPS, c)) }
         if (MI_KIND(MI355RT_PRIM_PLANE)) { MI_RUN(MI355RT_PRIM_PLANE,  hit_plane(prims + i, i, ro, rd, EPS, c)) }
         if (HAS_MESH) { MI_RUN(MI355RT_PRIM_MESH, hit_mesh(prims + i, i, nodes, tris, ro, rd, EPS, c)) }
@@ -438,11 +453,11 @@ DI void walk_list(cprim_t prims, uint32_t n_prims, const DevNode* __restrict__ n
 // CARRY_PO: the candidate keeps the cube's object-space hit point (CandP).  On for both mesh-free kernels: the Lambert-only one
 // (cornell -1.8 % at 72 VGPRs) and the general one, which needs 80 VGPRs = 6 waves per SIMD for it (veach-mis: +1.9 % at 72 with
 // spills, -2.6 % at 80; see MI355RT_OCC_LOCKSTEP).
-template <bool HAS_MESH, bool CARRY_PO = false, uint32_t KINDS = PRIMS_ALL>
+template <bool HAS_MESH, bool CARRY_PO = false, uint32_t KINDS = PRIMS_ALL, bool BOUNDED = false>
 DI bool hit_scene(cprim_t prims, uint32_t n_prims, const DevNode* __restrict__ nodes, const DevTri* __restrict__ tris,
                   f3 ro, f3 rd, Hit& best, uint32_t pmask = ~0u) {
     typename std::conditional<CARRY_PO && !HAS_MESH, CandP, Cand>::type c; cand_reset(c);
-    walk_list<HAS_MESH, KINDS>(prims, n_prims, nodes, tris, ro, rd, c, pmask);
+    walk_list<HAS_MESH, KINDS, BOUNDED>(prims, n_prims, nodes, tris, ro, rd, c, pmask);
     if (c.idx == CAND_NONE) return false;
     finish_hit<HAS_MESH, !HAS_MESH, !HAS_MESH, KINDS>((const DevPrim*)prims, tris, c, ro, rd, best);          // (the lockstep kernels' entry: q0 rides along when there is no mesh)
     return true;

@@ -529,7 +529,7 @@ DI bool shade_and_regenerate(const RenderParams& P, WC& wc, uint32_t lane, bool&
 // point (also in the general kernel: pays at 80 VGPRs); the short reciprocal / square root / division of rt_math.h; in the Lambert-only kernel ONE try of the
 // unit-ball draw in the lane itself before the cooperative rounds (0 tries: +1.9 %, 2 tries: +-0 with pcg4d, +23 % with Philox: profiles/r05/ab_counter_generator.txt).
 // PREHIT: the wave stocks its camera rays' first hits (HitStock), walked in refill passes through the loop's one walk site.
-template <bool HAS_MESH, uint32_t MATS, uint32_t KINDS = PRIMS_ALL, bool PREHIT = false>
+template <bool HAS_MESH, uint32_t MATS, uint32_t KINDS = PRIMS_ALL, bool PREHIT = false, bool BOUNDED = false>
 DI void render_ctr_lockstep(const RenderParams& P) {
     constexpr bool SIMPLE = (MATS & ~MATS_LAMBERT) == 0u;
     // The mesh-free kernels are compiled for lists that hold something and for paths that may take a step: the host sends an empty list or max_depth == 0 to
@@ -587,7 +587,7 @@ DI void render_ctr_lockstep(const RenderParams& P) {
                 if (lane < n_cam) stock.camera(P, wc.next + lane, (wc.ring_head + wc.ring_count + lane) & 63u, ps.ro, ps.rd);
             }
         }
-        if (n_cam != 0u ? lane < n_cam : live) hit = hit_scene<HAS_MESH, true, KINDS>(prims, P.n_prims, P.nodes, P.tris, ps.ro, ps.rd, h, pmask);     // renderer.rs:24
+        if (n_cam != 0u ? lane < n_cam : live) hit = hit_scene<HAS_MESH, true, KINDS, BOUNDED>(prims, P.n_prims, P.nodes, P.tris, ps.ro, ps.rd, h, pmask);     // renderer.rs:24
         prof.mark(1);
         if constexpr (PREHIT) {
             if (n_cam != 0u) {                             // finish or stock the camera paths, take the parked rays back, and walk them next
@@ -638,7 +638,7 @@ __global__ void __launch_bounds__(BLOCK_THREADS) MI355RT_OCC_LS k_render_ctr_nom
 __global__ void __launch_bounds__(BLOCK_THREADS) MI355RT_OCC_SIMPLE k_render_ctr_simple(const RenderParams P) { render_ctr_lockstep<false, MATS_LAMBERT>(P); }
 // ... and the Lambert-only kernel for lists of quads and cubes (round 5: cornell -1.1 %, profiles/r05/ab_scalar_diet.txt r05_q16), with its camera rays'
 // first hits in stock (HitStock: cornell -3.7 %, profiles/ab_stocked_first_hits.txt)
-__global__ void __launch_bounds__(BLOCK_THREADS) MI355RT_OCC_SIMPLE k_render_ctr_simple_qc(const RenderParams P) { render_ctr_lockstep<false, MATS_LAMBERT, PRIMS_QUAD_CUBE, /* PREHIT */ true>(P); }
+__global__ void __launch_bounds__(BLOCK_THREADS) MI355RT_OCC_SIMPLE k_render_ctr_simple_qc(const RenderParams P) { render_ctr_lockstep<false, MATS_LAMBERT, PRIMS_QUAD_CUBE, /* PREHIT */ true, /* BOUNDED */ true>(P); }
 __global__ void __launch_bounds__(BLOCK_THREADS) MI355RT_OCC_SIMPLE k_render_ctr_nospec(const RenderParams P) { render_ctr_lockstep<false, MATS_NO_SPECULAR>(P); }
 __global__ void __launch_bounds__(BLOCK_THREADS) __attribute__((amdgpu_waves_per_eu(6, 6))) k_render_ctr_mesh(const RenderParams P) { render_ctr_lockstep<true, MATS_ALL>(P); }
 

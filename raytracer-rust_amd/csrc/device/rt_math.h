@@ -90,12 +90,28 @@ DI float div_by_rn(float a, float b, float r) {
     return __builtin_amdgcn_div_fixupf(q, b, a);
 }
 
+// "This value is computed here": an empty statement the optimizer cannot see through.  For a short form that a rare wave-uniform branch overwrites --
+// without it the compiler sinks the short form into an `else` of that branch, and the common path is laid out behind the rare one (a taken branch per test).
+DI void keep_computed(float& v) { asm volatile("" : "+v"(v)); }
+
 // 1 / x, 1 / y, 1 / z for ANY arguments: the short form where every lane of the wave has all three in its range (zero counts as
 // in range: v_div_fixup_f32 returns the infinity of the right sign), the compiler's division for the whole wave otherwise -- a
 // wave-uniform branch, so the common case pays three short reciprocals and a range test (two 3-input min / max on the magnitudes).
 // NaN components are ignored by the test and give NaN either way.  (The ballot covers the lanes that are active at the call.)
-template <bool FASTR>
+// BOUNDED (k_render_ctr_simple_qc's cube test): for callers that know every magnitude to be below 2^126 or NaN.  What is then left outside the short
+// form's range is a denormal, and one v_cmp_class_f32 per component finds it.  A wave with a denormal lane takes the compiler's reciprocals, which the
+// compiler lays out of line: the common path falls through the test into the short form.  (With keep_computed() on the three short results, so that they
+// run first and are overwritten, the kernel had 13 SGPR spills instead of 6: not taken.)
+template <bool FASTR, bool BOUNDED = false>
 DI void recip3(float x, float y, float z, float& ix, float& iy, float& iz) {
+    if constexpr (FASTR && BOUNDED) {
+        constexpr int DENORMAL = 0x010 | 0x080;                                             // v_cmp_class_f32: negative denormal, positive denormal
+        ix = recip_normal_range(x); iy = recip_normal_range(y); iz = recip_normal_range(z);
+        // (__builtin_isfpclass, not __builtin_amdgcn_class: this compiler folds the latter's denormal classes to `false`; both select v_cmp_class_f32)
+        const bool small = __builtin_isfpclass(x, DENORMAL) | __builtin_isfpclass(y, DENORMAL) | __builtin_isfpclass(z, DENORMAL);
+        if (__builtin_expect(__ballot(small) != 0ull, 0)) { ix = 1.0f / x; iy = 1.0f / y; iz = 1.0f / z; }
+        return;
+    }
     if constexpr (FASTR) {
     const float ax = fabsf(x), ay = fabsf(y), az = fabsf(z);
     const float mx = fmaxf(fmaxf(ax, ay), az);

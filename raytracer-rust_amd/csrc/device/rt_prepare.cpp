@@ -482,6 +482,10 @@ int prepare_scene(const mi355rt_scene* sc, PreparedScene& out) {
             for (int r = 0; r < 3; ++r) d.d[12 + r] = t[28 + r];
             for (int k = 16; k < 28; ++k) d.d[k] = t[k];
             for (int k = 31; k < 52; ++k) d.d[k] = t[k];
+            if (p.kind == MI355RT_PRIM_CUBE)
+                // (an entry that is NaN or infinite keeps the list: it makes the object-space direction NaN or infinite, never a finite magnitude of 2^126 or
+                //  more, and the short reciprocal is exact on NaN and infinities -- rt_math.h recip_normal_range.  A cube of zero scale on one axis is such a record.)
+                for (int k : {0, 1, 2, 3, 4, 5, 6, 7, 8, 12, 13, 14}) out.walk_bounded = out.walk_bounded && !(std::isfinite(d.d[k]) && std::fabs(d.d[k]) > WALK_CUBE_M_MAX);
             if (p.kind == MI355RT_PRIM_MESH) {
                 if (p.mesh >= sc->n_meshes) return fail(MI355RT_ERR_INVALID, "primitive mesh index");
                 d.node_begin = out.mesh_roots[p.mesh];
@@ -492,6 +496,7 @@ int prepare_scene(const mi355rt_scene* sc, PreparedScene& out) {
             for (int k = 0; k < 4; ++k) d.d[k] = p.data[9 + k];
             for (int k = 0; k < 9; ++k) d.d[4 + k] = p.data[k];
             d.d[13] = p.data[13]; d.d[14] = p.data[14];
+            out.walk_bounded = out.walk_bounded && std::fabs(d.d[3]) <= WALK_QUAD_D_MAX;                       // (false for NaN and infinities too)
         } else {
             std::memcpy(d.d, p.data, 32 * sizeof(float));
         }
@@ -509,6 +514,8 @@ uint32_t choose_variant(const PreparedScene& s, int forced_variant, uint32_t bui
     auto render_ctr_variant_built = [&](uint32_t variant) { return ((built_mask >> variant) & 1u) != 0u; };   // (what rt_kernels.hip says of this library, passed in)
     auto covers = [&](uint32_t variant) { return (scene_mats & ~VARIANT_TABLE[variant].mats) == 0u; };
     auto kinds_covered = [&](uint32_t variant) { return (scene_prim_kinds & ~VARIANT_TABLE[variant].prims) == 0u; };       // likewise for the primitive kinds of the list (a mesh among them)
+    // k_render_ctr_simple_qc tests its argument ranges once per walk instead of once per primitive (rt_intersect.h, BOUNDED), which needs bounded records.
+    auto ranges_ok = [&](uint32_t variant) { return variant != KERNEL_LOCKSTEP_SIMPLE_QC || s.walk_bounded; };
     uint32_t chosen;
     // Scenes with meshes: the wavefront kernel (path state in LDS, stage queues).  No mesh: a lockstep kernel.  In both
     // families the most pruned instantiation whose material set covers the scene's (rt_device.h, VARIANT_TABLE): the branches of
@@ -525,7 +532,7 @@ uint32_t choose_variant(const PreparedScene& s, int forced_variant, uint32_t bui
         // passes run it at ~57 lanes: veach-mis 18.30 -> 16.75 ms at 256 spp.  Cheap mixtures (Lambert + metal + dielectric + plastic)
         // measured 3-7 % FASTER in lockstep (tools/ab_fuzz_scene.py), and so stay there.
         const bool rough = (scene_mats & MATS_ROUGH) != 0u, other_scatter = (scene_mats & ~(MATS_ROUGH | MATS_TERMINAL)) != 0u;
-        chosen = covers(KERNEL_LOCKSTEP_SIMPLE) ? (kinds_covered(KERNEL_LOCKSTEP_SIMPLE_QC) ? KERNEL_LOCKSTEP_SIMPLE_QC : KERNEL_LOCKSTEP_SIMPLE)   // (... pruned to quads and cubes where the list holds nothing else: cornell)
+        chosen = covers(KERNEL_LOCKSTEP_SIMPLE) ? (kinds_covered(KERNEL_LOCKSTEP_SIMPLE_QC) && ranges_ok(KERNEL_LOCKSTEP_SIMPLE_QC) ? KERNEL_LOCKSTEP_SIMPLE_QC : KERNEL_LOCKSTEP_SIMPLE)   // (... pruned to quads and cubes where the list holds nothing else: cornell)
                      : (rough && other_scatter && covers(KERNEL_WAVEFRONT_MESHFREE)) ? KERNEL_WAVEFRONT_MESHFREE
                      : covers(KERNEL_LOCKSTEP_NOSPEC) ? KERNEL_LOCKSTEP_NOSPEC : KERNEL_LOCKSTEP;
     }
@@ -533,7 +540,7 @@ uint32_t choose_variant(const PreparedScene& s, int forced_variant, uint32_t bui
         const uint32_t v = (uint32_t)forced_variant;
         const bool ok = render_ctr_variant_built(v) && VARIANT_TABLE[v].forceable && covers(v) && kinds_covered(v) &&
                         !(VARIANT_TABLE[v].identity_meshes && !(has_mesh && all_meshes_identity));
-        if (ok) chosen = v;
+        if (ok && ranges_ok(v)) chosen = v;
     }
     return chosen;
 }

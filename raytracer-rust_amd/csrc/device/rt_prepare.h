@@ -116,7 +116,12 @@ struct PreparedScene {
     uint32_t scene_prim_kinds = 0u;                                  // ... and which primitive kinds the list holds (bit k = MI355RT_PRIM_k)
     uint32_t n_mesh_prims = 0;
     bool all_meshes_identity = true, all_meshes_shallow = true;
+    // Every quad's plane constant is at most WALK_QUAD_D_MAX in magnitude, and every cube's 3 x 3 part of world_to_object and its zd at most
+    // WALK_CUBE_M_MAX where it is finite (a plane constant that is NaN or infinite is outside): what k_render_ctr_simple_qc's list walk takes for granted (rt_intersect.h, hit_quad / hit_cube
+    // with BOUNDED).  A list that is not goes to k_render_ctr_simple, whose range tests are per primitive.
+    bool walk_bounded = true;
 };
+constexpr float WALK_QUAD_D_MAX = 0x1p99f, WALK_CUBE_M_MAX = 0x1p100f;
 
 // Validates `sc` and builds `out` from it; MI355RT_ERR_INVALID (and the text) for anything a kernel could not be launched on.
 int prepare_scene(const mi355rt_scene* sc, PreparedScene& out);
