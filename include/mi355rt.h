@@ -41,7 +41,9 @@ extern "C" {
                                     mi355rt_render_progressive_multi -- a caller that needs them probes for the symbols (dlsym), not the number.
                                     Likewise the ray queries: mi355rt_context_trace_rays, mi355rt_context_first_hits, mi355rt_trace_rays;
                                     and the denoiser: mi355rt_denoise_scratch_bytes, mi355rt_context_denoise, mi355rt_denoise;
-                                    and the occlusion queries: mi355rt_context_occluded, mi355rt_occluded, mi355rt_context_ambient_occlusion. */
+                                    and the occlusion queries: mi355rt_context_occluded, mi355rt_occluded, mi355rt_context_ambient_occlusion;
+                                    and, in the host library, the noise estimate: mi355rt_noise_create, mi355rt_noise_free, mi355rt_noise_reset,
+                                    mi355rt_noise_update, mi355rt_noise_evaluate. */
 
 /* ---- error codes ------------------------------------------------------------------------- */
 #define MI355RT_OK               0
@@ -588,6 +590,63 @@ int mi355rt_write_png(const char* path, const uint32_t* packed_rgb, uint32_t wid
 int mi355rt_write_pfm(const char* path, const float* linear_rgb, uint32_t width, uint32_t height);
 /* The same image as an OpenEXR file: scan-line, three 32-bit FLOAT channels (B, G, R), uncompressed, rows top-down. */
 int mi355rt_write_exr(const char* path, const float* linear_rgb, uint32_t width, uint32_t height);
+
+/* ---- noise estimate of a progressive render: is this image good enough yet? (added within ABI version 5: probe for the symbols) ------------
+ * For the caller of mi355rt_context_render_progressive that does not want to guess samples_per_pixel: after every chunk it hands a HOST copy
+ * of the running sums (d_accum) to mi355rt_noise_update, and mi355rt_noise_evaluate answers with a per-pixel relative standard error of the
+ * mean luminance and a verdict.  Pure CPU; not part of the reference (src/main.rs renders the file's spp and stops).
+ *
+ * DEFINITION.  All arithmetic is IEEE double, one rounding per operation, in the order written (the library is built without contraction).
+ * State per pixel p: prev[3] (float, the last running sums, 0 at the start), T (the sum of Y) and Q (the sum of Y*Y/n), both 0 at the start.
+ * Global state: K chunks and N samples, both 0 at the start.
+ *   update(accum, samples_total), which needs samples_total > N:   n = samples_total - N;   for c = r, g, b:
+ *       d_c = (double)accum[4p+c] - (double)prev[c];   Y = (0.2126*d_r + 0.7152*d_g) + 0.0722*d_b;
+ *       T += Y;   Q += (Y*Y)/(double)n;   prev = accum;   then K += 1, N = samples_total.   Chunks may differ in size.  accum[4p+3] is not read.
+ *   evaluate, which needs K >= 2:   m = T/N;   ss = Q - (T*T)/N;   var = (ss > 0 ? ss : 0)/(K-1);   se = sqrt(var/N);
+ *       err = se/((m > 0 ? m : 0) + floor).
+ *       A pixel whose T or Q is not finite has err = NaN; so has a pixel whose division is 0/0 (floor = 0 and neither signal nor variance).
+ *       Such a pixel is counted in `nonfinite`, never in `above`, and is left out of max_error and mean_error.
+ *       above = the number of pixels with err > threshold (an err of +inf counts).   max_error = the largest err, 0 when no pixel is counted.
+ *       mean_error = (the sum of err in pixel order) / (pixels - nonfinite), 0 when no pixel is counted.   out_error[p] = (float)err, a NaN as 0x7FC00000.
+ *       converged = (K >= min_chunks && above <= allowed_above).
+ * WHY.  This is the weighted batch-means estimator: the samples of the counter-mode stream are independent, a chunk of n_k samples has the
+ * mean m_k = Y_k/n_k, and the expectation of  sum over k of n_k*(m_k - m)^2  =  Q - T*T/N  is (K-1)*sigma^2, sigma^2 the variance of one
+ * sample's luminance.  So se estimates the standard error of the pixel's mean luminance after N samples, err the same relative to that mean;
+ * `floor` keeps dark pixels from asking for ever more samples.
+ * WHAT IT DOES NOT DO.  A firefly that no chunk has seen yet is not estimated: a pixel can look converged until its first rare bright path
+ * arrives.  A small K gives a noisy estimate (the relative deviation of se is about 1/sqrt(2(K-1))): min_chunks guards the verdict, not the map.
+ * Non-finite pixels (an infinite emitter, a NaN path: mi355rt_scene) are reported in `nonfinite` and do NOT block convergence -- more samples
+ * never make them finite.  It estimates luminance only, over the image before gamma and packing; it knows nothing of a denoiser applied later.
+ * REFUSALS are MI355RT_ERR_INVALID with a text (mi355rt_host_last_error) that names the argument: a null state, out, accum or out_summary;
+ * width or rows 0, width * rows >= 2^31; samples_total not above the samples already seen; evaluate before the second update; threshold not
+ * > 0 or not finite, floor negative or not finite, min_chunks < 2, _pad not 0.  A failed allocation is MI355RT_ERR_OOM.  A refused call
+ * changes nothing.  A state is not thread-safe; different states are independent. */
+typedef struct mi355rt_noise_state mi355rt_noise_state;
+typedef struct mi355rt_noise_params {   /* 32 bytes */
+    double   threshold;      /* > 0, finite: a pixel is `above` when err > threshold */
+    double   floor;          /* >= 0, finite: added to the mean luminance in the denominator */
+    uint32_t min_chunks;     /* >= 2: no verdict of `converged` before this many chunks */
+    uint32_t _pad;           /* must be 0 */
+    uint64_t allowed_above;  /* converged while at most this many pixels are above */
+} mi355rt_noise_params;
+/* params_or_null == NULL: {0.02, 0.01, 4, 0, 0} */
+
+typedef struct mi355rt_noise_summary {  /* 56 bytes */
+    uint32_t chunks, samples;           /* K, N */
+    uint64_t pixels, above, nonfinite;
+    double   max_error, mean_error;
+    uint32_t converged, _pad;           /* 0 / 1; _pad written as 0 */
+} mi355rt_noise_summary;
+
+int  mi355rt_noise_create(uint32_t width, uint32_t rows, mi355rt_noise_state** out);
+void mi355rt_noise_free(mi355rt_noise_state* state);
+/* Back to K = N = 0 and zero sums: the next update starts a new sequence (after a camera or scene change). */
+int  mi355rt_noise_reset(mi355rt_noise_state* state);
+/* accum: rows*width*4 floats, a host copy of d_accum after the chunk that ended at sample_end = samples_total. */
+int  mi355rt_noise_update(mi355rt_noise_state* state, const float* accum, uint32_t samples_total);
+/* out_error_or_null: rows*width floats.  Reads the state only: it may be called after any update, with any params. */
+int  mi355rt_noise_evaluate(const mi355rt_noise_state* state, const mi355rt_noise_params* params_or_null,
+                            float* out_error_or_null, mi355rt_noise_summary* out_summary);
 
 const char* mi355rt_host_last_error(void);
 

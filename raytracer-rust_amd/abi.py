@@ -130,6 +130,23 @@ class DenoiseParams(C.Structure):                         # mi355rt_denoise_para
 DENOISE_DEFAULTS = (5, 5, 2.0, 0.05)
 
 
+class NoiseParams(C.Structure):                           # mi355rt_noise_params, 32 bytes
+    _fields_ = [("threshold", C.c_double), ("floor", C.c_double), ("min_chunks", u32), ("_pad", u32), ("allowed_above", u64)]
+
+    @classmethod
+    def make(cls, threshold=0.02, floor=0.01, min_chunks=4, allowed_above=0):
+        """The defaults are what mi355rt_noise_evaluate uses for a null pointer."""
+        return cls(threshold, floor, min_chunks, 0, allowed_above)
+
+
+NOISE_DEFAULTS = (0.02, 0.01, 4, 0, 0)
+
+
+class NoiseSummary(C.Structure):                          # mi355rt_noise_summary, 56 bytes
+    _fields_ = [("chunks", u32), ("samples", u32), ("pixels", u64), ("above", u64), ("nonfinite", u64),
+                ("max_error", C.c_double), ("mean_error", C.c_double), ("converged", u32), ("_pad", u32)]
+
+
 # mi355rt_progress_fn: int (*)(void* user, uint32_t samples_done, uint32_t samples_total, const uint32_t* packed_rgb)
 ProgressFn = C.CFUNCTYPE(C.c_int, C.c_void_p, u32, u32, C.POINTER(u32))
 

@@ -5,13 +5,23 @@
 //   rt_render <scene.json> [-o out.png] [--width W] [--height H] [--spp N] [--max-depth D]
 //             [--rng ctr|ref] [--seed S] [--skip-unknown] [--chunk N] [--pfm out.pfm] [--exr out.exr] [--gpus N | --devices a,b,..]
 //             [--denoise-out denoised.png]
+//             [--noise-target T [--noise-floor F] [--noise-allow FRACTION] [--min-chunks K] [--max-spp N] [--noise-out map.pfm]]
 // --fix-aabb / --fix-wo3 switch on the two opt-in fixes (MI355RT_FLAG_FIXED_AABB, wo3_four_index_stride): not the reference's image.
 // --gpus N deals row strips over HIP devices 0..N-1 from this one process (mi355rt_render_multi); --devices a,b,... names them
 // (a device may repeat: the strip plan of N GPUs on a one-GPU machine).
 // --chunk N renders N samples per pixel at a time and rewrites the PNG after every chunk (a preview that refines).
 // --denoise-out PATH writes, besides -o, the final image filtered by mi355rt_context_denoise with its defaults, guided by the first hits of the
 // same view (a context on the first device: set_scene, first_hits, denoise).  Without it nothing the tool writes changes.
+// --noise-target T stops a chunked render when its estimated noise is low enough (mi355rt_noise_*, include/mi355rt.h): chunks of --chunk samples
+// (default 16) until at most --noise-allow FRACTION of the pixels (default 0) have a relative standard error of the mean luminance above T, but
+// not before --min-chunks K chunks (default 4) and not past --max-spp N samples (default: the scene's spp).  --noise-floor F is the estimate's
+// floor (default 0.01).  T = 0 never stops on the estimate.  Every output is the image of the samples the run stopped at, bit-identical to a
+// one-shot render of that many; --noise-out PATH.pfm writes the per-pixel error map (grey, NaN where the pixel is not finite).  No preview is
+// written between chunks.  One line `noise: samples=S chunks=K rendered=R above=A nonfinite=F max=.. mean=.. converged=0|1 wall_ms=.. kernel_ms=..`
+// reports the stop (R >= S: what the device traced, the speculative chunk included; kernel_ms covers all of R).
 #include <chrono>
+#include <cmath>
+#include <limits>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -46,11 +56,125 @@ static int denoise_image(int hip_device, const mi355rt_scene* sc, const mi355rt_
     return (rc || what) ? 1 : 0;
 }
 
+// --noise-target: render chunk by chunk until mi355rt_noise_evaluate says converged, or max_spp samples are in.  One context on one device;
+// the device never waits for the host's estimate: while the host looks at the sums of chunk k, chunk k + 1 is already running (one speculative
+// chunk, thrown away when chunk k turns out to be enough).  Per chunk k = 1, 2, ...:
+//   render stream:  mi355rt_context_render_progressive into the output pair [k & 1];  d_accum -> d_snap[k & 1] (device to device);  event E_k
+//   copy stream:    wait E_k;  d_snap[k & 1] -> h_snap[k & 1] (pinned);  event F_k
+//   host:           enqueue chunk k + 1 FIRST (unless chunk k ended at max_spp), then wait F_k, mi355rt_noise_update, mi355rt_noise_evaluate.
+// Chunk k's image is the pair [k & 1]; the speculative chunk k + 1 writes the other pair.  d_snap[k & 1], h_snap[k & 1] and the pair [k & 1]
+// are next written by chunk k + 2, and chunk k + 2 is enqueued only after the host has waited for F_k and consumed snapshot k -- so two of
+// each are enough and nothing is overwritten while it is still read.
+struct ConvergeArgs { uint32_t chunk, max_spp; mi355rt_noise_params params; std::string noise_out; };
+struct ConvergeResult { mi355rt_noise_summary summary; uint32_t rendered; double wall_ms, render_ms, resolve_ms, update_ms, evaluate_ms; };
+
+static int render_converging(int hip_device, const mi355rt_scene* sc, const mi355rt_camera* cam, const mi355rt_settings* st, const mi355rt_options* opt,
+                             const ConvergeArgs& a, uint32_t* out_packed, float* out_linear_or_null, ConvergeResult* res) {
+    const size_t n = (size_t)st->width * st->height;
+    mi355rt_context* ctx = nullptr; mi355rt_noise_state* noise = nullptr;
+    void *d_accum = nullptr, *d_packed[2] = {}, *d_linear[2] = {}, *d_snap[2] = {}, *h_snap[2] = {};
+    hipStream_t s_render = nullptr, s_copy = nullptr; hipEvent_t E[2] = {}, F[2] = {};
+    std::vector<float> error_map(a.noise_out.empty() ? 0 : n);
+    const char* what = nullptr; int rc = 0, host_rc = 0;
+    *res = ConvergeResult{};
+    auto hip_ok = [&](hipError_t e, const char* w) { if (e != hipSuccess && !what) what = w; return e == hipSuccess; };
+    const auto t0 = std::chrono::steady_clock::now();
+    rc = mi355rt_context_create(hip_device, &ctx);                                      // (first: without a device its message says so)
+    if (!rc) hip_ok(hipSetDevice(hip_device), "hipSetDevice");
+    if (!what && !rc) rc = mi355rt_context_set_scene(ctx, sc, cam, st);
+    if (!what && !rc) rc = mi355rt_context_set_timing(ctx, 1);
+    if (!what && !rc) host_rc = mi355rt_noise_create(st->width, st->height, &noise);
+    if (!what && !rc && !host_rc) {
+        hip_ok(hipMalloc(&d_accum, n * 16), "hipMalloc");
+        for (int i = 0; i < 2 && !what; ++i) {
+            hip_ok(hipMalloc(&d_packed[i], n * 4), "hipMalloc"); hip_ok(hipMalloc(&d_linear[i], n * 12), "hipMalloc"); hip_ok(hipMalloc(&d_snap[i], n * 16), "hipMalloc");
+            hip_ok(hipHostMalloc(&h_snap[i], n * 16, hipHostMallocDefault), "hipHostMalloc");
+            hip_ok(hipEventCreateWithFlags(&E[i], hipEventDisableTiming), "hipEventCreate"); hip_ok(hipEventCreateWithFlags(&F[i], hipEventDisableTiming), "hipEventCreate");
+        }
+        hip_ok(hipStreamCreateWithFlags(&s_render, hipStreamNonBlocking), "hipStreamCreate"); hip_ok(hipStreamCreateWithFlags(&s_copy, hipStreamNonBlocking), "hipStreamCreate");
+    }
+    // chunk k covers samples [begin(k), end(k)); the last one may be shorter
+    auto end_of = [&](uint32_t k) { const uint64_t e = (uint64_t)k * a.chunk; return e < a.max_spp ? (uint32_t)e : a.max_spp; };
+    auto enqueue = [&](uint32_t k) {
+        const int i = (int)(k & 1u);
+        rc = mi355rt_context_render_progressive(ctx, opt, end_of(k - 1), end_of(k), d_accum, d_packed[i], d_linear[i], s_render, nullptr);
+        if (rc) return;
+        hip_ok(hipMemcpyAsync(d_snap[i], d_accum, n * 16, hipMemcpyDeviceToDevice, s_render), "snapshot");
+        hip_ok(hipEventRecord(E[i], s_render), "hipEventRecord");
+        hip_ok(hipStreamWaitEvent(s_copy, E[i], 0), "hipStreamWaitEvent");
+        hip_ok(hipMemcpyAsync(h_snap[i], d_snap[i], n * 16, hipMemcpyDeviceToHost, s_copy), "snapshot copy");
+        hip_ok(hipEventRecord(F[i], s_copy), "hipEventRecord");
+        res->rendered = end_of(k);
+    };
+    uint32_t k = 1;
+    if (!what && !rc && !host_rc) enqueue(1);
+    for (; !what && !rc && !host_rc; ++k) {
+        const bool last = end_of(k) >= a.max_spp;
+        if (!last) enqueue(k + 1);                                                      // the device stays busy while the host estimates
+        if (what || rc) break;
+        if (!hip_ok(hipEventSynchronize(F[k & 1u]), "hipEventSynchronize")) break;
+        const auto u0 = std::chrono::steady_clock::now();
+        host_rc = mi355rt_noise_update(noise, static_cast<const float*>(h_snap[k & 1u]), end_of(k));
+        const auto u1 = std::chrono::steady_clock::now();
+        res->update_ms += std::chrono::duration<double, std::milli>(u1 - u0).count();
+        if (host_rc) break;
+        if (k >= 2) {
+            host_rc = mi355rt_noise_evaluate(noise, &a.params, error_map.empty() ? nullptr : error_map.data(), &res->summary);
+            res->evaluate_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - u1).count();
+            if (host_rc) break;
+            std::printf("  %u / %u samples per pixel: above=%llu max=%.6g mean=%.6g\n", end_of(k), a.max_spp, (unsigned long long)res->summary.above,
+                        res->summary.max_error, res->summary.mean_error);
+        } else {
+            res->summary.chunks = 1; res->summary.samples = end_of(k); res->summary.pixels = n;    // (a run that ends after one chunk has no estimate)
+            std::printf("  %u / %u samples per pixel\n", end_of(k), a.max_spp);
+        }
+        if (res->summary.converged || last) break;
+    }
+    // chunk k is the result.  Wait for everything enqueued (the speculative chunk included) before anything is read or freed.
+    if (s_render) hip_ok(hipStreamSynchronize(s_render), "hipStreamSynchronize");
+    if (s_copy) hip_ok(hipStreamSynchronize(s_copy), "hipStreamSynchronize");
+    if (!what && !rc && !host_rc) rc = mi355rt_context_check(ctx);
+    if (!what && !rc && !host_rc) {
+        uint32_t launches = 0;
+        rc = mi355rt_context_read_timing(ctx, &res->render_ms, &res->resolve_ms, &launches);
+        hip_ok(hipMemcpy(out_packed, d_packed[k & 1u], n * 4, hipMemcpyDeviceToHost), "copy back");
+        if (out_linear_or_null) hip_ok(hipMemcpy(out_linear_or_null, d_linear[k & 1u], n * 12, hipMemcpyDeviceToHost), "copy back");
+    }
+    res->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (rc) std::fprintf(stderr, "render failed (%d): %s\n", rc, mi355rt_last_error());
+    else if (host_rc) std::fprintf(stderr, "noise estimate failed (%d): %s\n", host_rc, mi355rt_host_last_error());
+    else if (what) std::fprintf(stderr, "render failed: %s: %s\n", what, hipGetErrorString(hipGetLastError()));
+    for (int i = 0; i < 2; ++i) {
+        (void)hipFree(d_packed[i]); (void)hipFree(d_linear[i]); (void)hipFree(d_snap[i]); if (h_snap[i]) (void)hipHostFree(h_snap[i]);
+        if (E[i]) (void)hipEventDestroy(E[i]);
+        if (F[i]) (void)hipEventDestroy(F[i]);
+    }
+    (void)hipFree(d_accum);
+    if (s_render) (void)hipStreamDestroy(s_render);
+    if (s_copy) (void)hipStreamDestroy(s_copy);
+    if (ctx) mi355rt_context_destroy(ctx);
+    int failed = (rc || host_rc || what) ? 1 : 0;
+    if (!failed && !a.noise_out.empty()) {                                              // the error map as grey RGB; NaN where the pixel is non-finite
+        std::vector<float> rgb(n * 3);
+        for (size_t p = 0; p < n; ++p) rgb[3 * p] = rgb[3 * p + 1] = rgb[3 * p + 2] = error_map[p];
+        if (res->summary.chunks < 2) { std::fprintf(stderr, "--noise-out: the run ended after one chunk, there is no estimate to write\n"); failed = 1; }
+        else if (mi355rt_write_pfm(a.noise_out.c_str(), rgb.data(), st->width, st->height) != MI355RT_OK) { std::fprintf(stderr, "%s\n", mi355rt_host_last_error()); failed = 1; }
+    }
+    mi355rt_noise_free(noise);
+    return failed;
+}
+
+static const char USAGE[] = "usage: %s <scene.json> [-o out.png] [--width W] [--height H] [--spp N] [--max-depth D] [--rng ctr|ref] [--seed S] [--skip-unknown] [--chunk N] [--pfm out.pfm] [--exr out.exr] [--gpus N | --devices a,b,..] [--fix-aabb] [--fix-wo3] [--denoise-out denoised.png]"
+                            " [--noise-target T [--noise-floor F] [--noise-allow FRACTION] [--min-chunks K] [--max-spp N] [--noise-out map.pfm]]\n";
+
 int main(int argc, char** argv) {
-    if (argc < 2) { std::fprintf(stderr, "usage: %s <scene.json> [-o out.png] [--width W] [--height H] [--spp N] [--max-depth D] [--rng ctr|ref] [--seed S] [--skip-unknown] [--chunk N] [--pfm out.pfm] [--exr out.exr] [--gpus N | --devices a,b,..] [--fix-aabb] [--fix-wo3] [--denoise-out denoised.png]\n", argv[0]); return 2; }
+    if (argc < 2) { std::fprintf(stderr, USAGE, argv[0]); return 2; }
     std::string scene_path = argv[1], out_path = "render_pt.png", pfm_path, exr_path, denoise_path;
     mi355rt_load_overrides ov{}; mi355rt_options opt{}; uint32_t chunk = 0, gpus = 1; std::vector<int> device_list;
     opt.abi_version = MI355RT_ABI_VERSION; opt.rng_mode = MI355RT_RNG_CTR; opt.strip_rows = 1; opt.n_parts = 1;
+    ConvergeArgs cv{}; cv.params = {0.02, 0.01, 4u, 0u, 0ull};                          // the library's defaults
+    bool noise = false, noise_option = false, multi_option = false; double noise_allow = 0.0;
+    auto usage = [&](const char* why) { std::fprintf(stderr, USAGE, argv[0]); std::fprintf(stderr, "%s\n", why); return 2; };
     for (int i = 2; i < argc; ++i) {
         auto next = [&]() -> const char* { if (i + 1 >= argc) { std::fprintf(stderr, "missing value for %s\n", argv[i]); std::exit(2); } return argv[++i]; };
         if (!std::strcmp(argv[i], "-o")) out_path = next();
@@ -65,8 +189,15 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--pfm")) pfm_path = next();
         else if (!std::strcmp(argv[i], "--exr")) exr_path = next();
         else if (!std::strcmp(argv[i], "--denoise-out")) denoise_path = next();
-        else if (!std::strcmp(argv[i], "--gpus")) gpus = (uint32_t)std::atoi(next());
+        else if (!std::strcmp(argv[i], "--noise-target")) { cv.params.threshold = std::atof(next()); noise = true; }
+        else if (!std::strcmp(argv[i], "--noise-floor")) { cv.params.floor = std::atof(next()); noise_option = true; }
+        else if (!std::strcmp(argv[i], "--noise-allow")) { noise_allow = std::atof(next()); noise_option = true; }
+        else if (!std::strcmp(argv[i], "--min-chunks")) { cv.params.min_chunks = (uint32_t)std::atoi(next()); noise_option = true; }
+        else if (!std::strcmp(argv[i], "--max-spp")) { cv.max_spp = (uint32_t)std::atoi(next()); noise_option = true; }
+        else if (!std::strcmp(argv[i], "--noise-out")) { cv.noise_out = next(); noise_option = true; }
+        else if (!std::strcmp(argv[i], "--gpus")) { gpus = (uint32_t)std::atoi(next()); multi_option = true; }
         else if (!std::strcmp(argv[i], "--devices")) {
+            multi_option = true;
             for (const char* q = next(); *q;) { char* e = nullptr; const long d = std::strtol(q, &e, 10); if (e == q) { std::fprintf(stderr, "--devices wants a comma-separated list of device numbers\n"); return 2; }
                                                 device_list.push_back((int)d); q = (*e == ',') ? e + 1 : e; if (*e && *e != ',') { std::fprintf(stderr, "--devices wants a comma-separated list of device numbers\n"); return 2; } }
             gpus = (uint32_t)device_list.size();
@@ -76,6 +207,18 @@ int main(int argc, char** argv) {
         else { std::fprintf(stderr, "unknown option %s\n", argv[i]); return 2; }
     }
     if (gpus == 0) { std::fprintf(stderr, "--gpus / --devices: at least one device\n"); return 2; }
+    if (noise_option && !noise) return usage(cv.noise_out.empty() ? "--noise-floor, --noise-allow, --min-chunks and --max-spp go with --noise-target" : "--noise-out needs --noise-target");
+    if (noise) {
+        if (multi_option) return usage("--noise-target renders on one GPU: it cannot be combined with --gpus or --devices");
+        if (opt.rng_mode == MI355RT_RNG_REF) return usage("--noise-target needs the counter-mode generator: it cannot be combined with --rng ref");
+        if (!(cv.params.threshold >= 0.0) || !(cv.params.threshold < 1e300)) return usage("--noise-target wants a number >= 0");
+        if (!(noise_allow >= 0.0 && noise_allow <= 1.0)) return usage("--noise-allow wants a fraction of the pixels, 0 .. 1");
+        // 0 = never stop on the estimate (render --max-spp samples): the library wants a threshold > 0, and `err > the smallest double` is `err > 0`
+        if (cv.params.threshold == 0.0) cv.params.threshold = std::numeric_limits<double>::denorm_min();
+        if (!(cv.params.floor >= 0.0) || !(cv.params.floor < 1e300)) return usage("--noise-floor wants a number >= 0");
+        if (cv.params.min_chunks < 2) return usage("--min-chunks wants at least 2: one chunk has no spread");
+        cv.chunk = chunk ? chunk : 16;
+    }
     const bool multi = gpus > 1 || !device_list.empty();
     if (multi && chunk) { std::fprintf(stderr, "--chunk (progressive preview) renders on one GPU: it cannot be combined with --gpus %u\n", gpus); return 2; }
     std::printf("Attempting to load scene from: %s\n", scene_path.c_str());
@@ -102,7 +245,21 @@ int main(int argc, char** argv) {
     if (devices.empty()) for (uint32_t d = 0; d < gpus; ++d) devices.push_back((int)d);
     if (multi) { opt.strip_rows = 4; opt.n_parts = 0; }
     const auto t_render = std::chrono::steady_clock::now();
-    int rc = multi ? mi355rt_render_multi(sc, mi355rt_loaded_scene_camera(ls), st, &opt, devices.data(), gpus, buffer.data(), lin, &stats)
+    if (noise) {
+        if (cv.max_spp == 0) cv.max_spp = st->samples_per_pixel;
+        const uint64_t n_px = (uint64_t)st->width * st->height;
+        cv.params.allowed_above = (uint64_t)std::floor(noise_allow * (double)n_px);
+        ConvergeResult cr;
+        if (render_converging(devices[0], sc, mi355rt_loaded_scene_camera(ls), st, &opt, cv, buffer.data(), lin, &cr)) { mi355rt_scene_free(ls); return 1; }
+        std::printf("noise: samples=%u chunks=%u rendered=%u above=%llu nonfinite=%llu max=%.9g mean=%.9g converged=%u wall_ms=%.3f kernel_ms=%.3f\n",
+                    cr.summary.samples, cr.summary.chunks, cr.rendered, (unsigned long long)cr.summary.above, (unsigned long long)cr.summary.nonfinite,
+                    cr.summary.max_error, cr.summary.mean_error, cr.summary.converged, cr.wall_ms, cr.render_ms + cr.resolve_ms);
+        std::printf("noise host: update_ms=%.3f evaluate_ms=%.3f per chunk (%u updates, %u evaluations)\n", cr.update_ms / cr.summary.chunks,
+                    cr.summary.chunks > 1 ? cr.evaluate_ms / (cr.summary.chunks - 1) : 0.0, cr.summary.chunks, cr.summary.chunks - 1);
+        if (!cv.noise_out.empty()) std::printf("Noise map saved as '%s'\n", cv.noise_out.c_str());
+        stats.samples = n_px * cr.rendered; stats.render_kernel_ms = cr.render_ms; stats.resolve_kernel_ms = cr.resolve_ms; stats.total_ms = cr.render_ms + cr.resolve_ms;
+    }
+    int rc = noise ? MI355RT_OK : multi ? mi355rt_render_multi(sc, mi355rt_loaded_scene_camera(ls), st, &opt, devices.data(), gpus, buffer.data(), lin, &stats)
            : chunk ? mi355rt_render_progressive(sc, mi355rt_loaded_scene_camera(ls), st, &opt, chunk, on_chunk, &pv, buffer.data(), lin, &stats)
                    : mi355rt_render(sc, mi355rt_loaded_scene_camera(ls), st, &opt, buffer.data(), lin, &stats);   // <- src/main.rs:57
     if (rc != MI355RT_OK) { std::fprintf(stderr, "render failed (%d): %s\n", rc, mi355rt_last_error()); mi355rt_scene_free(ls); return 1; }

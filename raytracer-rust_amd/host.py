@@ -38,6 +38,16 @@ def lib():
             L.mi355rt_write_exr.argtypes = [C.c_char_p, C.c_void_p, C.c_uint32, C.c_uint32]
             L.mi355rt_write_png.restype = C.c_int
             L.mi355rt_write_png.argtypes = [C.c_char_p, C.c_void_p, C.c_uint32, C.c_uint32]
+        L.mi355rt_noise_create.restype = C.c_int
+        L.mi355rt_noise_create.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
+        L.mi355rt_noise_free.restype = None
+        L.mi355rt_noise_free.argtypes = [C.c_void_p]
+        L.mi355rt_noise_reset.restype = C.c_int
+        L.mi355rt_noise_reset.argtypes = [C.c_void_p]
+        L.mi355rt_noise_update.restype = C.c_int
+        L.mi355rt_noise_update.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+        L.mi355rt_noise_evaluate.restype = C.c_int
+        L.mi355rt_noise_evaluate.argtypes = [C.c_void_p, C.POINTER(abi.NoiseParams), C.c_void_p, C.POINTER(abi.NoiseSummary)]
         _lib = L
     return _lib
 
@@ -111,6 +121,46 @@ class LoadedScene:
         if self._h:
             lib().mi355rt_scene_free(self._h)
             self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class NoiseState:
+    """mi355rt_noise_*: the per-pixel noise estimate of a progressive render (include/mi355rt.h has the definition).  Feed it a host copy of
+    the running sums after every chunk; evaluate() returns (error map float32 [rows, width] or None, abi.NoiseSummary)."""
+
+    def __init__(self, width, rows):
+        h = C.c_void_p()
+        _check(lib().mi355rt_noise_create(width, rows, C.byref(h)), "mi355rt_noise_create")
+        self._h, self.width, self.rows = h, width, rows
+
+    def reset(self):
+        _check(lib().mi355rt_noise_reset(self._h), "mi355rt_noise_reset")
+
+    def update(self, accum, samples_total):
+        """accum: float32, rows * width * 4 values (the layout of d_accum); samples_total: the chunk's sample_end."""
+        a = np.ascontiguousarray(accum, dtype=np.float32)
+        if a.size != self.rows * self.width * 4:
+            raise ValueError(f"accum holds {a.size} floats, not rows * width * 4 = {self.rows * self.width * 4}")
+        _check(lib().mi355rt_noise_update(self._h, a.ctypes.data, samples_total), "mi355rt_noise_update")
+
+    def evaluate(self, params=None, want_map=True):
+        err = np.empty((self.rows, self.width), np.float32) if want_map else None
+        summary = abi.NoiseSummary()
+        _check(lib().mi355rt_noise_evaluate(self._h, C.byref(params) if params is not None else None,
+                                            err.ctypes.data if want_map else None, C.byref(summary)), "mi355rt_noise_evaluate")
+        return err, summary
+
+    def close(self):
+        if self._h:
+            lib().mi355rt_noise_free(self._h)
+            self._h = None
+
+    free = close
 
     def __del__(self):
         try:

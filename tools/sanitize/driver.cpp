@@ -1,5 +1,5 @@
 // Sanitizer driver for the CPU-side producers (libmi355rt_host: scene loader, JSON, OBJ / WO3 / HDR readers, BVH build,
-// PNG / PFM writers), for the CPU oracle's entry points and for scene preparation, the HIP-free half of the device library
+// PNG / PFM writers, the noise estimate), for the CPU oracle's entry points and for scene preparation, the HIP-free half of the device library
 // (csrc/device/rt_prepare.cpp: validation, the BVH re-lay, the primitive records; the plan of a render call).  Built with -fsanitize=address,undefined by
 // tools/sanitize_host.py; every case must return (OK or an error code) without a sanitizer report.
 //   usage: driver <repo root> <scratch dir>
@@ -331,6 +331,30 @@ int main(int argc, char** argv) {
         expect(mi355rt_write_png((tmp + "/no/dir/a.png").c_str(), px.data(), 7, 5) != MI355RT_OK, "write_png to a missing directory");
         expect(mi355rt_write_png((tmp + "/z.png").c_str(), px.data(), 0, 5) != MI355RT_OK, "write_png of an empty image");
         expect(mi355rt_write_png(nullptr, px.data(), 7, 5) != MI355RT_OK, "write_png null path");
+    }
+
+    // ---- the noise estimate: exact buffer sizes (a read or write past rows * width * 4 floats / rows * width floats is a report), non-finite and huge sums ----
+    {
+        const uint32_t W = 13, R = 7; const size_t n = (size_t)W * R;
+        mi355rt_noise_state* s = nullptr; mi355rt_noise_summary sum{};
+        expect(mi355rt_noise_create(0, R, &s) == MI355RT_ERR_INVALID && !s, "noise_create width 0");
+        expect(mi355rt_noise_create(1u << 16, 1u << 15, &s) == MI355RT_ERR_INVALID && !s, "noise_create 2^31 pixels");
+        expect(mi355rt_noise_create(W, R, &s) == MI355RT_OK && s, "noise_create");
+        std::vector<float> acc(n * 4, 0.0f), err(n, -1.0f);
+        expect(mi355rt_noise_evaluate(s, nullptr, err.data(), &sum) == MI355RT_ERR_INVALID, "noise_evaluate before any chunk");
+        for (uint32_t k = 1; k <= 5; ++k) {
+            for (size_t p = 0; p < n; ++p) for (int c = 0; c < 3; ++c) acc[4 * p + c] += (float)((p * 7 + c * 3 + k * k) % 11) * 0.125f * (float)k;
+            acc[4 * 3 + 1] = k > 2 ? INFINITY : acc[4 * 3 + 1]; acc[4 * 5] = k > 3 ? NAN : acc[4 * 5]; acc[4 * 6 + 2] = 3.0e38f; acc[4 * 8] = -(float)k;
+            expect(mi355rt_noise_update(s, acc.data(), k * 3 + (k > 2 ? 5 : 0)) == MI355RT_OK, "noise_update");
+            expect(mi355rt_noise_update(s, acc.data(), k * 3) == MI355RT_ERR_INVALID, "noise_update with samples_total not increasing");
+            if (k >= 2) expect(mi355rt_noise_evaluate(s, nullptr, k & 1 ? err.data() : nullptr, &sum) == MI355RT_OK && sum.chunks == k && sum.pixels == n, "noise_evaluate");
+        }
+        expect(sum.nonfinite == 2 && std::isnan(err[3]) && std::isnan(err[5]) && err[0] >= 0.0f, "noise_evaluate: two non-finite pixels");
+        mi355rt_noise_params pr = {0.5, 0.0, 2u, 0u, n};
+        expect(mi355rt_noise_evaluate(s, &pr, err.data(), &sum) == MI355RT_OK && sum.converged == 1u, "noise_evaluate with floor 0");
+        pr._pad = 7u; expect(mi355rt_noise_evaluate(s, &pr, err.data(), &sum) == MI355RT_ERR_INVALID, "noise_evaluate with a pad");
+        expect(mi355rt_noise_reset(s) == MI355RT_OK && mi355rt_noise_evaluate(s, nullptr, nullptr, &sum) == MI355RT_ERR_INVALID, "noise_reset");
+        mi355rt_noise_free(s); mi355rt_noise_free(nullptr);
     }
     std::printf(g_fail ? "sanitize driver: %d unexpected result(s)\n" : "sanitize driver: all cases behaved (%d unexpected)\n", g_fail);
     return g_fail ? 1 : 0;
