@@ -94,6 +94,26 @@ int main(int argc, char** argv) {
         bool all = true; for (uint32_t m : table) all = all && m == 0xFFFu;
         expect(all, "a degenerate camera keeps everything");
     }
+    {   // cameras off the axes (the classes of tests/scene_shapes.py: position, forward, right, true_up, half_width, half_height), and each once more with
+        // a NaN in its basis: a table of full size that holds bits of the list only, and no report
+        const float off_axis[6][14] = {
+            {4.f, 3.f, 5.5f, -0.507803f, -0.439181f, -0.741118f, 0.855755f, -0.158207f, -0.492599f, -0.09909f, 0.884359f, -0.456169f, 0.694089f, 0.520567f},   // rolled_oblique
+            {-2.f, 1.5f, -8.f, 0.23862f, -0.178965f, 0.95448f, -0.970142f, 0.f, 0.242536f, 0.0434054f, 0.983855f, 0.173622f, 0.621744f, 0.466308f},             // from_minus_z
+            {0.3f, 9.f, 0.2f, -0.0333066f, -0.999198f, -0.0222044f, 0.999445f, -0.0333148f, 0.f, 0.000739736f, 0.0221921f, -0.999753f, 0.621744f, 0.466308f},   // looking_down
+            {0.5f, 0.5f, 3.f, -0.162221f, -0.162221f, -0.973328f, 0.986394f, 0.f, -0.164399f, -0.026669f, 0.986754f, -0.160014f, 4.97607f, 3.73205f},           // wide
+            {4000.f, 3000.f, 5000.f, -0.565685f, -0.424264f, -0.707107f, 0.780869f, 0.f, -0.624695f, -0.265036f, 0.905539f, -0.331295f, 0.000698132f, 0.000523599f},   // far_tele
+            {2.f, 1.5f, 8.f, -0.5f, -0.3f, -2.f, 1.5f, 0.2f, 0.3f, 0.3f, 0.8f, 0.1f, 0.7f, 0.4f}};                                                              // sheared
+        static_assert(sizeof(DevCamera) == sizeof off_axis[0], "a camera is fourteen floats");
+        for (const auto& values : off_axis) for (int poisoned = 0; poisoned < 2; ++poisoned) {
+            DevCamera c; std::memcpy(&c, values, sizeof c);
+            if (poisoned) c.right[1] = nan;
+            build_camera_masks(ps, c, W, H, table);
+            bool small = table.size() == N, all = true;
+            for (uint32_t m : table) { small = small && m <= 0xFFFu; all = all && m == 0xFFFu; }
+            expect(small, "an off-axis camera: one word per pixel, bits of the list only");
+            if (poisoned) expect(all, "a NaN in the basis keeps everything");
+        }
+    }
     build_camera_masks(ps, cam, 1, 1, table); expect(table.size() == 1, "1 x 1");
     build_camera_masks(ps, cam, 3, 1 << 14, table); expect(table.size() == (size_t)3 << 14, "3 x 16384");
     ps.prims.assign(33, quad(0, 0, 0, 1));
