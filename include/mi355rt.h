@@ -43,7 +43,9 @@ extern "C" {
                                     and the denoiser: mi355rt_denoise_scratch_bytes, mi355rt_context_denoise, mi355rt_denoise;
                                     and the occlusion queries: mi355rt_context_occluded, mi355rt_occluded, mi355rt_context_ambient_occlusion;
                                     and, in the host library, the noise estimate: mi355rt_noise_create, mi355rt_noise_free, mi355rt_noise_reset,
-                                    mi355rt_noise_update, mi355rt_noise_evaluate. */
+                                    mi355rt_noise_update, mi355rt_noise_evaluate;
+                                    and, in the device library, the same estimate on device memory: mi355rt_noise_device_create, mi355rt_noise_device_destroy,
+                                    mi355rt_noise_device_reset, mi355rt_noise_device_update, mi355rt_noise_device_evaluate. */
 
 /* ---- error codes ------------------------------------------------------------------------- */
 #define MI355RT_OK               0
@@ -649,6 +651,49 @@ int  mi355rt_noise_evaluate(const mi355rt_noise_state* state, const mi355rt_nois
                             float* out_error_or_null, mi355rt_noise_summary* out_summary);
 
 const char* mi355rt_host_last_error(void);
+
+/* ---- the same estimate on the device, beside the running sums (libmi355rt.so; added within ABI version 5: probe for the symbols) -------------
+ * mi355rt_noise_update / mi355rt_noise_evaluate above want a HOST copy of d_accum after every chunk; these read d_accum where it is -- the buffer of
+ * mi355rt_context_render_progressive, or what mi355rt_multi_context_render_progressive leaves in d_accum_or_null -- and leave the verdict as the
+ * 56 bytes of a mi355rt_noise_summary in stream order.  The object stands alone: a device number and its buffers (48 bytes per pixel and 32 per
+ * tile), no mi355rt_context.  reset, update and evaluate only ENQUEUE on hip_stream and return; K and N are kept on the host side of the object
+ * at enqueue time, so every refusal is decided before any HIP call.  The calls make the object's device current, as mi355rt_context_* do.  One
+ * object's calls belong on one stream at a time (evaluate's per-tile records are the object's); the caller synchronises the streams that carry
+ * its work before destroy.  An object is not thread-safe; different objects are independent.
+ *
+ * DEFINITION.  update and evaluate are the DEFINITION above, operation for operation in IEEE double with one rounding each (divisions and the
+ * square root correctly rounded), with the same NaN rules: the error map, chunks, samples, pixels, above, nonfinite, max_error, converged and
+ * _pad are bit for bit what mi355rt_noise_evaluate gives for the same sums.  accum[4p+3] is not read.  mean_error alone is summed in another
+ * ORDER -- a fixed tree instead of the host's sum in pixel order -- so it differs from the host's by rounding only: all terms are >= 0, so both
+ * sums are within (pixels + 64) * 2^-53, relative, of each other.  The order depends on the pixel count alone: not on a grid size, not on the
+ * device, not on timing (no floating-point atomics).
+ *   e[p] = err of pixel p, and +0.0 where the pixel is not counted (nonfinite) and for p >= pixels; pixels = width * rows.
+ *   TILES.   The list is cut into tiles of 256 consecutive pixels: tile j holds the pixels 256 j .. 256 j + 255, n_tiles = ceil(pixels / 256).
+ *   TREE(v), v[0 .. 255]:   each run of 64 (a wave: v[64 w .. 64 w + 63], w = 0 .. 3) is halved six times -- x[i] = x[i] + x[i + h] for
+ *       i < h, with h = 32, 16, 8, 4, 2, 1 -- which leaves the wave's sum s_w in x[0];   TREE = (s_0 + s_1) + (s_2 + s_3).
+ *   S_j = TREE(e[256 j .. 256 j + 255]) for every tile j.
+ *   ACROSS TILES.   a[t] = ((S_t + S_(t + 256)) + S_(t + 512)) + ... for t = 0 .. 255: tile sums 256 apart, added in ascending order,
+ *       0.0 where there is no tile t.   sum = TREE(a).
+ *   mean_error = sum / (double)(pixels - nonfinite), 0 when no pixel is counted.
+ *   max_error and the counts go the same way; a maximum and an integer sum do not depend on the order.
+ * evaluate writes every one of the 56 bytes of *d_out_summary, _pad as 0, and rows * width floats to d_out_error when that is given: nothing else.
+ * d_accum: rows * width * 4 floats, 16-byte aligned.  d_out_summary: any 8-byte aligned memory the device can write -- hipMalloc'ed, or
+ * pinned host memory (then the caller reads it after an event recorded behind evaluate).  d_out_error_or_null: rows * width floats, 4-byte aligned.
+ * REFUSALS are MI355RT_ERR_INVALID with a text (mi355rt_last_error) that names the argument, the host's texts with the prefix noise_device_:
+ * a null state, out, d_accum or d_out_summary; a d_accum that is not 16-byte aligned, a d_out_summary not 8-byte, a d_out_error not 4-byte
+ * aligned; width or rows 0, width * rows >= 2^31; samples_total not above the samples already seen; evaluate before the second update;
+ * threshold not > 0 or not finite, floor negative or not finite, min_chunks < 2, _pad not 0.  No device is MI355RT_ERR_NO_DEVICE, a failed
+ * allocation MI355RT_ERR_OOM.  A refused call changes nothing; a call that returns an error has not advanced K or N.  After MI355RT_ERR_HIP the
+ * contents are unspecified until reset. */
+typedef struct mi355rt_noise_device mi355rt_noise_device;
+int  mi355rt_noise_device_create(int hip_device, uint32_t width, uint32_t rows, mi355rt_noise_device** out);
+void mi355rt_noise_device_destroy(mi355rt_noise_device* s);
+/* Back to K = N = 0 and zero sums, in stream order. */
+int  mi355rt_noise_device_reset(mi355rt_noise_device* s, void* hip_stream);
+/* d_accum after the chunk that ended at sample_end = samples_total; it is read in stream order, so enqueue it behind the render on the same stream. */
+int  mi355rt_noise_device_update(mi355rt_noise_device* s, const void* d_accum, uint32_t samples_total, void* hip_stream);
+int  mi355rt_noise_device_evaluate(mi355rt_noise_device* s, const mi355rt_noise_params* params_or_null,
+                                   void* d_out_error_or_null, void* d_out_summary, void* hip_stream);
 
 #ifdef __cplusplus
 }

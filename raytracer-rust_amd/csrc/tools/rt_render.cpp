@@ -5,7 +5,7 @@
 //   rt_render <scene.json> [-o out.png] [--width W] [--height H] [--spp N] [--max-depth D]
 //             [--rng ctr|ref] [--seed S] [--skip-unknown] [--chunk N] [--pfm out.pfm] [--exr out.exr] [--gpus N | --devices a,b,..]
 //             [--denoise-out denoised.png]
-//             [--noise-target T [--noise-floor F] [--noise-allow FRACTION] [--min-chunks K] [--max-spp N] [--noise-out map.pfm]]
+//             [--noise-target T [--noise-floor F] [--noise-allow FRACTION] [--min-chunks K] [--max-spp N] [--noise-out map.pfm] [--noise-device]]
 // --fix-aabb / --fix-wo3 switch on the two opt-in fixes (MI355RT_FLAG_FIXED_AABB, wo3_four_index_stride): not the reference's image.
 // --gpus N deals row strips over HIP devices 0..N-1 from this one process (mi355rt_render_multi); --devices a,b,... names them
 // (a device may repeat: the strip plan of N GPUs on a one-GPU machine).
@@ -19,6 +19,8 @@
 // one-shot render of that many; --noise-out PATH.pfm writes the per-pixel error map (grey, NaN where the pixel is not finite).  No preview is
 // written between chunks.  One line `noise: samples=S chunks=K rendered=R above=A nonfinite=F max=.. mean=.. converged=0|1 wall_ms=.. kernel_ms=..`
 // reports the stop (R >= S: what the device traced, the speculative chunk included; kernel_ms covers all of R).
+// --noise-device (only with --noise-target) takes the estimate on the device, beside the running sums (mi355rt_noise_device_*): the same images,
+// the same map and the same verdict, mean= equal up to the rounding of another order of summation; no copy of the sums leaves the device.
 #include <chrono>
 #include <cmath>
 #include <limits>
@@ -65,15 +67,20 @@ static int denoise_image(int hip_device, const mi355rt_scene* sc, const mi355rt_
 // Chunk k's image is the pair [k & 1]; the speculative chunk k + 1 writes the other pair.  d_snap[k & 1], h_snap[k & 1] and the pair [k & 1]
 // are next written by chunk k + 2, and chunk k + 2 is enqueued only after the host has waited for F_k and consumed snapshot k -- so two of
 // each are enough and nothing is overwritten while it is still read.
-struct ConvergeArgs { uint32_t chunk, max_spp; mi355rt_noise_params params; std::string noise_out; };
-struct ConvergeResult { mi355rt_noise_summary summary; uint32_t rendered; double wall_ms, render_ms, resolve_ms, update_ms, evaluate_ms; };
+// With --noise-device there are no snapshots and no copy stream.  Per chunk k, all on the render stream:
+//   mi355rt_context_render_progressive into the output pair [k & 1];  event P_k;  mi355rt_noise_device_update(d_accum);  for k >= 2
+//   mi355rt_noise_device_evaluate into the pinned summary [k & 1] (and the device error map [k & 1] with --noise-out);  event F_k
+//   host:           enqueue chunk k + 1 first, as above, then wait F_k and read the 56 bytes.
+// P_k .. F_k (timing events) bracket the estimate's kernels of chunk k: their sum over the chunks k >= 2 is the `noise device:` line.
+struct ConvergeArgs { uint32_t chunk, max_spp; mi355rt_noise_params params; std::string noise_out; bool on_device; };
+struct ConvergeResult { mi355rt_noise_summary summary; uint32_t rendered; double wall_ms, render_ms, resolve_ms, update_ms, evaluate_ms, pass_ms; uint32_t passes; };
 
 static int render_converging(int hip_device, const mi355rt_scene* sc, const mi355rt_camera* cam, const mi355rt_settings* st, const mi355rt_options* opt,
                              const ConvergeArgs& a, uint32_t* out_packed, float* out_linear_or_null, ConvergeResult* res) {
     const size_t n = (size_t)st->width * st->height;
-    mi355rt_context* ctx = nullptr; mi355rt_noise_state* noise = nullptr;
-    void *d_accum = nullptr, *d_packed[2] = {}, *d_linear[2] = {}, *d_snap[2] = {}, *h_snap[2] = {};
-    hipStream_t s_render = nullptr, s_copy = nullptr; hipEvent_t E[2] = {}, F[2] = {};
+    mi355rt_context* ctx = nullptr; mi355rt_noise_state* noise = nullptr; mi355rt_noise_device* noise_dev = nullptr;
+    void *d_accum = nullptr, *d_packed[2] = {}, *d_linear[2] = {}, *d_snap[2] = {}, *h_snap[2] = {}, *d_err[2] = {}, *h_sum[2] = {};
+    hipStream_t s_render = nullptr, s_copy = nullptr; hipEvent_t E[2] = {}, F[2] = {}, P[2] = {};
     std::vector<float> error_map(a.noise_out.empty() ? 0 : n);
     const char* what = nullptr; int rc = 0, host_rc = 0;
     *res = ConvergeResult{};
@@ -83,15 +90,24 @@ static int render_converging(int hip_device, const mi355rt_scene* sc, const mi35
     if (!rc) hip_ok(hipSetDevice(hip_device), "hipSetDevice");
     if (!what && !rc) rc = mi355rt_context_set_scene(ctx, sc, cam, st);
     if (!what && !rc) rc = mi355rt_context_set_timing(ctx, 1);
-    if (!what && !rc) host_rc = mi355rt_noise_create(st->width, st->height, &noise);
+    if (!what && !rc && !a.on_device) host_rc = mi355rt_noise_create(st->width, st->height, &noise);
+    if (!what && !rc && a.on_device) rc = mi355rt_noise_device_create(hip_device, st->width, st->height, &noise_dev);
     if (!what && !rc && !host_rc) {
         hip_ok(hipMalloc(&d_accum, n * 16), "hipMalloc");
         for (int i = 0; i < 2 && !what; ++i) {
-            hip_ok(hipMalloc(&d_packed[i], n * 4), "hipMalloc"); hip_ok(hipMalloc(&d_linear[i], n * 12), "hipMalloc"); hip_ok(hipMalloc(&d_snap[i], n * 16), "hipMalloc");
+            hip_ok(hipMalloc(&d_packed[i], n * 4), "hipMalloc"); hip_ok(hipMalloc(&d_linear[i], n * 12), "hipMalloc");
+            if (a.on_device) {
+                hip_ok(hipHostMalloc(&h_sum[i], sizeof(mi355rt_noise_summary), hipHostMallocDefault), "hipHostMalloc");
+                if (!a.noise_out.empty()) hip_ok(hipMalloc(&d_err[i], n * 4), "hipMalloc");
+                hip_ok(hipEventCreate(&P[i]), "hipEventCreate"); hip_ok(hipEventCreate(&F[i]), "hipEventCreate");
+                continue;
+            }
+            hip_ok(hipMalloc(&d_snap[i], n * 16), "hipMalloc");
             hip_ok(hipHostMalloc(&h_snap[i], n * 16, hipHostMallocDefault), "hipHostMalloc");
             hip_ok(hipEventCreateWithFlags(&E[i], hipEventDisableTiming), "hipEventCreate"); hip_ok(hipEventCreateWithFlags(&F[i], hipEventDisableTiming), "hipEventCreate");
         }
-        hip_ok(hipStreamCreateWithFlags(&s_render, hipStreamNonBlocking), "hipStreamCreate"); hip_ok(hipStreamCreateWithFlags(&s_copy, hipStreamNonBlocking), "hipStreamCreate");
+        hip_ok(hipStreamCreateWithFlags(&s_render, hipStreamNonBlocking), "hipStreamCreate");
+        if (!a.on_device) hip_ok(hipStreamCreateWithFlags(&s_copy, hipStreamNonBlocking), "hipStreamCreate");
     }
     // chunk k covers samples [begin(k), end(k)); the last one may be shorter
     auto end_of = [&](uint32_t k) { const uint64_t e = (uint64_t)k * a.chunk; return e < a.max_spp ? (uint32_t)e : a.max_spp; };
@@ -99,6 +115,15 @@ static int render_converging(int hip_device, const mi355rt_scene* sc, const mi35
         const int i = (int)(k & 1u);
         rc = mi355rt_context_render_progressive(ctx, opt, end_of(k - 1), end_of(k), d_accum, d_packed[i], d_linear[i], s_render, nullptr);
         if (rc) return;
+        if (a.on_device) {
+            hip_ok(hipEventRecord(P[i], s_render), "hipEventRecord");
+            rc = mi355rt_noise_device_update(noise_dev, d_accum, end_of(k), s_render);
+            if (!rc && k >= 2) rc = mi355rt_noise_device_evaluate(noise_dev, &a.params, d_err[i], h_sum[i], s_render);
+            if (rc) return;
+            hip_ok(hipEventRecord(F[i], s_render), "hipEventRecord");
+            res->rendered = end_of(k);
+            return;
+        }
         hip_ok(hipMemcpyAsync(d_snap[i], d_accum, n * 16, hipMemcpyDeviceToDevice, s_render), "snapshot");
         hip_ok(hipEventRecord(E[i], s_render), "hipEventRecord");
         hip_ok(hipStreamWaitEvent(s_copy, E[i], 0), "hipStreamWaitEvent");
@@ -113,6 +138,21 @@ static int render_converging(int hip_device, const mi355rt_scene* sc, const mi35
         if (!last) enqueue(k + 1);                                                      // the device stays busy while the host estimates
         if (what || rc) break;
         if (!hip_ok(hipEventSynchronize(F[k & 1u]), "hipEventSynchronize")) break;
+        if (a.on_device) {
+            if (k >= 2) {
+                float ms = 0.0f;
+                if (!hip_ok(hipEventElapsedTime(&ms, P[k & 1u], F[k & 1u]), "hipEventElapsedTime")) break;
+                res->pass_ms += ms; res->passes += 1;
+                std::memcpy(&res->summary, h_sum[k & 1u], sizeof res->summary);
+                std::printf("  %u / %u samples per pixel: above=%llu max=%.6g mean=%.6g\n", end_of(k), a.max_spp, (unsigned long long)res->summary.above,
+                            res->summary.max_error, res->summary.mean_error);
+            } else {
+                res->summary.chunks = 1; res->summary.samples = end_of(k); res->summary.pixels = n;
+                std::printf("  %u / %u samples per pixel\n", end_of(k), a.max_spp);
+            }
+            if (res->summary.converged || last) break;
+            continue;
+        }
         const auto u0 = std::chrono::steady_clock::now();
         host_rc = mi355rt_noise_update(noise, static_cast<const float*>(h_snap[k & 1u]), end_of(k));
         const auto u1 = std::chrono::steady_clock::now();
@@ -139,6 +179,7 @@ static int render_converging(int hip_device, const mi355rt_scene* sc, const mi35
         rc = mi355rt_context_read_timing(ctx, &res->render_ms, &res->resolve_ms, &launches);
         hip_ok(hipMemcpy(out_packed, d_packed[k & 1u], n * 4, hipMemcpyDeviceToHost), "copy back");
         if (out_linear_or_null) hip_ok(hipMemcpy(out_linear_or_null, d_linear[k & 1u], n * 12, hipMemcpyDeviceToHost), "copy back");
+        if (d_err[k & 1u] && res->summary.chunks >= 2) hip_ok(hipMemcpy(error_map.data(), d_err[k & 1u], n * 4, hipMemcpyDeviceToHost), "copy back");
     }
     res->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     if (rc) std::fprintf(stderr, "render failed (%d): %s\n", rc, mi355rt_last_error());
@@ -146,12 +187,15 @@ static int render_converging(int hip_device, const mi355rt_scene* sc, const mi35
     else if (what) std::fprintf(stderr, "render failed: %s: %s\n", what, hipGetErrorString(hipGetLastError()));
     for (int i = 0; i < 2; ++i) {
         (void)hipFree(d_packed[i]); (void)hipFree(d_linear[i]); (void)hipFree(d_snap[i]); if (h_snap[i]) (void)hipHostFree(h_snap[i]);
+        (void)hipFree(d_err[i]); if (h_sum[i]) (void)hipHostFree(h_sum[i]);
         if (E[i]) (void)hipEventDestroy(E[i]);
         if (F[i]) (void)hipEventDestroy(F[i]);
+        if (P[i]) (void)hipEventDestroy(P[i]);
     }
     (void)hipFree(d_accum);
     if (s_render) (void)hipStreamDestroy(s_render);
     if (s_copy) (void)hipStreamDestroy(s_copy);
+    mi355rt_noise_device_destroy(noise_dev);                                            // (both streams have been waited for)
     if (ctx) mi355rt_context_destroy(ctx);
     int failed = (rc || host_rc || what) ? 1 : 0;
     if (!failed && !a.noise_out.empty()) {                                              // the error map as grey RGB; NaN where the pixel is non-finite
@@ -165,7 +209,7 @@ static int render_converging(int hip_device, const mi355rt_scene* sc, const mi35
 }
 
 static const char USAGE[] = "usage: %s <scene.json> [-o out.png] [--width W] [--height H] [--spp N] [--max-depth D] [--rng ctr|ref] [--seed S] [--skip-unknown] [--chunk N] [--pfm out.pfm] [--exr out.exr] [--gpus N | --devices a,b,..] [--fix-aabb] [--fix-wo3] [--denoise-out denoised.png]"
-                            " [--noise-target T [--noise-floor F] [--noise-allow FRACTION] [--min-chunks K] [--max-spp N] [--noise-out map.pfm]]\n";
+                            " [--noise-target T [--noise-floor F] [--noise-allow FRACTION] [--min-chunks K] [--max-spp N] [--noise-out map.pfm] [--noise-device]]\n";
 
 int main(int argc, char** argv) {
     if (argc < 2) { std::fprintf(stderr, USAGE, argv[0]); return 2; }
@@ -173,7 +217,7 @@ int main(int argc, char** argv) {
     mi355rt_load_overrides ov{}; mi355rt_options opt{}; uint32_t chunk = 0, gpus = 1; std::vector<int> device_list;
     opt.abi_version = MI355RT_ABI_VERSION; opt.rng_mode = MI355RT_RNG_CTR; opt.strip_rows = 1; opt.n_parts = 1;
     ConvergeArgs cv{}; cv.params = {0.02, 0.01, 4u, 0u, 0ull};                          // the library's defaults
-    bool noise = false, noise_option = false, multi_option = false; double noise_allow = 0.0;
+    bool noise = false, noise_option = false, noise_device = false, multi_option = false; double noise_allow = 0.0;
     auto usage = [&](const char* why) { std::fprintf(stderr, USAGE, argv[0]); std::fprintf(stderr, "%s\n", why); return 2; };
     for (int i = 2; i < argc; ++i) {
         auto next = [&]() -> const char* { if (i + 1 >= argc) { std::fprintf(stderr, "missing value for %s\n", argv[i]); std::exit(2); } return argv[++i]; };
@@ -195,6 +239,7 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--min-chunks")) { cv.params.min_chunks = (uint32_t)std::atoi(next()); noise_option = true; }
         else if (!std::strcmp(argv[i], "--max-spp")) { cv.max_spp = (uint32_t)std::atoi(next()); noise_option = true; }
         else if (!std::strcmp(argv[i], "--noise-out")) { cv.noise_out = next(); noise_option = true; }
+        else if (!std::strcmp(argv[i], "--noise-device")) noise_device = true;
         else if (!std::strcmp(argv[i], "--gpus")) { gpus = (uint32_t)std::atoi(next()); multi_option = true; }
         else if (!std::strcmp(argv[i], "--devices")) {
             multi_option = true;
@@ -208,6 +253,8 @@ int main(int argc, char** argv) {
     }
     if (gpus == 0) { std::fprintf(stderr, "--gpus / --devices: at least one device\n"); return 2; }
     if (noise_option && !noise) return usage(cv.noise_out.empty() ? "--noise-floor, --noise-allow, --min-chunks and --max-spp go with --noise-target" : "--noise-out needs --noise-target");
+    if (noise_device && !noise) return usage("--noise-device needs --noise-target");
+    cv.on_device = noise_device;
     if (noise) {
         if (multi_option) return usage("--noise-target renders on one GPU: it cannot be combined with --gpus or --devices");
         if (opt.rng_mode == MI355RT_RNG_REF) return usage("--noise-target needs the counter-mode generator: it cannot be combined with --rng ref");
@@ -254,8 +301,9 @@ int main(int argc, char** argv) {
         std::printf("noise: samples=%u chunks=%u rendered=%u above=%llu nonfinite=%llu max=%.9g mean=%.9g converged=%u wall_ms=%.3f kernel_ms=%.3f\n",
                     cr.summary.samples, cr.summary.chunks, cr.rendered, (unsigned long long)cr.summary.above, (unsigned long long)cr.summary.nonfinite,
                     cr.summary.max_error, cr.summary.mean_error, cr.summary.converged, cr.wall_ms, cr.render_ms + cr.resolve_ms);
-        std::printf("noise host: update_ms=%.3f evaluate_ms=%.3f per chunk (%u updates, %u evaluations)\n", cr.update_ms / cr.summary.chunks,
-                    cr.summary.chunks > 1 ? cr.evaluate_ms / (cr.summary.chunks - 1) : 0.0, cr.summary.chunks, cr.summary.chunks - 1);
+        if (cv.on_device) std::printf("noise device: pass_ms=%.3f per chunk (update + evaluate of %u chunks, device time)\n", cr.passes ? cr.pass_ms / cr.passes : 0.0, cr.passes);
+        else std::printf("noise host: update_ms=%.3f evaluate_ms=%.3f per chunk (%u updates, %u evaluations)\n", cr.update_ms / cr.summary.chunks,
+                         cr.summary.chunks > 1 ? cr.evaluate_ms / (cr.summary.chunks - 1) : 0.0, cr.summary.chunks, cr.summary.chunks - 1);
         if (!cv.noise_out.empty()) std::printf("Noise map saved as '%s'\n", cv.noise_out.c_str());
         stats.samples = n_px * cr.rendered; stats.render_kernel_ms = cr.render_ms; stats.resolve_kernel_ms = cr.resolve_ms; stats.total_ms = cr.render_ms + cr.resolve_ms;
     }

@@ -19,7 +19,9 @@ EXPORTS = ["mi355rt_render", "mi355rt_render_multi", "mi355rt_render_progressive
            "mi355rt_multi_context_check", "mi355rt_multi_context_render_progressive", "mi355rt_render_progressive_multi",
            "mi355rt_context_trace_rays", "mi355rt_context_first_hits", "mi355rt_trace_rays",
            "mi355rt_denoise_scratch_bytes", "mi355rt_context_denoise", "mi355rt_denoise",
-           "mi355rt_context_occluded", "mi355rt_occluded", "mi355rt_context_ambient_occlusion"]
+           "mi355rt_context_occluded", "mi355rt_occluded", "mi355rt_context_ambient_occlusion",
+           "mi355rt_noise_device_create", "mi355rt_noise_device_destroy", "mi355rt_noise_device_reset", "mi355rt_noise_device_update",
+           "mi355rt_noise_device_evaluate"]
 
 _lib = None
 _extra = {}
@@ -191,6 +193,16 @@ def _bind(so):
         L.mi355rt_occluded.argtypes = [C.POINTER(abi.Scene), C.c_void_p, C.c_uint32, C.c_void_p]
         L.mi355rt_context_ambient_occlusion.restype = C.c_int
         L.mi355rt_context_ambient_occlusion.argtypes = [C.c_void_p, C.POINTER(abi.Options), C.POINTER(abi.AoParams), C.c_void_p, C.c_void_p, C.c_void_p]
+        L.mi355rt_noise_device_create.restype = C.c_int
+        L.mi355rt_noise_device_create.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
+        L.mi355rt_noise_device_destroy.restype = None
+        L.mi355rt_noise_device_destroy.argtypes = [C.c_void_p]
+        L.mi355rt_noise_device_reset.restype = C.c_int
+        L.mi355rt_noise_device_reset.argtypes = [C.c_void_p, C.c_void_p]
+        L.mi355rt_noise_device_update.restype = C.c_int
+        L.mi355rt_noise_device_update.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+        L.mi355rt_noise_device_evaluate.restype = C.c_int
+        L.mi355rt_noise_device_evaluate.argtypes = [C.c_void_p, C.POINTER(abi.NoiseParams), C.c_void_p, C.c_void_p, C.c_void_p]
         L.mi355rt_debug_multi_part_ms.restype = C.c_int
         L.mi355rt_debug_multi_part_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_uint32, C.POINTER(C.c_uint32)]
         L.mi355rt_debug_set_knob.restype = C.c_int
@@ -599,6 +611,91 @@ class Context:
     def __del__(self):
         try:
             self.close()
+        except Exception:
+            pass
+
+
+_hip_rt = None
+
+
+def _hip():
+    """The HIP runtime the device library is linked against, for NoiseDevice's own buffers (torch is not needed here)."""
+    global _hip_rt
+    if _hip_rt is None:
+        H = C.CDLL("libamdhip64.so")
+        H.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
+        H.hipHostMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t, C.c_uint]
+        H.hipFree.argtypes = [C.c_void_p]
+        H.hipHostFree.argtypes = [C.c_void_p]
+        H.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+        H.hipStreamSynchronize.argtypes = [C.c_void_p]
+        H.hipSetDevice.argtypes = [C.c_int]
+        _hip_rt = H
+    return _hip_rt
+
+
+class NoiseDevice:
+    """mi355rt_noise_device_*: the noise estimate of a progressive render on the device, beside the running sums (include/mi355rt.h has the
+    definition).  update() reads d_accum where it is; evaluate() returns (error map float32 [rows, width] or None, abi.NoiseSummary).  The
+    object owns a device buffer for the map and a pinned word for the summary; update, reset and evaluate_into only enqueue."""
+
+    def __init__(self, width, rows, device=0, library=None):
+        self._L = library or lib()
+        self._h = C.c_void_p()
+        self._d_error = C.c_void_p()
+        self._h_summary = C.c_void_p()
+        _check(self._L.mi355rt_noise_device_create(int(device), int(width), int(rows), C.byref(self._h)), "mi355rt_noise_device_create", self._L)
+        self.width, self.rows, self.device = int(width), int(rows), int(device)
+
+    def reset(self, stream=None):
+        _check(self._L.mi355rt_noise_device_reset(self._h, C.c_void_p(stream) if stream else None), "mi355rt_noise_device_reset", self._L)
+
+    def update(self, d_accum_ptr, samples_total, stream=None):
+        """d_accum_ptr: integer device address of rows * width * 4 floats (d_accum of render_progressive); samples_total: the chunk's sample_end."""
+        _check(self._L.mi355rt_noise_device_update(self._h, C.c_void_p(d_accum_ptr) if d_accum_ptr else None, int(samples_total),
+                                                   C.c_void_p(stream) if stream else None), "mi355rt_noise_device_update", self._L)
+
+    def evaluate_into(self, d_out_error, d_out_summary, params=None, stream=None):
+        """Enqueue only: the map to the device address d_out_error (or None) and the 56-byte summary to d_out_summary, in stream order."""
+        _check(self._L.mi355rt_noise_device_evaluate(self._h, C.byref(params) if params is not None else None,
+                                                     C.c_void_p(d_out_error) if d_out_error else None, C.c_void_p(d_out_summary) if d_out_summary else None,
+                                                     C.c_void_p(stream) if stream else None), "mi355rt_noise_device_evaluate", self._L)
+
+    def _hip_check(self, rc, what):
+        if rc != 0:
+            raise RuntimeError(f"NoiseDevice: {what} failed (hipError_t {rc})")
+
+    def evaluate(self, params=None, want_map=True, stream=None):
+        H = _hip()
+        self._hip_check(H.hipSetDevice(self.device), "hipSetDevice")
+        if not self._h_summary:
+            self._hip_check(H.hipHostMalloc(C.byref(self._h_summary), C.sizeof(abi.NoiseSummary), 0), "hipHostMalloc")
+        if want_map and not self._d_error:
+            self._hip_check(H.hipMalloc(C.byref(self._d_error), self.rows * self.width * 4), "hipMalloc")
+        self.evaluate_into(self._d_error.value if want_map else None, self._h_summary.value, params, stream)
+        self._hip_check(H.hipStreamSynchronize(C.c_void_p(stream) if stream else None), "hipStreamSynchronize")
+        summary = abi.NoiseSummary.from_buffer_copy(C.string_at(self._h_summary.value, C.sizeof(abi.NoiseSummary)))
+        err = None
+        if want_map:
+            err = np.empty((self.rows, self.width), np.float32)
+            self._hip_check(H.hipMemcpy(err.ctypes.data, self._d_error, err.nbytes, 2), "hipMemcpy")      # 2: device to host
+        return err, summary
+
+    def free(self):
+        """The caller has synchronised the streams that carry this object's work."""
+        if self._h:
+            self._L.mi355rt_noise_device_destroy(self._h)
+            self._h = C.c_void_p()
+        if self._d_error:
+            _hip().hipFree(self._d_error); self._d_error = C.c_void_p()
+        if self._h_summary:
+            _hip().hipHostFree(self._h_summary); self._h_summary = C.c_void_p()
+
+    close = free
+
+    def __del__(self):
+        try:
+            self.free()
         except Exception:
             pass
 
