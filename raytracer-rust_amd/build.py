@@ -43,8 +43,9 @@ DEVICE_HEADERS = sorted(os.path.join(CSRC, "device", f) for f in os.listdir(os.p
 DEVICE_DEPS = DEVICE_SRCS + DEVICE_HEADERS + [os.path.join(ROOT, "include", "mi355rt.h")]
 # Compiled into the tests' reference build (-DMI355RT_REFS) only, so neither the product library nor kernel_hash() contains it:
 # mi355rt_debug_stages, the transcendental stages over enumerated inputs (tests/test_gpu_transcendental_stages.py);
-# mi355rt_debug_resolve / mi355rt_debug_gather, the shipped resolve and gather launchers on caller-supplied buffers (tests/test_gpu_resolve_stage.py).
-REFS_SRCS = [os.path.join(CSRC, "refs", "rt_stages.hip"), os.path.join(CSRC, "refs", "rt_resolve_probe.hip")]
+# mi355rt_debug_resolve / mi355rt_debug_gather, the shipped resolve and gather launchers on caller-supplied buffers (tests/test_gpu_resolve_stage.py);
+# mi355rt_debug_rng_block, one generator block through each form of the draw address at a chosen ray and try (tests/test_gpu_rng_stepped.py).
+REFS_SRCS = [os.path.join(CSRC, "refs", "rt_stages.hip"), os.path.join(CSRC, "refs", "rt_resolve_probe.hip"), os.path.join(CSRC, "refs", "rt_rng_probe.hip")]
 
 
 def _host_srcs():

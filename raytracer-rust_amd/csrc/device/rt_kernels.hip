@@ -184,7 +184,8 @@ typedef WorkCursorT<BATCH_MIN, BATCH_MAX> WorkCursor;                    // lock
 typedef WorkCursorT<RUN_WAVEFRONT_MIN, RUN_WAVEFRONT> WorkCursorWf;          // wavefront kernel: fixed, aligned runs (rt_device.h)
 
 // Decode a band-local sample index into (x, y, s) and key the path's RNG (renderer.rs:91-97).
-DI void start_path(const RenderParams& P, uint32_t sidx, RngCtr& rng, uint32_t& px, uint32_t& py) {
+template <class RNG>
+DI void start_path(const RenderParams& P, uint32_t sidx, RNG& rng, uint32_t& px, uint32_t& py) {
     const uint32_t pix_local = fastdiv(sidx, P.spp_mul, P.spp_shift);
     const uint32_t s = sidx - pix_local * P.spp;
     const uint32_t pix = P.band_pixel0 + pix_local;
@@ -195,13 +196,16 @@ DI void start_path(const RenderParams& P, uint32_t sidx, RngCtr& rng, uint32_t& 
     rng.start((uint32_t)ykey, (uint32_t)(ykey >> 32), px, s + P.sample0);
 }
 
-// Per-lane path state shared by both kernels.
-struct PathState {
+// Per-lane path state shared by both kernels.  STEP: the form of the generator's draw address (rt_rng.h), chosen per kernel.
+template <bool STEP>
+struct PathStateT {
+    typedef RngCtrT<STEP> Rng;
     f3 ro, rd, thr;
     uint32_t sidx, ray_index;
     uint32_t px, py;               // only meaningful while `fresh`
-    RngCtr rng;
+    Rng rng;
 };
+typedef PathStateT<false> PathState;
 
 // Camera rays IN STOCK (lockstep kernels, round 5).  A path that ends hands its lane to a fresh sample in the same iteration, so every iteration
 // started a few paths -- 11 of 64 lanes on cornell, in 93 % of the iterations (profiles/r05/stamps_final_kernels.txt) -- and paid the whole
@@ -213,11 +217,11 @@ struct PathState {
 // two ds_read_b128.  Same arithmetic per path, same bits.  Entries change hands between lanes: wave_lds_handoff() around refill (deal_stocked).
 struct RayStock {
     float4* dir; uint4* key;                                   // [64] each, this wave's
-    template <bool FASTN>
+    template <bool FASTN, class RNG>
     DI void refill(const RenderParams& P, uint32_t first, uint32_t count, uint32_t lane) const {
         if (lane < count) {
             const uint32_t sidx = first + lane;
-            RngCtr rng; uint32_t px, py;
+            RNG rng; uint32_t px, py;
             start_path(P, sidx, rng, px, py);
             rng.template load_block0<true>();                                                   // ray 0, block 0: the jitter (words 0 / 1)
             const float un = (float)px + rng.jitter_u(), vn = (float)py + rng.jitter_v();
@@ -225,15 +229,16 @@ struct RayStock {
             const float v = FASTN ? div_by_rn(vn, P.height_f, P.inv_height_rn) : vn / (float)P.height;    // renderer.rs:97
             const f3 raw = camera_raw(P.cam, u, v);                                              // renderer.rs:99
             dir[sidx & 63u] = make_float4(raw.x, raw.y, raw.z, 0.f);
-            if constexpr (RngCtr::NW == 4) key[sidx & 63u] = make_uint4(rng.w[0], rng.w[1], rng.w[2], rng.w[3]);
+            if constexpr (RNG::NW == 4) key[sidx & 63u] = make_uint4(rng.w[0], rng.w[1], rng.w[2], rng.w[3]);   // (the draw address as the generator keeps it: opaque here)
         }
     }
-    DI void take(const RenderParams& P, uint32_t sidx, f3& raw, PathState& ps) const {
+    template <class PS>
+    DI void take(const RenderParams& P, uint32_t sidx, f3& raw, PS& ps) const {
         const float4 d = dir[sidx & 63u];
         raw = mk(d.x, d.y, d.z);
         // (handing the key over only after the iteration's shared generator call -- a fresh path does not use that call's block -- so that the wave need not
         //  wait for this read in front of it was measured: four more live registers, cornell +0.5 %, the general kernels +0.5 ... 2 %)
-        if constexpr (RngCtr::NW == 4) { const uint4 k = key[sidx & 63u]; ps.rng.w[0] = k.x; ps.rng.w[1] = k.y; ps.rng.w[2] = k.z; ps.rng.w[3] = k.w; }
+        if constexpr (PS::Rng::NW == 4) { const uint4 k = key[sidx & 63u]; ps.rng.w[0] = k.x; ps.rng.w[1] = k.y; ps.rng.w[2] = k.z; ps.rng.w[3] = k.w; }
         else start_path(P, sidx, ps.rng, ps.px, ps.py);                                          // (the Philox builds address by (key, x, s): nothing to keep)
     }
 };
@@ -246,22 +251,27 @@ struct RayStock {
 // entries.  A lane that is dealt an entry scatters its first hit in the same iteration, as a continuing lane at ray 0.  Every value of an entry is the
 // one the loop computed for that sample before (same functions, same order), so radiance and ray counts are the same bits.
 // An entry is 64 bytes (four ds_read_b128): {h.p, sample index}, {h.n, mat_ff}, q0, the generator key at ray 0 (pcg4d: its four words; Philox: the
-// key, x and s -- the ray word is 0).  The parking area holds ro and rd of the 64 lanes (24 bytes each) during a refill pass.
+// key, x and s -- the ray word is 0; the words are the generator's own, stored and reloaded untouched).  The parking area holds ro and rd of the 64 lanes (24 bytes each) during a refill pass.
 struct HitStock {
     float4* e;                                                 // [64][4] this wave's ring of entries
     float4* park_a; float2* park_b;                            // [64] each: {ro, rd.x}, {rd.y, rd.z}; lane i writes and reads back element i only: no hand-off
     // Before the walk: the camera ray of sample `sidx` into (ro, rd) -- what RayStock::refill and the loop's shared tail computed -- and its key
     // into the entry at `slot` (the entry's other words are written after the walk).  The slot is one that another lane was dealt earlier, and append()
     // reads the key from another lane: the caller puts a wave_lds_handoff() in front of the camera() calls and one behind them.
-    DI void camera(const RenderParams& P, uint32_t sidx, uint32_t slot, f3& ro, f3& rd) const {
-        RngCtr rng; uint32_t px, py;
+    // `here` is 0: a wave-uniform index that the caller makes from the pass's first sample index (below 2^31, rt_device.h), so that the camera record is read (scalar loads) where the pass
+    // uses it.  Read as P.cam it is a launch constant, and with the stepped generator the compiler kept its first 32 bytes in eight scalar registers
+    // across the whole loop and spilled the loop's own masks for them (13 spilled SGPRs, 23 v_readlane; like this 3 and 9, the plain form 6 and 10).
+    template <class RNG>
+    DI void camera(const RenderParams& P, uint32_t sidx, uint32_t slot, f3& ro, f3& rd, uint32_t here) const {
+        RNG rng; uint32_t px, py;
         start_path(P, sidx, rng, px, py);
         rng.template load_block0<true>();                                                   // ray 0, block 0: the jitter (words 0 / 1)
         const float un = (float)px + rng.jitter_u(), vn = (float)py + rng.jitter_v();
         const float u = div_by_rn(un, P.width_f, P.inv_width_rn);                           // renderer.rs:96
         const float v = div_by_rn(vn, P.height_f, P.inv_height_rn);                         // renderer.rs:97
-        ro = mk(P.cam.position[0], P.cam.position[1], P.cam.position[2]);
-        rd = ray_direction<true>(camera_raw(P.cam, u, v));                                   // renderer.rs:99
+        const DevCamera& cam = (&P.cam)[here];
+        ro = mk(cam.position[0], cam.position[1], cam.position[2]);
+        rd = ray_direction<true>(camera_raw(cam, u, v));                                     // renderer.rs:99
         e[4u * slot + 3u] = make_float4(__uint_as_float(rng.w[0]), __uint_as_float(rng.w[1]), __uint_as_float(rng.w[2]), __uint_as_float(rng.w[3]));
     }
     // After the walk (lanes with cam == true walked sample first + lane from `tail` + lane): finish the paths that end at their camera ray, exactly as
@@ -306,13 +316,18 @@ struct NoStock {};
 // its segment of the ballot, i.e. exactly the try the sequential loop would have stopped at.  Typically two
 // rounds instead of E[max over 64 lanes of a geometric(0.52)] ~ 7.7 iterations of a mostly idle wave.
 // Must be called in wave-uniform control flow.
+// Stepped draw address (RngCtrT<true>): try j enters the generator's rounds as W_3 + j * A.  The owner keeps the word of its NEXT try, `wnext`, instead
+// of the try's number and advances it by A << lg when a round fails; wnext travels in the place of W_3, so a round moves four words per worker, not
+// five.  A worker adds sub * A for its place sub < 64 in the group: a 24-bit multiply (A < 2^24, sub < 2^6: the product is exact in 32 bits), the only
+// place where one may be used -- everywhere else j is unbounded and takes the full multiply (RngCtrT::block) or a running word.
 DI int lane_shfl(int v, uint32_t src_lane) { return __builtin_amdgcn_ds_bpermute((int)(src_lane << 2), v); }
 DI float lane_shfl(float v, uint32_t src_lane) { return __int_as_float(__builtin_amdgcn_ds_bpermute((int)(src_lane << 2), __float_as_int(v))); }
-template <bool WIDE = false, int TRY1 = 0>
-DI f3 unit_ball_cooperative(bool diffuse, const RngCtr& rng, uint32_t lane, const uint32_t* b1 = nullptr) {
+template <bool WIDE = false, int TRY1 = 0, class RNG>
+DI f3 unit_ball_cooperative(bool diffuse, const RNG& rng, uint32_t lane, const uint32_t* b1 = nullptr) {
+    constexpr bool STEPPED = RNG::STEPPED;
     f3 p = mk(u32_to_range11(rng.b0[1]), u32_to_range11(rng.b0[2]), u32_to_range11(rng.b0[3]));   // try 0
     bool need = diffuse && !(len2(p) < 1.0f);
-    uint32_t jbase = 1;
+    uint32_t jbase = 1;                                                            // plain form: the number of the owner's next try
     if constexpr (TRY1 >= 1) {                                                     // try 1 was drawn in the lane itself, next to the event's block
         const f3 p1 = mk(u32_to_range11(b1[1]), u32_to_range11(b1[2]), u32_to_range11(b1[3]));
         if (need && len2(p1) < 1.0f) { p = p1; need = false; }
@@ -320,12 +335,14 @@ DI f3 unit_ball_cooperative(bool diffuse, const RngCtr& rng, uint32_t lane, cons
     }
     if constexpr (TRY1 >= 2) {
         if (__ballot(need) != 0ull) {
-            uint32_t b2[4]; RngCtr::block<WIDE>(rng.w, 2u, b2);
+            uint32_t b2[4]; RNG::template block<WIDE>(rng.w, 2u, b2);
             const f3 p2 = mk(u32_to_range11(b2[1]), u32_to_range11(b2[2]), u32_to_range11(b2[3]));
             if (need && len2(p2) < 1.0f) { p = p2; need = false; }
         }
         jbase = 3;
     }
+    uint32_t wnext = 0u;                                                           // stepped form: the last word of the owner's next try, W_3 + jbase * A
+    if constexpr (STEPPED) wnext = rng.w[3] + jbase * LCG_A;                       // (jbase is a constant here)
     for (;;) {
         const uint64_t m = __ballot(need);
         if (m == 0ull) break;
@@ -337,12 +354,18 @@ DI f3 unit_ball_cooperative(bool diffuse, const RngCtr& rng, uint32_t lane, cons
         const uint32_t orank = lane >> lg;
         const bool worker = orank < n;
         const uint32_t olane = (uint32_t)lane_shfl(tab, worker ? orank : 0u);
-        uint32_t ow[RngCtr::NW];                                                   // the owner's draw address (rt_rng.h)
-#pragma unroll
-        for (int i = 0; i < RngCtr::NW; ++i) ow[i] = (uint32_t)lane_shfl((int)rng.w[i], olane);
-        const uint32_t oj = (uint32_t)lane_shfl((int)jbase, olane);
         uint32_t w[4];
-        RngCtr::block<WIDE>(ow, oj + (lane & ((1u << lg) - 1u)), w);
+        if constexpr (STEPPED) {
+            const uint32_t o0 = (uint32_t)lane_shfl((int)rng.w[0], olane), o1 = (uint32_t)lane_shfl((int)rng.w[1], olane), o2 = (uint32_t)lane_shfl((int)rng.w[2], olane);
+            const uint32_t o3 = (uint32_t)lane_shfl((int)wnext, olane);
+            RNG::block_at(o0, o1, o2, o3 + __umul24(lane & ((1u << lg) - 1u), LCG_A), w);   // sub < 64, A < 2^24
+        } else {
+        uint32_t ow[RNG::NW];                                                      // the owner's draw address (rt_rng.h)
+#pragma unroll
+        for (int i = 0; i < RNG::NW; ++i) ow[i] = (uint32_t)lane_shfl((int)rng.w[i], olane);
+        const uint32_t oj = (uint32_t)lane_shfl((int)jbase, olane);
+        RNG::template block<WIDE>(ow, oj + (lane & ((1u << lg) - 1u)), w);
+        }
         const f3 q = mk(u32_to_range11(w[1]), u32_to_range11(w[2]), u32_to_range11(w[3]));
         const uint64_t acc = __ballot(worker && (len2(q) < 1.0f));
         const uint32_t seg_lo = r << lg;                                           // my segment of the ballot (owners only)
@@ -351,7 +374,12 @@ DI f3 unit_ball_cooperative(bool diffuse, const RngCtr& rng, uint32_t lane, cons
         const bool found = seg != 0ull;
         const uint32_t src = found ? seg_lo + (uint32_t)__builtin_ctzll(seg) : lane;
         const float qx = lane_shfl(q.x, src), qy = lane_shfl(q.y, src), qz = lane_shfl(q.z, src);
+        if constexpr (STEPPED) {
+            if (need && found) { p = mk(qx, qy, qz); need = false; }
+            wnext += LCG_A << lg;                                                  // (every lane: the word matters only to an owner that still needs a try)
+        } else {
         if (need) { if (found) { p = mk(qx, qy, qz); need = false; } else jbase += (1u << lg); }
+        }
     }
     return p;
 }
@@ -374,9 +402,10 @@ DI f3 unit_ball_cooperative(bool diffuse, const RngCtr& rng, uint32_t lane, cons
 // REKEY (wavefront kernel: a path's generator state is not carried in its slot): the state is derived from the sample index HERE, once, for continuing
 // and freshly dealt lanes together, right in front of the event's block -- instead of by the caller when the slot is loaded (live through the hit record,
 // the material read and the radiance store) and a second time where fresh samples are dealt.
-template <uint32_t MATS, bool DEFAULTS = true, bool WIDE = !DEFAULTS, bool DROP_PRIO = false, bool Q0_IN_HIT = false, bool FASTN = false, int TRY1 = 0, bool REKEY = false, class WC, class STOCK = NoStock>
+template <uint32_t MATS, bool DEFAULTS = true, bool WIDE = !DEFAULTS, bool DROP_PRIO = false, bool Q0_IN_HIT = false, bool FASTN = false, int TRY1 = 0, bool REKEY = false, class WC, class PS, class STOCK = NoStock>
 DI bool shade_and_regenerate(const RenderParams& P, WC& wc, uint32_t lane, bool& live, bool can_take, bool hit, const Hit& h,
-                             PathState& ps, uint32_t& n_paths, uint32_t& n_rays, Prof& prof, const STOCK& stock = STOCK()) {
+                             PS& ps, uint32_t& n_paths, uint32_t& n_rays, Prof& prof, const STOCK& stock = STOCK()) {
+    typedef typename PS::Rng Rng;                                                            // RngCtrT<STEP>: the kernel's form of the draw address
     constexpr bool STOCKED = std::is_same<STOCK, RayStock>::value;                           // camera rays come out of the wave's stock (lockstep kernels)
     constexpr bool PREHIT = std::is_same<STOCK, HitStock>::value;                            // ... or their first hits (k_render_ctr_simple_qc)
     static_assert(!(STOCKED || PREHIT) || (!DEFAULTS && !REKEY), "the stock serves the lockstep form");
@@ -411,12 +440,12 @@ DI bool shade_and_regenerate(const RenderParams& P, WC& wc, uint32_t lane, bool&
             hs.n = mk(e1.x, e1.y, e1.z); hs.mat_ff = __float_as_uint(e1.w);
             q0 = e2;
             ps.rng.w[0] = __float_as_uint(e3.x); ps.rng.w[1] = __float_as_uint(e3.y); ps.rng.w[2] = __float_as_uint(e3.z); ps.rng.w[3] = __float_as_uint(e3.w);
-            if constexpr (RngCtr::NW == 5) ps.rng.w[4] = 0u;                                  // (Philox: the ray word)
+            if constexpr (Rng::NW == 5) ps.rng.w[4] = 0u;                                  // (Philox: the ray word)
             ps.thr = mk(1.f, 1.f, 1.f); ps.ray_index = 0; live = true;
         }
     } else
     if constexpr (STOCKED) {
-        if (wc.deal_stocked(P, can_take && !live, lane, ps.sidx, [&](uint32_t first, uint32_t count) { stock.template refill<FASTN>(P, first, count, lane); },
+        if (wc.deal_stocked(P, can_take && !live, lane, ps.sidx, [&](uint32_t first, uint32_t count) { stock.template refill<FASTN, Rng>(P, first, count, lane); },
                             [&](uint32_t sidx) { stock.take(P, sidx, stocked_raw, ps); })) { fresh = true; live = true; ++n_paths; }
     } else
     if (wc.deal(P, can_take && !live, lane, ps.sidx)) { if constexpr (!REKEY) start_path(P, ps.sidx, ps.rng, ps.px, ps.py); fresh = true; live = true; ++n_paths; }
@@ -466,7 +495,7 @@ DI bool shade_and_regenerate(const RenderParams& P, WC& wc, uint32_t lane, bool&
         else if (!fresh) ps.rng.next_event();
         ps.rng.template load_block0<WIDE>();
         uint32_t blk1[4] = {0u, 0u, 0u, 0u};
-        if constexpr (TRY1 >= 1) RngCtr::block<WIDE>(ps.rng.w, 1u, blk1);
+        if constexpr (TRY1 >= 1) Rng::template block<WIDE>(ps.rng.w, 1u, blk1);
         if (live) {
             if (fresh) {
                 // (FASTN: div_bounded with the host's RN(1/width) -- the dividend is 0 or in [2^-24, 2^24), the divisor an image dimension in [1, 2^24);
@@ -529,7 +558,8 @@ DI bool shade_and_regenerate(const RenderParams& P, WC& wc, uint32_t lane, bool&
 // point (also in the general kernel: pays at 80 VGPRs); the short reciprocal / square root / division of rt_math.h; in the Lambert-only kernel ONE try of the
 // unit-ball draw in the lane itself before the cooperative rounds (0 tries: +1.9 %, 2 tries: +-0 with pcg4d, +23 % with Philox: profiles/r05/ab_counter_generator.txt).
 // PREHIT: the wave stocks its camera rays' first hits (HitStock), walked in refill passes through the loop's one walk site.
-template <bool HAS_MESH, uint32_t MATS, uint32_t KINDS = PRIMS_ALL, bool PREHIT = false, bool BOUNDED = false>
+// STEP: the generator's draw address in LCG-stepped form (rt_rng.h); per kernel, see the entry points below.
+template <bool HAS_MESH, uint32_t MATS, uint32_t KINDS = PRIMS_ALL, bool PREHIT = false, bool BOUNDED = false, bool STEP = false>
 DI void render_ctr_lockstep(const RenderParams& P) {
     constexpr bool SIMPLE = (MATS & ~MATS_LAMBERT) == 0u;
     // The mesh-free kernels are compiled for lists that hold something and for paths that may take a step: the host sends an empty list or max_depth == 0 to
@@ -551,7 +581,7 @@ DI void render_ctr_lockstep(const RenderParams& P) {
     __shared__ __attribute__((aligned(16))) uint4 s_stock_key[BLOCK_THREADS];
     stock.dir = s_stock_dir + (threadIdx.x & ~63u); stock.key = s_stock_key + (threadIdx.x & ~63u);
     }
-    PathState ps; ps.ro = mk(0, 0, 0); ps.rd = mk(0, 0, 1); ps.thr = mk(1, 1, 1); ps.sidx = 0; ps.ray_index = 0; ps.px = ps.py = 0;
+    PathStateT<STEP> ps; ps.ro = mk(0, 0, 0); ps.rd = mk(0, 0, 1); ps.thr = mk(1, 1, 1); ps.sidx = 0; ps.ray_index = 0; ps.px = ps.py = 0;
     ps.rng.clear();
     bool live = false;
     uint32_t n_paths = 0, n_rays = 0;
@@ -584,7 +614,7 @@ DI void render_ctr_lockstep(const RenderParams& P) {
                 }
                 wave_lds_handoff();                        // (camera() writes into slots whose entries other lanes were dealt)
                 stock.park_a[lane] = make_float4(ps.ro.x, ps.ro.y, ps.ro.z, ps.rd.x); stock.park_b[lane] = make_float2(ps.rd.y, ps.rd.z);
-                if (lane < n_cam) stock.camera(P, wc.next + lane, (wc.ring_head + wc.ring_count + lane) & 63u, ps.ro, ps.rd);
+                if (lane < n_cam) stock.template camera<RngCtrT<STEP>>(P, wc.next + lane, (wc.ring_head + wc.ring_count + lane) & 63u, ps.ro, ps.rd, /* here = 0: sample indices stay below 2^31 (band_samples) */ wc.next >> 31);
             }
         }
         if (n_cam != 0u ? lane < n_cam : live) hit = hit_scene<HAS_MESH, true, KINDS, BOUNDED>(prims, P.n_prims, P.nodes, P.tris, ps.ro, ps.rd, h, pmask);     // renderer.rs:24
@@ -634,13 +664,24 @@ DI void render_ctr_lockstep(const RenderParams& P) {
 //   k_render_ctr_simple_qc  the same for lists of quads and cubes only              (cornell: another -1.1 %)                         7 waves/SIMD
 //   k_render_ctr_nospec     no metal, no dielectric, no mesh                        (-2.5 % vs nomesh on veach-mis; the probe kernel) 7 waves/SIMD
 //   k_render_ctr_mesh       lockstep with the per-lane BVH walk inlined             (diagnostic knob; the two degenerate renders: an empty list, max_depth 0)
-__global__ void __launch_bounds__(BLOCK_THREADS) MI355RT_OCC_LS k_render_ctr_nomesh(const RenderParams P) { render_ctr_lockstep<false, MATS_ALL>(P); }
-__global__ void __launch_bounds__(BLOCK_THREADS) MI355RT_OCC_SIMPLE k_render_ctr_simple(const RenderParams P) { render_ctr_lockstep<false, MATS_LAMBERT>(P); }
+// Which kernels keep the generator's draw address in LCG-stepped form (rt_rng.h, RngCtrT<true>): one bit per kernel.  The form saves the generator's
+// four-multiply LCG step in every block after a path's first, and moves the register allocation of every kernel it touches; a kernel keeps it only where
+// its figures stay inside tests/test_isa_budget.py with no more SGPR spills and no more v_readlane / v_writelane in its loop than the plain form has
+// (profiles/isa_diff_stepped_generator_vs_parent.txt), and where it measures faster on the kernel's workload (profiles/bench_stepped_generator_vs_parent.txt).
+// A kernel whose bit is clear compiles to the instructions it had before the form existed.  -DMI355RT_STEP_MASK=... builds the other choices for A/B.
+enum : uint32_t { STEP_SIMPLE_QC = 1u, STEP_SIMPLE = 2u, STEP_NOSPEC = 4u, STEP_NOMESH = 8u, STEP_MESH = 16u, STEP_WF = 32u, STEP_WF_NOMETAL = 64u,
+                  STEP_WF_NOMETAL_SHALLOW = 128u, STEP_WF_NOMETAL_IDENT = 256u, STEP_WF_MESHFREE = 512u, STEP_WF_FIXAABB = 1024u };
+#ifndef MI355RT_STEP_MASK
+#define MI355RT_STEP_MASK (STEP_SIMPLE_QC)
+#endif
+constexpr bool step_form(uint32_t kernel_bit) { return ((uint32_t)(MI355RT_STEP_MASK) & kernel_bit) != 0u; }
+__global__ void __launch_bounds__(BLOCK_THREADS) MI355RT_OCC_LS k_render_ctr_nomesh(const RenderParams P) { render_ctr_lockstep<false, MATS_ALL, PRIMS_ALL, false, false, step_form(STEP_NOMESH)>(P); }
+__global__ void __launch_bounds__(BLOCK_THREADS) MI355RT_OCC_SIMPLE k_render_ctr_simple(const RenderParams P) { render_ctr_lockstep<false, MATS_LAMBERT, PRIMS_ALL, false, false, step_form(STEP_SIMPLE)>(P); }
 // ... and the Lambert-only kernel for lists of quads and cubes (round 5: cornell -1.1 %, profiles/r05/ab_scalar_diet.txt r05_q16), with its camera rays'
 // first hits in stock (HitStock: cornell -3.7 %, profiles/ab_stocked_first_hits.txt)
-__global__ void __launch_bounds__(BLOCK_THREADS) MI355RT_OCC_SIMPLE k_render_ctr_simple_qc(const RenderParams P) { render_ctr_lockstep<false, MATS_LAMBERT, PRIMS_QUAD_CUBE, /* PREHIT */ true, /* BOUNDED */ true>(P); }
-__global__ void __launch_bounds__(BLOCK_THREADS) MI355RT_OCC_SIMPLE k_render_ctr_nospec(const RenderParams P) { render_ctr_lockstep<false, MATS_NO_SPECULAR>(P); }
-__global__ void __launch_bounds__(BLOCK_THREADS) __attribute__((amdgpu_waves_per_eu(6, 6))) k_render_ctr_mesh(const RenderParams P) { render_ctr_lockstep<true, MATS_ALL>(P); }
+__global__ void __launch_bounds__(BLOCK_THREADS) MI355RT_OCC_SIMPLE k_render_ctr_simple_qc(const RenderParams P) { render_ctr_lockstep<false, MATS_LAMBERT, PRIMS_QUAD_CUBE, /* PREHIT */ true, /* BOUNDED */ true, step_form(STEP_SIMPLE_QC)>(P); }
+__global__ void __launch_bounds__(BLOCK_THREADS) MI355RT_OCC_SIMPLE k_render_ctr_nospec(const RenderParams P) { render_ctr_lockstep<false, MATS_NO_SPECULAR, PRIMS_ALL, false, false, step_form(STEP_NOSPEC)>(P); }
+__global__ void __launch_bounds__(BLOCK_THREADS) __attribute__((amdgpu_waves_per_eu(6, 6))) k_render_ctr_mesh(const RenderParams P) { render_ctr_lockstep<true, MATS_ALL, PRIMS_ALL, false, false, step_form(STEP_MESH)>(P); }
 
 }  // namespace mi355rt
 
@@ -804,7 +845,7 @@ __global__ void __launch_bounds__(64) k_debug_scatter(const DevMat* __restrict__
     const DebugScatterIn r = in[i];
     Hit h; h.t = 0.f; h.p = mk(r.p[0], r.p[1], r.p[2]); h.n = mk(r.n[0], r.n[1], r.n[2]);
     h.mat_ff = r.material | (r.front_face ? 0x80000000u : 0u);
-    RngCtr rng; rng.start(r.k0, r.k1, r.x, r.s); rng.set_ray(r.ray); rng.load_block0();
+    RngCtrT<true> rng; rng.start(r.k0, r.k1, r.x, r.s); rng.set_ray(r.ray); rng.load_block0();     // (the stepped form: any ray number, any try number)
     const float4 q0 = reinterpret_cast<const float4*>(mats + r.material)[0];
     f3 no = mk(0, 0, 0), nd = mk(0, 0, 0), atten = mk(0, 0, 0), emitted = mk(0, 0, 0);
     const bool ok = surface_scatter(mats, texs, q0, h, mk(r.rd[0], r.rd[1], r.rd[2]), rng, no, nd, atten, emitted);

@@ -68,10 +68,13 @@ DI void occluded_segments(const OcclusionParams& P) {
 
 // The ray of sample s of the pixel (x, y) whose first hit is (p, n): a point of the unit ball by rejection (16 tries, then the zero vector)
 // added to the normal; mi355rt.h spells out every operation.
-DI f3 ao_direction(uint32_t x, uint32_t y, uint32_t s, uint32_t seed, f3 n) {
+// Try j draws pcg4d(x, y, s * 16 + j, seed).  The generator's LCG step (rt_rng.h) is taken once: the caller passes x, y and seed already stepped
+// (constant per pixel), and the third word runs, (s * 16 + j) * A + C = (s * 16 * A + C) + j * A: the same integers mod 2^32, the same draws.
+DI f3 ao_direction(uint32_t x_stepped, uint32_t y_stepped, uint32_t s, uint32_t seed_stepped, f3 n) {
     f3 v = mk(0.f, 0.f, 0.f);
-    for (uint32_t j = 0; j < 16u; ++j) {
-        uint32_t w[4]; pcg4d(x, y, s * 16u + j, seed, w);
+    uint32_t z = lcg_step(s * 16u);
+    for (uint32_t j = 0; j < 16u; ++j, z += LCG_A) {
+        uint32_t w[4]; pcg4d_stepped(x_stepped, y_stepped, z, seed_stepped, w);
         const f3 c = mk(u32_to_f01(w[0]) * 2.0f - 1.0f, u32_to_f01(w[1]) * 2.0f - 1.0f, u32_to_f01(w[2]) * 2.0f - 1.0f);
         if (dot(c, c) < 1.0f) { v = c; break; }
     }
@@ -96,19 +99,20 @@ DI void ambient_occlusion(const AoLaunch& P) {
         const uint32_t jrow = P.width_mul ? (__umulhi(pixel, P.width_mul) >> P.width_shift) : pixel;   // pixel / width (host magic pair, pixel < 2^31)
         x = pixel - jrow * P.width; y = P.rows[jrow];
     }
+    const uint32_t xs = lcg_step(x), ys = lcg_step(y), seeds = lcg_step(P.seed);            // the generator's step on the words a pixel's tries share, once
     uint32_t count = 0u;
     if constexpr (SPREAD) {
         const uint32_t lane = threadIdx.x & 63u, first = lane - sub;                        // the group's first lane
         const uint64_t group = lg == 6u ? ~0ull : ((1ull << (1u << lg)) - 1ull);
         for (uint32_t s = sub; s < P.samples; s += 64u) {                                   // samples / g iterations, the same for every lane
             bool occ = false;
-            if (live) occ = occluded<HAS_MESH>((cprim_t)P.prims, P.n_prims, P.nodes, P.tris, p, ao_direction(x, y, s, P.seed, n), P.radius, P.may_exit != 0u);
+            if (live) occ = occluded<HAS_MESH>((cprim_t)P.prims, P.n_prims, P.nodes, P.tris, p, ao_direction(xs, ys, s, seeds, n), P.radius, P.may_exit != 0u);
             count += (uint32_t)__popcll((__ballot(occ) >> first) & group);
         }
         if (sub != 0u) return;
     } else {
         if (live) for (uint32_t s = 0; s < P.samples; ++s)
-            count += occluded<HAS_MESH>((cprim_t)P.prims, P.n_prims, P.nodes, P.tris, p, ao_direction(x, y, s, P.seed, n), P.radius, P.may_exit != 0u) ? 1u : 0u;
+            count += occluded<HAS_MESH>((cprim_t)P.prims, P.n_prims, P.nodes, P.tris, p, ao_direction(xs, ys, s, seeds, n), P.radius, P.may_exit != 0u) ? 1u : 0u;
     }
     if (inside) P.out[pixel] = live ? 1.0f - (float)count / (float)P.samples : 1.0f;
 }

@@ -208,7 +208,7 @@ struct WfQueues {
 // MESH_IDENT: every mesh of the list is untransformed (the host picks this instantiation then): see ray_nonzero_finite() in rt_intersect.h.
 // INLINE_STEPS: box tests of a walk that TOP runs itself when at least half the wave is inside the root box (8; 12 measured better for the deep trees of the
 // scene the MESH_IDENT form serves: teapot -0.7 %, and worse for semesterbild's shallower one: +0.8 %).
-template <bool FIXED_AABB, uint32_t MATS, bool HAS_MESH = true, bool MESH_IDENT = false, int INLINE_STEPS = 8, int WF_ROUNDS = 3, int WF_STEPS = 8>
+template <bool FIXED_AABB, uint32_t MATS, bool HAS_MESH = true, bool MESH_IDENT = false, int INLINE_STEPS = 8, int WF_ROUNDS = 3, int WF_STEPS = 8, bool STEP = false>
 DI void render_ctr_wavefront(const RenderParams& P) {
     typedef SlotIO Slot;
     constexpr uint32_t WF_PATHS = HAS_MESH ? mi355rt::WF_PATHS : WF_PATHS_MESHFREE, WF_SLOT_WORDS = HAS_MESH ? mi355rt::WF_SLOT_WORDS : 16u;
@@ -384,7 +384,7 @@ DI void render_ctr_wavefront(const RenderParams& P) {
             uint32_t* sl = slots + WF_SLOT_WORDS * id;
             // (the defaults stay: with the path state and the record left uninitialised for the lanes that hold no slot the same
             // kernel ran 50 % slower -- 41.5 instead of 27.9 ms on semesterbild)
-            PathState ps; ps.ro = mk(0, 0, 0); ps.rd = mk(0, 0, 1); ps.thr = mk(1, 1, 1); ps.sidx = 0; ps.ray_index = 0; ps.px = ps.py = 0;
+            PathStateT<STEP> ps; ps.ro = mk(0, 0, 0); ps.rd = mk(0, 0, 1); ps.thr = mk(1, 1, 1); ps.sidx = 0; ps.ray_index = 0; ps.px = ps.py = 0;
             ps.rng.clear();
             Cand c; cand_reset(c);
             if (have) Slot::load_shade(sl, ps.ro, ps.rd, ps.thr, ps.sidx, ps.ray_index, c);     // (the generator state is a function of sidx / ray_index: shade_and_regenerate derives it, REKEY)
@@ -524,20 +524,21 @@ DI void render_ctr_wavefront(const RenderParams& P) {
     }
 }
 #define MI355RT_OCC_WFK __attribute__((amdgpu_waves_per_eu(6, 6)))         // 80 VGPRs: 2 workgroups of 12 waves per CU (see the top of this file)
+// (the last template argument: the generator's draw address in stepped form, per kernel -- rt_kernels.hip, MI355RT_STEP_MASK)
 // Entry points: one body per material set (rt_device.h) -- and, for the set the mesh scenes use, per transform class of the meshes; the opt-in slab test only in the general form.
-__global__ void __launch_bounds__(BLOCK_THREADS_WF) MI355RT_OCC_WFK k_render_ctr_wf(const RenderParams P) { render_ctr_wavefront<false, MATS_ALL>(P); }
+__global__ void __launch_bounds__(BLOCK_THREADS_WF) MI355RT_OCC_WFK k_render_ctr_wf(const RenderParams P) { render_ctr_wavefront<false, MATS_ALL, true, false, 8, 3, 8, step_form(STEP_WF)>(P); }
 // WALK geometry by tree size (round 5; template arguments INLINE_STEPS, WF_ROUNDS, WF_STEPS): large trees want LONGER rounds -- teapot (8 191 / 14 161 nodes, depth 12 / 13), kernel ms at 800x600x256
 // (profiles/r05/ab_wavefront_walk_geometry_deep.txt): on its own instantiation 3 x 8 15.49, 3 x 9 15.31*, **3 x 10 15.33 (-1.0 %)**, 3 x 11 15.36, 3 x 12 15.59, 4 x 10 15.55, 2 x 12 15.33*; forced onto this general
 // form: 8 inline steps + 3 x 8 16.01, 8 + 3 x 10 15.81, **12 + 3 x 10 15.66 (-2.2 %)** (* = another session, base 15.40) -- small trees want SHORTER ones (k_render_ctr_wf_nometal_shallow below).
-__global__ void __launch_bounds__(BLOCK_THREADS_WF) MI355RT_OCC_WFK k_render_ctr_wf_nometal(const RenderParams P) { render_ctr_wavefront<false, MATS_NO_METAL, true, false, 12, 3, 10>(P); }
+__global__ void __launch_bounds__(BLOCK_THREADS_WF) MI355RT_OCC_WFK k_render_ctr_wf_nometal(const RenderParams P) { render_ctr_wavefront<false, MATS_NO_METAL, true, false, 12, 3, 10, step_form(STEP_WF_NOMETAL)>(P); }
 // ... and for lists whose meshes all have SMALL trees (every mesh <= WF_SHALLOW_NODES nodes: semesterbild's text mesh, 3 351 nodes, depth 11): WALK passes of 3 x 6 box tests instead of
 // 3 x 8 -- a shallow walk ends or stalls sooner, so the last steps of an 8-step round run nearly empty.  Round 5, 800x600x256 kernel ms (profiles/r05/ab_wavefront_walk_geometry_shallow.txt):
 // 3x8 26.68, 4x6 26.46, 3x6 26.36 (-1.2 %), 5x5 26.61, 4x5 26.63; teapot's deep trees (8 191 / 14 161 nodes) want 3 x 8 (every other geometry +1 ... +2.8 %, round 4).
-__global__ void __launch_bounds__(BLOCK_THREADS_WF) MI355RT_OCC_WFK k_render_ctr_wf_nometal_shallow(const RenderParams P) { render_ctr_wavefront<false, MATS_NO_METAL, true, false, 8, 3, 6>(P); }
+__global__ void __launch_bounds__(BLOCK_THREADS_WF) MI355RT_OCC_WFK k_render_ctr_wf_nometal_shallow(const RenderParams P) { render_ctr_wavefront<false, MATS_NO_METAL, true, false, 8, 3, 6, step_form(STEP_WF_NOMETAL_SHALLOW)>(P); }
 // ... and for lists whose meshes are all untransformed (teapot -1.9 % at 256 spp, another -0.7 % with 12 inline steps; profiles/r04/ab_wavefront_transform_classes.txt; round 5: rounds of 10 box tests, -1.0 %)
-__global__ void __launch_bounds__(BLOCK_THREADS_WF) MI355RT_OCC_WFK k_render_ctr_wf_nometal_ident(const RenderParams P) { render_ctr_wavefront<false, MATS_NO_METAL, true, true, 12, 3, 10>(P); }
-__global__ void __launch_bounds__(BLOCK_THREADS_WF_MESHFREE) __attribute__((amdgpu_waves_per_eu(8, 8))) k_render_ctr_wf_meshfree(const RenderParams P) { render_ctr_wavefront<false, MATS_NO_SPECULAR, false>(P); }
-__global__ void __launch_bounds__(BLOCK_THREADS_WF) MI355RT_OCC_WFK k_render_ctr_wf_fixaabb(const RenderParams P) { render_ctr_wavefront<true, MATS_ALL>(P); }
+__global__ void __launch_bounds__(BLOCK_THREADS_WF) MI355RT_OCC_WFK k_render_ctr_wf_nometal_ident(const RenderParams P) { render_ctr_wavefront<false, MATS_NO_METAL, true, true, 12, 3, 10, step_form(STEP_WF_NOMETAL_IDENT)>(P); }
+__global__ void __launch_bounds__(BLOCK_THREADS_WF_MESHFREE) __attribute__((amdgpu_waves_per_eu(8, 8))) k_render_ctr_wf_meshfree(const RenderParams P) { render_ctr_wavefront<false, MATS_NO_SPECULAR, false, false, 8, 3, 8, step_form(STEP_WF_MESHFREE)>(P); }
+__global__ void __launch_bounds__(BLOCK_THREADS_WF) MI355RT_OCC_WFK k_render_ctr_wf_fixaabb(const RenderParams P) { render_ctr_wavefront<true, MATS_ALL, true, false, 8, 3, 8, step_form(STEP_WF_FIXAABB)>(P); }
 
 
 }  // namespace mi355rt

@@ -37,7 +37,7 @@ def load(so):
 
 def refs():
     """The tests' reference build: the product sources plus the retired mesh kernel (the state machine), mi355rt_debug_stages and the
-    resolve / gather probe (mi355rt_debug_resolve, mi355rt_debug_gather), -DMI355RT_REFS."""
+    resolve / gather probe (mi355rt_debug_resolve, mi355rt_debug_gather) and the generator probe (mi355rt_debug_rng_block), -DMI355RT_REFS."""
     L = load(build.build_device_variant("refs", ["MI355RT_REFS"]))
     L.mi355rt_debug_stages.restype = C.c_int
     L.mi355rt_debug_stages.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
@@ -45,6 +45,8 @@ def refs():
     L.mi355rt_debug_resolve.argtypes = [C.c_void_p]
     L.mi355rt_debug_gather.restype = C.c_int
     L.mi355rt_debug_gather.argtypes = [C.c_void_p]
+    L.mi355rt_debug_rng_block.restype = C.c_int
+    L.mi355rt_debug_rng_block.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_int]
     return L
 
 
@@ -78,6 +80,17 @@ def debug_gather(src_row, n_rows, width, src_packed=0, dst_packed=0, src_linear=
                         int(n_rows), int(width))
     L = refs()
     _check(L.mi355rt_debug_gather(C.addressof(a)), "mi355rt_debug_gather", L)
+
+
+def debug_rng_block(records, hip_device=0):
+    """Diagnostic (reference build, csrc/refs/rt_rng_probe.hip): one block of the counter-mode generator per record.  records: uint32 [n, 6] =
+    (key lo, key hi, x, sample, ray, try).  Returns uint32 [n, 3, 4]: the block through the plain draw address, through the stepped one
+    (set_ray + next_event, the full multiply for the try) and through the stepped form's running word (unit_ball_cooperative's arithmetic)."""
+    L = refs()
+    rec = np.ascontiguousarray(records, np.uint32).reshape(-1, 6)
+    out = np.zeros((rec.shape[0], 3, 4), np.uint32)
+    _check(L.mi355rt_debug_rng_block(rec.ctypes.data, rec.shape[0], out.ctypes.data, hip_device), "mi355rt_debug_rng_block", L)
+    return out
 
 
 # mi355rt_debug_stages (csrc/refs/rt_stages.hip; the oracle's twin is oracle_debug_stages): stage numbers and the argument record
