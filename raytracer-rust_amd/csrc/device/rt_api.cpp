@@ -35,7 +35,8 @@ static int report_device_error(mi355rt_context* ctx, bool this_render = false);
 struct mi355rt_context {
     int device = 0;
     int cu_count = 0;
-    int blocks_per_cu[KERNEL_VARIANTS] = {}, vgprs[KERNEL_VARIANTS] = {}, sgprs = 0;
+    int blocks_per_cu[KERNEL_ENTRIES][KERNEL_VARIANTS] = {}, vgprs[KERNEL_ENTRIES][KERNEL_VARIANTS] = {}, sgprs = 0;   // per entry point (rt_device.h ENTRY_*): with / without a sky texture
+    uint32_t entry() const { return variant_entry(variant, sky_w != 0); }   // the entry point the resident scene is launched on
     uint32_t variant = KERNEL_LOCKSTEP;  // chosen per scene in set_scene
     bool has_mesh = false;
     bool occlusion_may_exit = false;     // every number the hit tests read from the scene lies inside OCCLUSION_BOUND: the occlusion kernels may leave the list early (rt_prepare.h)
@@ -88,6 +89,7 @@ struct mi355rt_context {
     DevBuf<unsigned long long> errword; unsigned long long* h_err = nullptr; unsigned long long err_reported = 0;
     uint32_t spin_limit_idle = SPIN_LIMIT_IDLE, spin_limit_entry = SPIN_LIMIT_ENTRY;   // diagnostic knobs "spin_idle" / "spin_entry"
     uint32_t launched_variants = 0;      // bit v: kernel variant v was launched since the last failure report (names the kernel in the message)
+    uint32_t launched_sky_entries = 0;   // bit v: ... on its entry point for scenes with a sky texture
     int forced_variant = -1;             // diagnostic knob "kernel": applied by set_scene when the scene allows it
     int knob_inline_steps = -1;          // diagnostic knob "inline_steps" (reference build's state machine)
     // timing pool (mi355rt_context_set_timing): event triples recorded around every kernel pair without
@@ -126,8 +128,9 @@ static int report_device_error(mi355rt_context* ctx, bool this_render) {
         {WAIT_WF_IDLE, "idle: no progress in the workgroup"}, {WAIT_WF_RING, "ring entry: a reserved ticket was never written, or an entry never emptied"},
         {WAIT_WF_FOLLOWED, "waves that followed their workgroup's error flag out"}};
     std::string kernels, which;
-    for (uint32_t v = 0; v < KERNEL_VARIANTS; ++v) if ((ctx->launched_variants >> v) & 1u) kernels += std::string(kernels.empty() ? "" : ", ") + VARIANT_TABLE[v].kernel + " (variant " + std::to_string(v) + ")";
-    ctx->launched_variants = 0;
+    for (uint32_t v = 0; v < KERNEL_VARIANTS; ++v) if ((ctx->launched_variants >> v) & 1u)
+        kernels += std::string(kernels.empty() ? "" : ", ") + entry_kernel_name(v, (ctx->launched_sky_entries >> v) & 1u ? ENTRY_SKY : ENTRY_PLAIN) + " (variant " + std::to_string(v) + ")";
+    ctx->launched_variants = 0; ctx->launched_sky_entries = 0;
     for (const auto& w : waits) if ((now >> 32) & w.bit) which += std::string(which.empty() ? "" : "; ") + w.what;
     return fail(MI355RT_ERR_HIP, "kernel watchdog: " + std::to_string(n) + " wave(s) gave up a bounded wait " + (this_render ? "in this render" : "in an earlier render on this context") +
                                  " -- that image is incomplete [kernel(s) launched on this context since the last report: " + (kernels.empty() ? "?" : kernels) + "; wait: " + (which.empty() ? "?" : which) +
@@ -265,7 +268,8 @@ int mi355rt_context_create(int hip_device, mi355rt_context** out_ctx) {
     ctx->cu_count = prop.multiProcessorCount;
     for (uint32_t v = 0; v < KERNEL_VARIANTS; ++v) {
         if (!render_ctr_variant_built(v)) continue;                    // the retired mesh kernels exist in the tests' reference build only
-        if (query_render_ctr_occupancy(v, &ctx->blocks_per_cu[v], &ctx->vgprs[v], &ctx->sgprs) != 0 || ctx->blocks_per_cu[v] <= 0) {
+        for (uint32_t e = 0; e < KERNEL_ENTRIES; ++e)
+        if (query_render_ctr_occupancy(v, e, &ctx->blocks_per_cu[e][v], &ctx->vgprs[e][v], &ctx->sgprs) != 0 || ctx->blocks_per_cu[e][v] <= 0) {
             delete ctx;
             return fail(MI355RT_ERR_HIP, std::string("kernel image not usable on this device (") + prop.gcnArchName + "); built for gfx950");
         }
@@ -394,7 +398,7 @@ static int render_samples(mi355rt_context* ctx, const mi355rt_options* opt, uint
     if (int erc = report_device_error(ctx)) return erc;              // an earlier asynchronous render on this context failed (no wait: what has finished so far)
     const mi355rt_settings& st = ctx->settings;
     uint32_t block_slots[KERNEL_VARIANTS];
-    for (uint32_t v = 0; v < KERNEL_VARIANTS; ++v) block_slots[v] = (uint32_t)(ctx->cu_count * ctx->blocks_per_cu[v]);
+    for (uint32_t v = 0; v < KERNEL_VARIANTS; ++v) block_slots[v] = (uint32_t)(ctx->cu_count * ctx->blocks_per_cu[variant_entry(v, ctx->sky_w != 0)][v]);   // (of the entry point that launch_render_ctr picks)
     const RenderPlanIn in{&st, opt, s0, s1, d_accum != nullptr, ctx->variant, ctx->has_mesh, ctx->n_prims, !ctx->row_cost.empty(), d_row_counters != nullptr,
                           block_slots, ctx->grid_div, ctx->guided_mult};
     RowSel sel; RenderPlan plan;
@@ -417,7 +421,7 @@ static int render_samples(mi355rt_context* ctx, const mi355rt_options* opt, uint
     }
     const uint32_t variant = plan.variant;
     const uint32_t n_rows = (uint32_t)ctx->rows_host.size();
-    if (stats) { std::memset(stats, 0, sizeof *stats); stats->rows_rendered = n_rows; stats->kernel_vgprs = (uint32_t)ctx->vgprs[variant]; stats->kernel_sgprs = (uint32_t)ctx->sgprs; }
+    if (stats) { std::memset(stats, 0, sizeof *stats); stats->rows_rendered = n_rows; stats->kernel_vgprs = (uint32_t)ctx->vgprs[variant_entry(variant, ctx->sky_w != 0)][variant]; stats->kernel_sgprs = (uint32_t)ctx->sgprs; }
     if (n_rows == 0) return MI355RT_OK;
 
     if (!same_rows) {
@@ -508,6 +512,7 @@ static int render_samples(mi355rt_context* ctx, const mi355rt_options* opt, uint
             if (pe0) HIP_TRY(hipEventRecord(pe0, stream));
             if (launch_render_ctr(p, variant, band.grid, stream) != 0) return fail(MI355RT_ERR_HIP, "k_render_ctr launch failed");
             ctx->launched_variants |= 1u << variant;
+            if (variant_entry(variant, p.sky != nullptr) == ENTRY_SKY) ctx->launched_sky_entries |= 1u << variant;
             if (stats) HIP_TRY(hipEventRecord(ctx->ev[1], stream));
             if (pe1) HIP_TRY(hipEventRecord(pe1, stream));
             if (!d_row_counters && launch_resolve(r, stream) != 0) return fail(MI355RT_ERR_HIP, "k_resolve launch failed");
@@ -716,6 +721,20 @@ int mi355rt_debug_kernel_variant(mi355rt_context* ctx, uint32_t* out) {
     *out = ctx->variant;
     return MI355RT_OK;
     });
+}
+
+// Diagnostic hook (not part of the public header): the entry point the resident scene is launched on -- its kernel's name (a static string), how many of
+// its workgroups the device holds per CU, and its VGPRs.  Variant 14 has two (rt_device.h ENTRY_*): with and without a sky texture.  Returns the name, or
+// null for a context without a scene (nothing in here allocates or throws).
+const char* mi355rt_debug_kernel_entry(mi355rt_context* ctx, uint32_t* out_blocks_per_cu, uint32_t* out_vgprs) {
+    if (!ctx || !out_blocks_per_cu || !out_vgprs || !ctx->have_scene) return nullptr;
+    const uint32_t e = ctx->entry();
+    *out_blocks_per_cu = (uint32_t)ctx->blocks_per_cu[e][ctx->variant]; *out_vgprs = (uint32_t)ctx->vgprs[e][ctx->variant];
+    return entry_kernel_name(ctx->variant, e);
+}
+// ... and the same choice without a device or a context: the name of the kernel a scene on `variant` is launched on, with or without a sky texture.
+const char* mi355rt_debug_entry_kernel(uint32_t variant, int has_sky) {
+    return variant < KERNEL_VARIANTS ? entry_kernel_name(variant, variant_entry(variant, has_sky != 0)) : nullptr;
 }
 
 // Diagnostic hook (not part of the public header): what set_scene would upload and choose for `scene`, without a device -- no HIP call, no

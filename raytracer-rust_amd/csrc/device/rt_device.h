@@ -206,7 +206,7 @@ int launch_resolve(const ResolveParams& p, void* stream);
 int launch_gather_strips(const GatherParams& p, void* stream);
 int launch_gather_accum(const GatherAccumParams& p, void* stream);
 int launch_render_ref(const RefParams& p, void* stream);
-int query_render_ctr_occupancy(uint32_t variant, int* blocks_per_cu, int* vgprs, int* sgprs);
+int query_render_ctr_occupancy(uint32_t variant, uint32_t entry, int* blocks_per_cu, int* vgprs, int* sgprs);   // entry: ENTRY_* (below VARIANT_TABLE)
 bool render_ctr_variant_built(uint32_t variant);   // false for the retired mesh kernels in the product library (they live in the tests' -DMI355RT_REFS build)
 constexpr uint32_t BLOCK_THREADS_WF = 768;                  // wavefront kernel: 12 waves per workgroup (measured against 8 / 10 / 14 / 16: rt_wavefront.h)
 // Wavefront kernel, LDS budget of one workgroup (rt_wavefront.h): control words, one ring per queue, the path slots, and -- in what is
@@ -253,8 +253,15 @@ constexpr VariantInfo VARIANT_TABLE[KERNEL_VARIANTS] = {
     {KERNEL_WAVEFRONT_MESHFREE,        "k_render_ctr_wf_meshfree",        BLOCK_THREADS_WF_MESHFREE,  FAMILY_WAVEFRONT,     MATS_NO_SPECULAR, PRIMS_MESH_FREE, false, true,  KERNEL_WAVEFRONT_MESHFREE},       // the wavefront for lists WITHOUT a mesh, no metal / dielectric: material-sorted SHADE passes for scenes whose materials diverge (veach-mis)
     {KERNEL_WAVEFRONT_NOMETAL_IDENT,   "k_render_ctr_wf_nometal_ident",   BLOCK_THREADS_WF,           FAMILY_WAVEFRONT,     MATS_NO_METAL,    PRIMS_ALL,       true,  true,  KERNEL_WAVEFRONT_FIXAABB},        // KERNEL_WAVEFRONT_NOMETAL for lists whose meshes are all untransformed (teapot): mesh_setup without its matrix products
     {KERNEL_WAVEFRONT_NOMETAL_SHALLOW, "k_render_ctr_wf_nometal_shallow", BLOCK_THREADS_WF,           FAMILY_WAVEFRONT,     MATS_NO_METAL,    PRIMS_ALL,       false, true,  KERNEL_WAVEFRONT_FIXAABB},        // KERNEL_WAVEFRONT_NOMETAL for lists whose meshes all have small trees (semesterbild): WALK passes of 3 x 6 instead of 3 x 8 box tests (only a tuning: any tree is walked correctly)
-    {KERNEL_LOCKSTEP_SIMPLE_QC,        "k_render_ctr_simple_qc",          BLOCK_THREADS,              FAMILY_LOCKSTEP,      MATS_LAMBERT,     PRIMS_QUAD_CUBE, false, true,  KERNEL_LOCKSTEP_SIMPLE_QC},       // KERNEL_LOCKSTEP_SIMPLE for lists of quads and cubes only (cornell): no sphere / plane run checks in the walk, a two-way finish_hit
+    {KERNEL_LOCKSTEP_SIMPLE_QC,        "k_render_ctr_simple_qc",          BLOCK_THREADS,              FAMILY_LOCKSTEP,      MATS_LAMBERT,     PRIMS_QUAD_CUBE, false, true,  KERNEL_LOCKSTEP_SIMPLE_QC},       // KERNEL_LOCKSTEP_SIMPLE for lists of quads and cubes only (cornell): no sphere / plane run checks in the walk, a two-way finish_hit; compiled without the sky lookup, scenes with a sky texture run its twin (SKY_TWIN_KERNEL)
 };
+// A variant's entry points.  Every variant has one kernel for scenes with and without a sky texture, except KERNEL_LOCKSTEP_SIMPLE_QC: its table row names
+// the kernel compiled WITHOUT the sky lookup (8 waves per SIMD), and a resident scene with a texture is launched on the twin that keeps it (7).  The variant
+// number is 14 either way; grid sizes follow the entry's own occupancy.
+enum : uint32_t { ENTRY_PLAIN = 0, ENTRY_SKY = 1, KERNEL_ENTRIES = 2 };
+constexpr const char* SKY_TWIN_KERNEL = "k_render_sky_simple_qc";
+constexpr uint32_t variant_entry(uint32_t variant, bool has_sky) { return (variant == KERNEL_LOCKSTEP_SIMPLE_QC && has_sky) ? ENTRY_SKY : ENTRY_PLAIN; }
+constexpr const char* entry_kernel_name(uint32_t variant, uint32_t entry) { return (variant == KERNEL_LOCKSTEP_SIMPLE_QC && entry == ENTRY_SKY) ? SKY_TWIN_KERNEL : VARIANT_TABLE[variant].kernel; }
 constexpr bool variant_rows_in_order() { for (uint32_t v = 0; v < KERNEL_VARIANTS; ++v) if (VARIANT_TABLE[v].variant != v) return false; return true; }
 static_assert(variant_rows_in_order(), "row v of VARIANT_TABLE describes variant v");
 

@@ -251,10 +251,11 @@ struct RayStock {
 // entries.  A lane that is dealt an entry scatters its first hit in the same iteration, as a continuing lane at ray 0.  Every value of an entry is the
 // one the loop computed for that sample before (same functions, same order), so radiance and ray counts are the same bits.
 // An entry is 64 bytes (four ds_read_b128): {h.p, sample index}, {h.n, mat_ff}, q0, the generator key at ray 0 (pcg4d: its four words; Philox: the
-// key, x and s -- the ray word is 0; the words are the generator's own, stored and reloaded untouched).  The parking area holds ro and rd of the 64 lanes (24 bytes each) during a refill pass.
+// key, x and s -- the ray word is 0; the words are the generator's own, stored and reloaded untouched).  The parking area holds ro and rd of the 64 lanes (24 bytes each) during a refill pass;
+// the kernel compiled without the sky lookup has none and parks them in bytes 0-23 of the (then empty) ring's slots instead: render_ctr_lockstep, PARK_IN_RING.
 struct HitStock {
     float4* e;                                                 // [64][4] this wave's ring of entries
-    float4* park_a; float2* park_b;                            // [64] each: {ro, rd.x}, {rd.y, rd.z}; lane i writes and reads back element i only: no hand-off
+    float4* park_a; float2* park_b;                            // [64] each: {ro, rd.x}, {rd.y, rd.z}; lane i writes and reads back element i only: no hand-off (null with PARK_IN_RING)
     // Before the walk: the camera ray of sample `sidx` into (ro, rd) -- what RayStock::refill and the loop's shared tail computed -- and its key
     // into the entry at `slot` (the entry's other words are written after the walk).  The slot is one that another lane was dealt earlier, and append()
     // reads the key from another lane: the caller puts a wave_lds_handoff() in front of the camera() calls and one behind them.
@@ -276,12 +277,14 @@ struct HitStock {
     }
     // After the walk (lanes with cam == true walked sample first + lane from `tail` + lane): finish the paths that end at their camera ray, exactly as
     // shade_and_regenerate classifies a path at ray 0 (throughput 1), and append the others to the ring in sample order.  Returns how many were appended.
+    // NOSKY: see shade_and_regenerate; `rd` is then not read.
+    template <bool NOSKY = false>
     DI uint32_t append(const RenderParams& P, uint32_t lane, uint32_t first, uint32_t tail, bool cam, bool hit, const Hit& h, f3 rd) const {
         struct Rad { float x, y, z; };
         bool keep = false;
         if (cam) {
             f3 term = mk(0.f, 0.f, 0.f); bool fin = false;
-            if (!hit) { term = miss_colour(P.sky, P.sky_w, P.sky_h, P.miss, rd); fin = true; }      // renderer.rs:38-63
+            if (!hit) { if constexpr (NOSKY) term = mk(P.miss[0], P.miss[1], P.miss[2]); else term = miss_colour(P.sky, P.sky_w, P.sky_h, P.miss, rd); fin = true; }      // renderer.rs:38-63
             else {
                 const uint32_t kind = __float_as_uint(h.q0.x);
                 if (kind == MI355RT_MAT_EMISSIVE) { term = mk(h.q0.y, h.q0.z, h.q0.w); fin = true; }
@@ -402,7 +405,10 @@ DI f3 unit_ball_cooperative(bool diffuse, const RNG& rng, uint32_t lane, const u
 // REKEY (wavefront kernel: a path's generator state is not carried in its slot): the state is derived from the sample index HERE, once, for continuing
 // and freshly dealt lanes together, right in front of the event's block -- instead of by the caller when the slot is loaded (live through the hit record,
 // the material read and the radiance store) and a second time where fresh samples are dealt.
-template <uint32_t MATS, bool DEFAULTS = true, bool WIDE = !DEFAULTS, bool DROP_PRIO = false, bool Q0_IN_HIT = false, bool FASTN = false, int TRY1 = 0, bool REKEY = false, class WC, class PS, class STOCK = NoStock>
+// NOSKY: this instantiation is never launched with a sky texture (launch_render_ctr sees to it): a miss returns P.miss, three scalar registers.  Compiled in,
+// the lookup of miss_colour() sits in the loop whether or not a scene has a sky -- its polynomial constants in vector registers across the whole
+// iteration, and `sky == nullptr ? &P.miss : texel` as a pointer select with a per-lane load from the kernel-argument segment behind every miss.
+template <uint32_t MATS, bool DEFAULTS = true, bool WIDE = !DEFAULTS, bool DROP_PRIO = false, bool Q0_IN_HIT = false, bool FASTN = false, int TRY1 = 0, bool REKEY = false, bool NOSKY = false, class WC, class PS, class STOCK = NoStock>
 DI bool shade_and_regenerate(const RenderParams& P, WC& wc, uint32_t lane, bool& live, bool can_take, bool hit, const Hit& h,
                              PS& ps, uint32_t& n_paths, uint32_t& n_rays, Prof& prof, const STOCK& stock = STOCK()) {
     typedef typename PS::Rng Rng;                                                            // RngCtrT<STEP>: the kernel's form of the draw address
@@ -416,7 +422,7 @@ DI bool shade_and_regenerate(const RenderParams& P, WC& wc, uint32_t lane, bool&
     if (DEFAULTS) q0 = make_float4(0.f, 0.f, 0.f, 0.f);
     if (live) {
         f3 term = mk(0.f, 0.f, 0.f); bool fin = false;
-        if (!hit) { term = miss_colour(P.sky, P.sky_w, P.sky_h, P.miss, ps.rd); fin = true; }   // renderer.rs:38-63
+        if (!hit) { if constexpr (NOSKY) term = mk(P.miss[0], P.miss[1], P.miss[2]); else term = miss_colour(P.sky, P.sky_w, P.sky_h, P.miss, ps.rd); fin = true; }   // renderer.rs:38-63
         else {
             if constexpr (Q0_IN_HIT) q0 = h.q0;                                              // (finish_hit read it with the hit record)
             else q0 = reinterpret_cast<const float4*>(P.mats + (h.mat_ff & 0x7FFFFFFFu))[0];
@@ -546,7 +552,19 @@ DI bool shade_and_regenerate(const RenderParams& P, WC& wc, uint32_t lane, bool&
                                                             // 7 -> 5.73.  After the instruction diet: 7 -> 4.94, 6 -> 4.88, and with the cube hit point
                                                             // carried (3 more registers): 7 -> 5.03 (spills), 6 -> 4.81, 5 -> 5.04
 #define MI355RT_OCC_LS __attribute__((amdgpu_waves_per_eu(MI355RT_OCC_LOCKSTEP, MI355RT_OCC_LOCKSTEP)))
-#define MI355RT_OCC_SIMPLE __attribute__((amdgpu_waves_per_eu(7, 7)))
+#define MI355RT_OCC_SIMPLE __attribute__((amdgpu_waves_per_eu(7, 7)))   // k_render_ctr_simple, k_render_ctr_nospec, k_render_sky_simple_qc: 72 VGPRs
+// k_render_ctr_simple_qc, compiled without the sky lookup (NOSKY), step by step; each define's 0 builds the form before it (A/B:
+// profiles/bench_nosky_eight_waves_vs_parent.txt).  8 waves per SIMD need 64 VGPRs and the rays parked in the ring (16 KB of LDS per workgroup).
+#ifndef MI355RT_NOSKY_RECIP_FIRST
+#define MI355RT_NOSKY_RECIP_FIRST 1
+#endif
+#ifndef MI355RT_NOSKY_PARK_IN_RING
+#define MI355RT_NOSKY_PARK_IN_RING 1
+#endif
+#ifndef MI355RT_NOSKY_WAVES
+#define MI355RT_NOSKY_WAVES 8
+#endif
+#define MI355RT_OCC_NOSKY __attribute__((amdgpu_waves_per_eu(MI355RT_NOSKY_WAVES, MI355RT_NOSKY_WAVES)))
 #define MI355RT_OCC_SMK __attribute__((amdgpu_waves_per_eu(4, 4)))      // (reference build's state machine)
 
 // ===================================================================================================
@@ -559,9 +577,17 @@ DI bool shade_and_regenerate(const RenderParams& P, WC& wc, uint32_t lane, bool&
 // unit-ball draw in the lane itself before the cooperative rounds (0 tries: +1.9 %, 2 tries: +-0 with pcg4d, +23 % with Philox: profiles/r05/ab_counter_generator.txt).
 // PREHIT: the wave stocks its camera rays' first hits (HitStock), walked in refill passes through the loop's one walk site.
 // STEP: the generator's draw address in LCG-stepped form (rt_rng.h); per kernel, see the entry points below.
-template <bool HAS_MESH, uint32_t MATS, uint32_t KINDS = PRIMS_ALL, bool PREHIT = false, bool BOUNDED = false, bool STEP = false>
+// NOSKY: never launched with a sky texture (shade_and_regenerate); with it the cube's reciprocals run first (recip3) and the refill pass parks the paths'
+// rays inside the ring (below), each behind its build define so that the form before it can still be built for an A/B.
+template <bool HAS_MESH, uint32_t MATS, uint32_t KINDS = PRIMS_ALL, bool PREHIT = false, bool BOUNDED = false, bool STEP = false, bool NOSKY = false>
 DI void render_ctr_lockstep(const RenderParams& P) {
     constexpr bool SIMPLE = (MATS & ~MATS_LAMBERT) == 0u;
+    constexpr bool RECIP_FIRST = NOSKY && BOUNDED && (MI355RT_NOSKY_RECIP_FIRST != 0);
+    // The refill pass parks the paths' rays INSIDE the ring: a refill happens only when the ring is empty, camera() writes bytes 48-63 of a slot and nothing
+    // else until append(), so lane i keeps its 24 bytes in bytes 0-23 of slot i and takes them back right behind the walk, in front of append() -- which,
+    // without a sky, does not read the camera ray's direction.  16 KB of LDS per workgroup instead of 22: the eighth workgroup of a CU fits.
+    constexpr bool PARK_IN_RING = NOSKY && PREHIT && (MI355RT_NOSKY_PARK_IN_RING != 0);
+    static_assert(!PARK_IN_RING || MI355RT_PREHIT_LOW == 1, "rays are parked in the ring's slots: a refill must find the ring empty");
     // The mesh-free kernels are compiled for lists that hold something and for paths that may take a step: the host sends an empty list or max_depth == 0 to
     // k_render_ctr_mesh, the plain loop (rt_api.cpp render_samples).  Both are launch constants, and the compiler had turned `n_prims != 0` and `max_depth == 0`
     // into lane masks tested in every iteration (the masks spilled: four v_readlane, two mask operations, two branches): cornell -1.9 %.
@@ -572,10 +598,14 @@ DI void render_ctr_lockstep(const RenderParams& P) {
     WorkCursor wc; wc.init();
     std::conditional_t<PREHIT, HitStock, RayStock> stock;
     if constexpr (PREHIT) {                                                                    // HitStock: 64 entries of 64 B + 1.5 KB of parked rays per wave
-        __shared__ __attribute__((aligned(16))) float4 s_ring[4u * BLOCK_THREADS];             // (22 KB per workgroup: 7 workgroups fit in 160 KB)
+        __shared__ __attribute__((aligned(16))) float4 s_ring[4u * BLOCK_THREADS];             // (22 KB per workgroup: 7 workgroups fit in 160 KB; PARK_IN_RING: 16 KB, 8 fit)
+        stock.e = s_ring + 4u * (threadIdx.x & ~63u);
+        if constexpr (PARK_IN_RING) { stock.park_a = nullptr; stock.park_b = nullptr; }
+        else {
         __shared__ __attribute__((aligned(16))) float4 s_park_a[BLOCK_THREADS];
         __shared__ __attribute__((aligned(16))) float2 s_park_b[BLOCK_THREADS];
-        stock.e = s_ring + 4u * (threadIdx.x & ~63u); stock.park_a = s_park_a + (threadIdx.x & ~63u); stock.park_b = s_park_b + (threadIdx.x & ~63u);
+        stock.park_a = s_park_a + (threadIdx.x & ~63u); stock.park_b = s_park_b + (threadIdx.x & ~63u);
+        }
     } else {
     __shared__ __attribute__((aligned(16))) float4 s_stock_dir[BLOCK_THREADS];                // RayStock: 64 entries per wave
     __shared__ __attribute__((aligned(16))) uint4 s_stock_key[BLOCK_THREADS];
@@ -613,27 +643,35 @@ DI void render_ctr_lockstep(const RenderParams& P) {
                     if (pix1 - pix0 <= 1u) pmask = cm[pix0] | cm[pix1];
                 }
                 wave_lds_handoff();                        // (camera() writes into slots whose entries other lanes were dealt)
-                stock.park_a[lane] = make_float4(ps.ro.x, ps.ro.y, ps.ro.z, ps.rd.x); stock.park_b[lane] = make_float2(ps.rd.y, ps.rd.z);
+                if constexpr (PARK_IN_RING) { stock.e[4u * lane] = make_float4(ps.ro.x, ps.ro.y, ps.ro.z, ps.rd.x); *reinterpret_cast<float2*>(stock.e + 4u * lane + 1u) = make_float2(ps.rd.y, ps.rd.z); }
+                else { stock.park_a[lane] = make_float4(ps.ro.x, ps.ro.y, ps.ro.z, ps.rd.x); stock.park_b[lane] = make_float2(ps.rd.y, ps.rd.z); }
                 if (lane < n_cam) stock.template camera<RngCtrT<STEP>>(P, wc.next + lane, (wc.ring_head + wc.ring_count + lane) & 63u, ps.ro, ps.rd, /* here = 0: sample indices stay below 2^31 (band_samples) */ wc.next >> 31);
             }
         }
-        if (n_cam != 0u ? lane < n_cam : live) hit = hit_scene<HAS_MESH, true, KINDS, BOUNDED>(prims, P.n_prims, P.nodes, P.tris, ps.ro, ps.rd, h, pmask);     // renderer.rs:24
+        if (n_cam != 0u ? lane < n_cam : live) hit = hit_scene<HAS_MESH, true, KINDS, BOUNDED, RECIP_FIRST>(prims, P.n_prims, P.nodes, P.tris, ps.ro, ps.rd, h, pmask);     // renderer.rs:24
         prof.mark(1);
         if constexpr (PREHIT) {
             if (n_cam != 0u) {                             // finish or stock the camera paths, take the parked rays back, and walk them next
                 const bool cam = lane < n_cam;
                 if (cam) { ++n_paths; ++n_rays; }
                 wave_lds_handoff();                        // camera() wrote the keys, append() reads them from other lanes ...
-                wc.ring_count += stock.append(P, lane, wc.next, wc.ring_head + wc.ring_count, cam, hit, h, ps.rd);
+                if constexpr (PARK_IN_RING) {              // ... and writes its entries over the parked rays: every lane takes its own back first
+                    const float4 a = stock.e[4u * lane]; const float2 b = *reinterpret_cast<const float2*>(stock.e + 4u * lane + 1u);
+                    ps.ro = mk(a.x, a.y, a.z); ps.rd = mk(a.w, b.x, b.y);
+                    wave_lds_handoff();
+                }
+                wc.ring_count += stock.template append<NOSKY>(P, lane, wc.next, wc.ring_head + wc.ring_count, cam, hit, h, ps.rd);
                 wave_lds_handoff();                        // ... and deal_ring() hands the entries it wrote to whichever lanes are idle
                 wc.next += n_cam;
+                if constexpr (!PARK_IN_RING) {
                 const float4 a = stock.park_a[lane]; const float2 b = stock.park_b[lane];
                 ps.ro = mk(a.x, a.y, a.z); ps.rd = mk(a.w, b.x, b.y);
+                }
                 prof.mark(2);
                 continue;
             }
         }
-        if (!shade_and_regenerate<MATS, false, true, true, !HAS_MESH, /* FASTN */ true, /* TRY1 */ SIMPLE ? 1 : 0>(P, wc, lane, live, true, hit, h, ps, n_paths, n_rays, prof, stock)) break;
+        if (!shade_and_regenerate<MATS, false, true, true, !HAS_MESH, /* FASTN */ true, /* TRY1 */ SIMPLE ? 1 : 0, /* REKEY */ false, NOSKY>(P, wc, lane, live, true, hit, h, ps, n_paths, n_rays, prof, stock)) break;
         prof.mark(4);
 #ifdef MI355RT_STAMPS
         if (wc.exhausted()) {                              // all work dealt: from here on the wave only drains its own paths
@@ -661,7 +699,8 @@ DI void render_ctr_lockstep(const RenderParams& P) {
 // Entry points: one body, instantiated per scene class so that each gets its own register budget.
 //   k_render_ctr_nomesh     any materials, no mesh in the list                      (any other mesh-free list)                        6 waves/SIMD
 //   k_render_ctr_simple     Lambertian/Emissive/Null only, no mesh                  (-3 % vs nomesh on cornell)                       7 waves/SIMD
-//   k_render_ctr_simple_qc  the same for lists of quads and cubes only              (cornell: another -1.1 %)                         7 waves/SIMD
+//   k_render_ctr_simple_qc  the same for lists of quads and cubes only, no sky      (cornell: another -1.1 %; without the sky lookup) 8 waves/SIMD
+//   k_render_sky_simple_qc  its twin for scenes with a sky texture                  (the body with the lookup)                        7 waves/SIMD
 //   k_render_ctr_nospec     no metal, no dielectric, no mesh                        (-2.5 % vs nomesh on veach-mis; the probe kernel) 7 waves/SIMD
 //   k_render_ctr_mesh       lockstep with the per-lane BVH walk inlined             (diagnostic knob; the two degenerate renders: an empty list, max_depth 0)
 // Which kernels keep the generator's draw address in LCG-stepped form (rt_rng.h, RngCtrT<true>): one bit per kernel.  The form saves the generator's
@@ -679,7 +718,10 @@ __global__ void __launch_bounds__(BLOCK_THREADS) MI355RT_OCC_LS k_render_ctr_nom
 __global__ void __launch_bounds__(BLOCK_THREADS) MI355RT_OCC_SIMPLE k_render_ctr_simple(const RenderParams P) { render_ctr_lockstep<false, MATS_LAMBERT, PRIMS_ALL, false, false, step_form(STEP_SIMPLE)>(P); }
 // ... and the Lambert-only kernel for lists of quads and cubes (round 5: cornell -1.1 %, profiles/r05/ab_scalar_diet.txt r05_q16), with its camera rays'
 // first hits in stock (HitStock: cornell -3.7 %, profiles/ab_stocked_first_hits.txt)
-__global__ void __launch_bounds__(BLOCK_THREADS) MI355RT_OCC_SIMPLE k_render_ctr_simple_qc(const RenderParams P) { render_ctr_lockstep<false, MATS_LAMBERT, PRIMS_QUAD_CUBE, /* PREHIT */ true, /* BOUNDED */ true, step_form(STEP_SIMPLE_QC)>(P); }
+// Variant 14 has two entry points.  k_render_ctr_simple_qc is compiled WITHOUT the sky lookup and serves the scenes without a sky texture (cornell);
+// k_render_sky_simple_qc is the body with the lookup, for the scenes that carry one.  launch_render_ctr picks by RenderParams.sky.
+__global__ void __launch_bounds__(BLOCK_THREADS) MI355RT_OCC_NOSKY k_render_ctr_simple_qc(const RenderParams P) { render_ctr_lockstep<false, MATS_LAMBERT, PRIMS_QUAD_CUBE, /* PREHIT */ true, /* BOUNDED */ true, step_form(STEP_SIMPLE_QC), /* NOSKY */ true>(P); }
+__global__ void __launch_bounds__(BLOCK_THREADS) MI355RT_OCC_SIMPLE k_render_sky_simple_qc(const RenderParams P) { render_ctr_lockstep<false, MATS_LAMBERT, PRIMS_QUAD_CUBE, /* PREHIT */ true, /* BOUNDED */ true, step_form(STEP_SIMPLE_QC)>(P); }
 __global__ void __launch_bounds__(BLOCK_THREADS) MI355RT_OCC_SIMPLE k_render_ctr_nospec(const RenderParams P) { render_ctr_lockstep<false, MATS_NO_SPECULAR, PRIMS_ALL, false, false, step_form(STEP_NOSPEC)>(P); }
 __global__ void __launch_bounds__(BLOCK_THREADS) __attribute__((amdgpu_waves_per_eu(6, 6))) k_render_ctr_mesh(const RenderParams P) { render_ctr_lockstep<true, MATS_ALL, PRIMS_ALL, false, false, step_form(STEP_MESH)>(P); }
 
@@ -898,10 +940,15 @@ static const void* const render_ctr_kernel[KERNEL_VARIANTS] = {
 #undef KFN
 #undef REFS_KFN
 bool render_ctr_variant_built(uint32_t variant) { return variant < KERNEL_VARIANTS && render_ctr_kernel[variant]; }
+// The entry point of `variant` for a scene with (ENTRY_SKY) or without (ENTRY_PLAIN) a sky texture: one kernel for both everywhere but at variant 14.
+static const void* render_ctr_entry(uint32_t variant, uint32_t entry) {
+    return variant_entry(variant, entry == ENTRY_SKY) == ENTRY_SKY ? reinterpret_cast<const void*>(k_render_sky_simple_qc) : render_ctr_kernel[variant];
+}
 int launch_render_ctr(const RenderParams& p, uint32_t variant, uint32_t grid_blocks, void* stream) {
     if (!render_ctr_variant_built(variant)) return -1;
     void* args[] = {const_cast<RenderParams*>(&p)};
-    (void)hipLaunchKernel(render_ctr_kernel[variant], dim3(grid_blocks), dim3(VARIANT_TABLE[variant].block_threads), args, 0, (hipStream_t)stream);
+    // (by the pointer the kernel would read: the entry compiled without the lookup never sees a texture)
+    (void)hipLaunchKernel(render_ctr_entry(variant, p.sky ? ENTRY_SKY : ENTRY_PLAIN), dim3(grid_blocks), dim3(VARIANT_TABLE[variant].block_threads), args, 0, (hipStream_t)stream);
     return (int)hipGetLastError();
 }
 int launch_resolve(const ResolveParams& p, void* stream) {
@@ -925,9 +972,9 @@ int launch_render_ref(const RefParams& p, void* stream) {
     hipLaunchKernelGGL(k_render_ref, dim3(p.n_rows), dim3(64), 0, (hipStream_t)stream, p);      // one wave per row
     return (int)hipGetLastError();
 }
-int query_render_ctr_occupancy(uint32_t variant, int* blocks_per_cu, int* vgprs, int* sgprs) {
+int query_render_ctr_occupancy(uint32_t variant, uint32_t entry, int* blocks_per_cu, int* vgprs, int* sgprs) {
     if (!render_ctr_variant_built(variant)) return -1;
-    const void* fn = render_ctr_kernel[variant];
+    const void* fn = render_ctr_entry(variant, entry);
     int nb = 0;
     hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, (int)VARIANT_TABLE[variant].block_threads, 0);
     if (e != hipSuccess) return (int)e;

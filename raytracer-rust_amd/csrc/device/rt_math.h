@@ -100,13 +100,15 @@ DI void keep_computed(float& v) { asm volatile("" : "+v"(v)); }
 // NaN components are ignored by the test and give NaN either way.  (The ballot covers the lanes that are active at the call.)
 // BOUNDED (k_render_ctr_simple_qc's cube test): for callers that know every magnitude to be below 2^126 or NaN.  What is then left outside the short
 // form's range is a denormal, and one v_cmp_class_f32 per component finds it.  A wave with a denormal lane takes the compiler's reciprocals, which the
-// compiler lays out of line: the common path falls through the test into the short form.  (With keep_computed() on the three short results, so that they
-// run first and are overwritten, the kernel had 13 SGPR spills instead of 6: not taken.)
-template <bool FASTR, bool BOUNDED = false>
+// compiler lays out of line: the common path falls through the test into the short form.
+// FIRST (the kernel compiled without the sky lookup): keep_computed() on the three short results, so that they run first, in front of the test, and a
+// wave with a denormal overwrites them.  With the sky lookup's scalar registers in the loop this form had 13 SGPR spills instead of 6; without them none.
+template <bool FASTR, bool BOUNDED = false, bool FIRST = false>
 DI void recip3(float x, float y, float z, float& ix, float& iy, float& iz) {
     if constexpr (FASTR && BOUNDED) {
         constexpr int DENORMAL = 0x010 | 0x080;                                             // v_cmp_class_f32: negative denormal, positive denormal
         ix = recip_normal_range(x); iy = recip_normal_range(y); iz = recip_normal_range(z);
+        if constexpr (FIRST) { keep_computed(ix); keep_computed(iy); keep_computed(iz); }
         // (__builtin_isfpclass, not __builtin_amdgcn_class: this compiler folds the latter's denormal classes to `false`; both select v_cmp_class_f32)
         const bool small = __builtin_isfpclass(x, DENORMAL) | __builtin_isfpclass(y, DENORMAL) | __builtin_isfpclass(z, DENORMAL);
         if (__builtin_expect(__ballot(small) != 0ull, 0)) { ix = 1.0f / x; iy = 1.0f / y; iz = 1.0f / z; }

@@ -281,6 +281,18 @@ def prepare_scene(scene, forced_variant=-1, library=None):
     return Prepared(variant.value, inline_steps.value, prims, nodes, tris)
 
 
+def entry_kernel(variant, has_sky, library=None):
+    """Diagnostic (mi355rt_debug_entry_kernel): the name of the kernel a scene on `variant` is launched on, with or without a sky texture.  One
+    kernel per variant, except 14: k_render_ctr_simple_qc is compiled without the sky lookup, scenes with a texture run k_render_sky_simple_qc.
+    No GPU and no context are needed."""
+    L = library or lib()
+    f = L.mi355rt_debug_entry_kernel
+    f.restype = C.c_char_p
+    f.argtypes = [C.c_uint32, C.c_int]
+    name = f(int(variant), 1 if has_sky else 0)
+    return None if name is None else name.decode()
+
+
 def camera_masks(scene, camera, settings, options=None, forced_variant=-1, library=None):
     """Diagnostic (mi355rt_debug_camera_masks): the per-pixel primitive masks set_scene builds for the camera pass of k_render_ctr_simple_qc -- bit i
     of a pixel's word set = a camera ray of that pixel may hit primitive i.  No GPU and no context are needed.  Without options: uint32
@@ -594,6 +606,17 @@ class Context:
         v = C.c_uint32()
         _check(self._L.mi355rt_debug_kernel_variant(self._h, C.byref(v)), "mi355rt_debug_kernel_variant", self._L)
         return v.value
+
+    def kernel_entry(self):
+        """Diagnostic: (kernel name, workgroups per CU, VGPRs) of the entry point the resident scene is launched on (see entry_kernel)."""
+        f = self._L.mi355rt_debug_kernel_entry
+        f.restype = C.c_char_p
+        f.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        blocks, vgprs = C.c_uint32(), C.c_uint32()
+        name = f(self._h, C.byref(blocks), C.byref(vgprs))
+        if name is None:
+            raise RuntimeError("mi355rt_debug_kernel_entry: the context has no scene")
+        return name.decode(), blocks.value, vgprs.value
 
     def row_tables(self):
         """Diagnostic: (natural, processing, out_row) row tables of the last render on this context and the per-image-row cost (rays per path

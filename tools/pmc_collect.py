@@ -43,7 +43,8 @@ def summarize(root):
     for f in glob.glob(os.path.join(root, "**", "*counter_collection.csv"), recursive=True):
         for row in csv.DictReader(open(f)):
             k = row.get("Kernel_Name", "")
-            fam = "k_render_ctr" if "k_render_ctr" in k else "k_resolve" if "k_resolve" in k else None
+            # (k_render_sky_simple_qc: variant 14's entry point for scenes with a sky texture, named outside the k_render_ctr pattern)
+            fam = "k_render_ctr" if "k_render_ctr" in k or "k_render_sky" in k else "k_resolve" if "k_resolve" in k else None
             if fam is None:
                 continue
             names[fam] = k.split("(")[0].split("::")[-1]

@@ -7,7 +7,7 @@ acc = defaultdict(lambda: defaultdict(list))
 for f in glob.glob(os.path.join(root, "**", "*counter_collection.csv"), recursive=True):
     for row in csv.DictReader(open(f)):
         k = row.get("Kernel_Name", "")
-        short = "k_render_ctr" if "k_render_ctr" in k else "k_resolve" if "k_resolve" in k else "k_render_ref" if "k_render_ref" in k else None
+        short = "k_render_ctr" if "k_render_ctr" in k or "k_render_sky" in k else "k_resolve" if "k_resolve" in k else "k_render_ref" if "k_render_ref" in k else None
         if short is None:
             continue
         acc[short][row["Counter_Name"]].append(float(row["Counter_Value"]))
