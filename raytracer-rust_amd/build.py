@@ -130,6 +130,15 @@ def build_device_variant(name, defines=(), force=False, verbose=False, flags=())
     return so
 
 
+# k_render_ctr_simple_qc as it was before it carried its path state in place (rt_kernels.hip, MI355RT_QC_*): every step's define at 0.  The tests render
+# with both libraries and compare bit for bit (tests/test_gpu_state_in_place.py); never loaded by the product path.
+QC_FORM0_DEFINES = ["MI355RT_QC_HIT_IN_PLACE=0", "MI355RT_QC_STATE_IN_PLACE=0", "MI355RT_QC_TERM_SELECT=0"]
+
+
+def build_qc_form0(force=False, verbose=False):
+    return build_device_variant("qc_form0", QC_FORM0_DEFINES, force=force, verbose=verbose)
+
+
 def build_host(force=False, verbose=False):
     os.makedirs(OUT, exist_ok=True)
     srcs = _host_srcs()

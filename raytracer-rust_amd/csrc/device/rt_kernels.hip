@@ -253,6 +253,22 @@ struct RayStock {
 // An entry is 64 bytes (four ds_read_b128): {h.p, sample index}, {h.n, mat_ff}, q0, the generator key at ray 0 (pcg4d: its four words; Philox: the
 // key, x and s -- the ray word is 0; the words are the generator's own, stored and reloaded untouched).  The parking area holds ro and rd of the 64 lanes (24 bytes each) during a refill pass;
 // the kernel compiled without the sky lookup has none and parks them in bytes 0-23 of the (then empty) ring's slots instead: render_ctr_lockstep, PARK_IN_RING.
+// The forms of k_render_ctr_simple_qc that carry a path's state in place (FORM, a template argument of render_ctr_lockstep, shade_and_regenerate and
+// HitStock::append; 0 everywhere else, which folds to the code as it was).  Each bit has a build define, MI355RT_QC_*, whose 0 builds the form before it.
+//   FORM_HIT_IN_PLACE    a dealt lane reads its ring entry into the Hit it scatters: the one the walk wrote for the continuing lanes (no `hs = h`).
+//   FORM_STATE_IN_PLACE  the bounce writes the next origin and throughput over the old ones as soon as the hit is known, for all lanes and outside
+//                        any lane mask, so that the hit point and the albedo are dead before the generator runs and nothing is copied at the loop's bottom.
+//   FORM_TERM_SELECT     the terminal classification selects `term` by the comparison results: no defaults, no nested regions, one store region.
+//                        The shortest listing of all and slower on the GPU (+0.06 ms per step on cornell): its define stays at 0.
+// The first two ship together: cornell -1.35 % (DESIGN.md 4.1 "Path state carried in place", profiles/bench_state_in_place_vs_parent.txt).
+enum : uint32_t { FORM_HIT_IN_PLACE = 1u, FORM_STATE_IN_PLACE = 2u, FORM_TERM_SELECT = 4u };
+// A path's terminal radiance by selects (FORM_TERM_SELECT): the miss colour where nothing was hit, the emitter's colour, 0 for a Null material;
+// returns whether the path ends here.  `q0` is read only where `hit` says it was written.
+DI bool terminal_select(const RenderParams& P, bool hit, const float4& q0, f3& term) {
+    const bool emis = hit && __float_as_uint(q0.x) == MI355RT_MAT_EMISSIVE;
+    term = mk(hit ? (emis ? q0.y : 0.f) : P.miss[0], hit ? (emis ? q0.z : 0.f) : P.miss[1], hit ? (emis ? q0.w : 0.f) : P.miss[2]);
+    return !hit || emis || __float_as_uint(q0.x) == MI355RT_MAT_NULL;
+}
 struct HitStock {
     float4* e;                                                 // [64][4] this wave's ring of entries
     float4* park_a; float2* park_b;                            // [64] each: {ro, rd.x}, {rd.y, rd.z}; lane i writes and reads back element i only: no hand-off (null with PARK_IN_RING)
@@ -278,10 +294,15 @@ struct HitStock {
     // After the walk (lanes with cam == true walked sample first + lane from `tail` + lane): finish the paths that end at their camera ray, exactly as
     // shade_and_regenerate classifies a path at ray 0 (throughput 1), and append the others to the ring in sample order.  Returns how many were appended.
     // NOSKY: see shade_and_regenerate; `rd` is then not read.
-    template <bool NOSKY = false>
+    template <bool NOSKY = false, uint32_t FORM = 0u>
     DI uint32_t append(const RenderParams& P, uint32_t lane, uint32_t first, uint32_t tail, bool cam, bool hit, const Hit& h, f3 rd) const {
         struct Rad { float x, y, z; };
         bool keep = false;
+        if constexpr (NOSKY && (FORM & FORM_TERM_SELECT) != 0u) {
+            f3 term; const bool fin = terminal_select(P, hit, h.q0, term);
+            if (cam && fin) { const f3 L = mk(1.f, 1.f, 1.f) * term; reinterpret_cast<Rad*>(P.radiance)[first + lane] = Rad{L.x, L.y, L.z}; }
+            keep = cam && !fin;
+        } else
         if (cam) {
             f3 term = mk(0.f, 0.f, 0.f); bool fin = false;
             if (!hit) { if constexpr (NOSKY) term = mk(P.miss[0], P.miss[1], P.miss[2]); else term = miss_colour(P.sky, P.sky_w, P.sky_h, P.miss, rd); fin = true; }      // renderer.rs:38-63
@@ -408,18 +429,26 @@ DI f3 unit_ball_cooperative(bool diffuse, const RNG& rng, uint32_t lane, const u
 // NOSKY: this instantiation is never launched with a sky texture (launch_render_ctr sees to it): a miss returns P.miss, three scalar registers.  Compiled in,
 // the lookup of miss_colour() sits in the loop whether or not a scene has a sky -- its polynomial constants in vector registers across the whole
 // iteration, and `sky == nullptr ? &P.miss : texel` as a pointer select with a per-lane load from the kernel-argument segment behind every miss.
-template <uint32_t MATS, bool DEFAULTS = true, bool WIDE = !DEFAULTS, bool DROP_PRIO = false, bool Q0_IN_HIT = false, bool FASTN = false, int TRY1 = 0, bool REKEY = false, bool NOSKY = false, class WC, class PS, class STOCK = NoStock>
-DI bool shade_and_regenerate(const RenderParams& P, WC& wc, uint32_t lane, bool& live, bool can_take, bool hit, const Hit& h,
+// FORM: see FORM_HIT_IN_PLACE (HitStock; k_render_ctr_simple_qc only).  `h` is written only there: by the lanes that are dealt a ring entry.
+template <uint32_t MATS, bool DEFAULTS = true, bool WIDE = !DEFAULTS, bool DROP_PRIO = false, bool Q0_IN_HIT = false, bool FASTN = false, int TRY1 = 0, bool REKEY = false, bool NOSKY = false, uint32_t FORM = 0u, class WC, class PS, class STOCK = NoStock>
+DI bool shade_and_regenerate(const RenderParams& P, WC& wc, uint32_t lane, bool& live, bool can_take, bool hit, Hit& h,
                              PS& ps, uint32_t& n_paths, uint32_t& n_rays, Prof& prof, const STOCK& stock = STOCK()) {
     typedef typename PS::Rng Rng;                                                            // RngCtrT<STEP>: the kernel's form of the draw address
     constexpr bool STOCKED = std::is_same<STOCK, RayStock>::value;                           // camera rays come out of the wave's stock (lockstep kernels)
     constexpr bool PREHIT = std::is_same<STOCK, HitStock>::value;                            // ... or their first hits (k_render_ctr_simple_qc)
+    constexpr bool HIT_IN_PLACE = (FORM & FORM_HIT_IN_PLACE) != 0u, STATE_IN_PLACE = (FORM & FORM_STATE_IN_PLACE) != 0u, TERM_SELECT = (FORM & FORM_TERM_SELECT) != 0u;
     static_assert(!(STOCKED || PREHIT) || (!DEFAULTS && !REKEY), "the stock serves the lockstep form");
     static_assert(!PREHIT || (MATS & ~MATS_LAMBERT) == 0u, "an entry holds no incoming direction: the Lambert bounce does not read it");
+    static_assert(FORM == 0u || (PREHIT && Q0_IN_HIT && NOSKY && TRY1 == 1), "the in-place forms belong to k_render_ctr_simple_qc");
     struct Rad { float x, y, z; };                                                        // 12 bytes per path: global_store_dwordx3
     Rad* __restrict__ radiance = reinterpret_cast<Rad*>(P.radiance);
     float4 q0;                                                                            // first 16 bytes of the hit material; read by lanes that loaded it
     if (DEFAULTS) q0 = make_float4(0.f, 0.f, 0.f, 0.f);
+    if constexpr (TERM_SELECT) {
+        f3 term; const bool fin = terminal_select(P, hit, h.q0, term);
+        q0 = h.q0;
+        if (live && fin) { const f3 L = ps.thr * term; radiance[ps.sidx] = Rad{L.x, L.y, L.z}; live = false; }
+    } else
     if (live) {
         f3 term = mk(0.f, 0.f, 0.f); bool fin = false;
         if (!hit) { if constexpr (NOSKY) term = mk(P.miss[0], P.miss[1], P.miss[2]); else term = miss_colour(P.sky, P.sky_w, P.sky_h, P.miss, ps.rd); fin = true; }   // renderer.rs:38-63
@@ -437,13 +466,14 @@ DI bool shade_and_regenerate(const RenderParams& P, WC& wc, uint32_t lane, bool&
     f3 stocked_raw = mk(0.f, 0.f, 1.f);
     Hit hs;                                                                                // PREHIT: the hit a lane scatters (a dealt lane's comes from the ring)
     if constexpr (PREHIT) {
-        hs = h;
+        if constexpr (!HIT_IN_PLACE) hs = h;                                               // (in place: a dealt lane's h is dead, its ring entry goes there)
         uint32_t slot;
         if (wc.deal_ring(can_take && !live, slot)) {                                       // a continuing path at ray 0 from here on
             const float4* e = stock.e + 4u * slot;
             const float4 e0 = e[0], e1 = e[1], e2 = e[2], e3 = e[3];
-            hs.p = mk(e0.x, e0.y, e0.z); ps.sidx = __float_as_uint(e0.w);
-            hs.n = mk(e1.x, e1.y, e1.z); hs.mat_ff = __float_as_uint(e1.w);
+            Hit& hd = HIT_IN_PLACE ? h : hs;
+            hd.p = mk(e0.x, e0.y, e0.z); ps.sidx = __float_as_uint(e0.w);
+            hd.n = mk(e1.x, e1.y, e1.z); hd.mat_ff = __float_as_uint(e1.w);
             q0 = e2;
             ps.rng.w[0] = __float_as_uint(e3.x); ps.rng.w[1] = __float_as_uint(e3.y); ps.rng.w[2] = __float_as_uint(e3.z); ps.rng.w[3] = __float_as_uint(e3.w);
             if constexpr (Rng::NW == 5) ps.rng.w[4] = 0u;                                  // (Philox: the ray word)
@@ -456,9 +486,39 @@ DI bool shade_and_regenerate(const RenderParams& P, WC& wc, uint32_t lane, bool&
     } else
     if (wc.deal(P, can_take && !live, lane, ps.sidx)) { if constexpr (!REKEY) start_path(P, ps.sidx, ps.rng, ps.px, ps.py); fresh = true; live = true; ++n_paths; }
     if constexpr (DROP_PRIO) __builtin_amdgcn_s_setprio(0);                               // the lockstep kernels' arithmetic half (see render_ctr_lockstep)
+    if constexpr (STATE_IN_PLACE) {
+        // No lane is live behind the deal only when the ring was empty, and the loop comes here with an empty ring only when refill_size() found no
+        // work left to claim (it refills whenever the ring is empty: MI355RT_PREHIT_LOW == 1).  So this is the end of the wave, not a third way back
+        // to the loop's head with the state as it was -- the edge that kept the next state out of the registers of the old one.
+        static_assert(MI355RT_PREHIT_LOW == 1, "an empty ring behind the deal means that no work is left");
+        if (__ballot(live) == 0ull) return false;
+    } else
     if (__ballot(live) == 0ull) return !wc.exhausted();
     uint32_t ball_use = BALL_NONE; bool scattered = false;
     f3 raw, atten, emitted; float side, fuzz = 0.f;  // written by the branch a lane takes below, read only on that lane's own path
+    if constexpr (STATE_IN_PLACE) {
+        // k_render_ctr_simple_qc: every live lane carries a hit on a Lambert surface (the terminal kinds are finished, a dealt lane is a continuing path
+        // at ray 0), so the bounce is one straight line and its state is written IN PLACE: the next throughput thr * albedo (material.rs:47-71) and the next
+        // origin p + n * EPS over the old ones, by all lanes and outside any lane mask (an idle lane's state may hold anything), before the generator runs.
+        // The hit point, the albedo and the old state are dead from there on; only the normal lives on to the new direction.  The same operations on the
+        // same operands as the form before it (scatter_pre / ball_finish / scatter_origin with MATS_LAMBERT), in another order.
+        ps.thr = ps.thr * mk(q0.y, q0.z, q0.w);
+        ps.ro = scatter_origin(PREHIT && !HIT_IN_PLACE ? hs : h, EPS);
+        ++ps.ray_index;
+        ps.rng.next_event();
+        ps.rng.template load_block0<WIDE>();
+        uint32_t blk1[4]; Rng::template block<WIDE>(ps.rng.w, 1u, blk1);
+        ps.rng.begin_scatter();
+        prof.mark(5);
+        prof.classes(live, false, __float_as_uint(q0.x));
+        const f3 ball = unit_ball_cooperative<WIDE, TRY1>(live, ps.rng, lane, blk1);          // whole wave, uniform control flow
+        if (live && ps.ray_index == P.max_depth) {                                            // next level has depth == 0 (renderer.rs:20-22)
+            const f3 L = ps.thr * mk(0.f, 0.f, 0.f);
+            radiance[ps.sidx] = Rad{L.x, L.y, L.z}; live = false;
+        }
+        ps.rd = ray_direction<FASTN>(diffuse_finish<FASTN>(PREHIT && !HIT_IN_PLACE ? hs : h, ball));
+        if (live) ++n_rays;
+    } else
     if constexpr (DEFAULTS) {
         raw = mk(0.f, 0.f, 1.f); atten = mk(0.f, 0.f, 0.f); emitted = mk(0.f, 0.f, 0.f); side = EPS;
         if (live) {
@@ -517,16 +577,16 @@ DI bool shade_and_regenerate(const RenderParams& P, WC& wc, uint32_t lane, bool&
                 n_thr = mk(1.f, 1.f, 1.f); n_ri = 0;
                 if (P.max_depth == 0u) { radiance[ps.sidx] = Rad{0.f, 0.f, 0.f}; live = false; }   // depth == 0 -> BLACK
             } else {
-                scattered = scatter_pre<MATS, WIDE, FASTN, /* TERMINAL_DONE */ true>(P.mats, P.textures, q0, PREHIT ? hs : h, ps.rd, ps.rng, side, raw, atten, emitted, ball_use, fuzz);
+                scattered = scatter_pre<MATS, WIDE, FASTN, /* TERMINAL_DONE */ true>(P.mats, P.textures, q0, PREHIT && !HIT_IN_PLACE ? hs : h, ps.rd, ps.rng, side, raw, atten, emitted, ball_use, fuzz);
             }
         }
         prof.mark(5);
         prof.classes(live && !fresh, live && fresh, __float_as_uint(q0.x));
         const f3 ball = unit_ball_cooperative<WIDE, TRY1>(scattered && ball_use != BALL_NONE, ps.rng, lane, blk1);   // whole wave, uniform control flow
         if (live && !fresh) {
-            if (scattered) scattered = ball_finish<FASTN>(ball_use, PREHIT ? hs : h, ball, fuzz, raw);     // (a fuzzed metal reflection may still be absorbed)
+            if (scattered) scattered = ball_finish<FASTN>(ball_use, PREHIT && !HIT_IN_PLACE ? hs : h, ball, fuzz, raw);     // (a fuzzed metal reflection may still be absorbed)
             if (scattered) {
-                n_thr = ps.thr * atten; n_ro = scatter_origin(PREHIT ? hs : h, side); n_ri = ps.ray_index + 1u;
+                n_thr = ps.thr * atten; n_ro = scatter_origin(PREHIT && !HIT_IN_PLACE ? hs : h, side); n_ri = ps.ray_index + 1u;
                 if (n_ri == P.max_depth) {                                                   // next level has depth == 0 (renderer.rs:20-22)
                     const f3 L = n_thr * mk(0.f, 0.f, 0.f);
                     radiance[ps.sidx] = Rad{L.x, L.y, L.z}; live = false;
@@ -564,6 +624,18 @@ DI bool shade_and_regenerate(const RenderParams& P, WC& wc, uint32_t lane, bool&
 #ifndef MI355RT_NOSKY_WAVES
 #define MI355RT_NOSKY_WAVES 8
 #endif
+// ... and carrying a path's state in place (FORM_*, above HitStock; A/B: profiles/bench_state_in_place_vs_parent.txt), step by step in the same way.
+// build.QC_FORM0_DEFINES builds the three at 0 for the tests (tests/test_gpu_state_in_place.py); the third is the one that did not pay.
+#ifndef MI355RT_QC_HIT_IN_PLACE
+#define MI355RT_QC_HIT_IN_PLACE 1
+#endif
+#ifndef MI355RT_QC_STATE_IN_PLACE
+#define MI355RT_QC_STATE_IN_PLACE 1
+#endif
+#ifndef MI355RT_QC_TERM_SELECT
+#define MI355RT_QC_TERM_SELECT 0
+#endif
+#define MI355RT_QC_FORM ((MI355RT_QC_HIT_IN_PLACE != 0 ? FORM_HIT_IN_PLACE : 0u) | (MI355RT_QC_STATE_IN_PLACE != 0 ? FORM_STATE_IN_PLACE : 0u) | (MI355RT_QC_TERM_SELECT != 0 ? FORM_TERM_SELECT : 0u))
 #define MI355RT_OCC_NOSKY __attribute__((amdgpu_waves_per_eu(MI355RT_NOSKY_WAVES, MI355RT_NOSKY_WAVES)))
 #define MI355RT_OCC_SMK __attribute__((amdgpu_waves_per_eu(4, 4)))      // (reference build's state machine)
 
@@ -579,7 +651,7 @@ DI bool shade_and_regenerate(const RenderParams& P, WC& wc, uint32_t lane, bool&
 // STEP: the generator's draw address in LCG-stepped form (rt_rng.h); per kernel, see the entry points below.
 // NOSKY: never launched with a sky texture (shade_and_regenerate); with it the cube's reciprocals run first (recip3) and the refill pass parks the paths'
 // rays inside the ring (below), each behind its build define so that the form before it can still be built for an A/B.
-template <bool HAS_MESH, uint32_t MATS, uint32_t KINDS = PRIMS_ALL, bool PREHIT = false, bool BOUNDED = false, bool STEP = false, bool NOSKY = false>
+template <bool HAS_MESH, uint32_t MATS, uint32_t KINDS = PRIMS_ALL, bool PREHIT = false, bool BOUNDED = false, bool STEP = false, bool NOSKY = false, uint32_t FORM = 0u>
 DI void render_ctr_lockstep(const RenderParams& P) {
     constexpr bool SIMPLE = (MATS & ~MATS_LAMBERT) == 0u;
     constexpr bool RECIP_FIRST = NOSKY && BOUNDED && (MI355RT_NOSKY_RECIP_FIRST != 0);
@@ -660,7 +732,7 @@ DI void render_ctr_lockstep(const RenderParams& P) {
                     ps.ro = mk(a.x, a.y, a.z); ps.rd = mk(a.w, b.x, b.y);
                     wave_lds_handoff();
                 }
-                wc.ring_count += stock.template append<NOSKY>(P, lane, wc.next, wc.ring_head + wc.ring_count, cam, hit, h, ps.rd);
+                wc.ring_count += stock.template append<NOSKY, FORM>(P, lane, wc.next, wc.ring_head + wc.ring_count, cam, hit, h, ps.rd);
                 wave_lds_handoff();                        // ... and deal_ring() hands the entries it wrote to whichever lanes are idle
                 wc.next += n_cam;
                 if constexpr (!PARK_IN_RING) {
@@ -671,7 +743,7 @@ DI void render_ctr_lockstep(const RenderParams& P) {
                 continue;
             }
         }
-        if (!shade_and_regenerate<MATS, false, true, true, !HAS_MESH, /* FASTN */ true, /* TRY1 */ SIMPLE ? 1 : 0, /* REKEY */ false, NOSKY>(P, wc, lane, live, true, hit, h, ps, n_paths, n_rays, prof, stock)) break;
+        if (!shade_and_regenerate<MATS, false, true, true, !HAS_MESH, /* FASTN */ true, /* TRY1 */ SIMPLE ? 1 : 0, /* REKEY */ false, NOSKY, FORM>(P, wc, lane, live, true, hit, h, ps, n_paths, n_rays, prof, stock)) break;
         prof.mark(4);
 #ifdef MI355RT_STAMPS
         if (wc.exhausted()) {                              // all work dealt: from here on the wave only drains its own paths
@@ -720,7 +792,7 @@ __global__ void __launch_bounds__(BLOCK_THREADS) MI355RT_OCC_SIMPLE k_render_ctr
 // first hits in stock (HitStock: cornell -3.7 %, profiles/ab_stocked_first_hits.txt)
 // Variant 14 has two entry points.  k_render_ctr_simple_qc is compiled WITHOUT the sky lookup and serves the scenes without a sky texture (cornell);
 // k_render_sky_simple_qc is the body with the lookup, for the scenes that carry one.  launch_render_ctr picks by RenderParams.sky.
-__global__ void __launch_bounds__(BLOCK_THREADS) MI355RT_OCC_NOSKY k_render_ctr_simple_qc(const RenderParams P) { render_ctr_lockstep<false, MATS_LAMBERT, PRIMS_QUAD_CUBE, /* PREHIT */ true, /* BOUNDED */ true, step_form(STEP_SIMPLE_QC), /* NOSKY */ true>(P); }
+__global__ void __launch_bounds__(BLOCK_THREADS) MI355RT_OCC_NOSKY k_render_ctr_simple_qc(const RenderParams P) { render_ctr_lockstep<false, MATS_LAMBERT, PRIMS_QUAD_CUBE, /* PREHIT */ true, /* BOUNDED */ true, step_form(STEP_SIMPLE_QC), /* NOSKY */ true, MI355RT_QC_FORM>(P); }
 __global__ void __launch_bounds__(BLOCK_THREADS) MI355RT_OCC_SIMPLE k_render_sky_simple_qc(const RenderParams P) { render_ctr_lockstep<false, MATS_LAMBERT, PRIMS_QUAD_CUBE, /* PREHIT */ true, /* BOUNDED */ true, step_form(STEP_SIMPLE_QC)>(P); }
 __global__ void __launch_bounds__(BLOCK_THREADS) MI355RT_OCC_SIMPLE k_render_ctr_nospec(const RenderParams P) { render_ctr_lockstep<false, MATS_NO_SPECULAR, PRIMS_ALL, false, false, step_form(STEP_NOSPEC)>(P); }
 __global__ void __launch_bounds__(BLOCK_THREADS) __attribute__((amdgpu_waves_per_eu(6, 6))) k_render_ctr_mesh(const RenderParams P) { render_ctr_lockstep<true, MATS_ALL, PRIMS_ALL, false, false, step_form(STEP_MESH)>(P); }
