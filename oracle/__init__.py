@@ -76,6 +76,8 @@ def lib():
         L.oracle_scatter_ctr.argtypes = [C.POINTER(abi.Material), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                          C.c_void_p]
+        L.oracle_scatter_ctr_batch.restype = C.c_int
+        L.oracle_scatter_ctr_batch.argtypes = [C.POINTER(abi.Material), C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]
         L.oracle_sort_paths.restype = None
         L.oracle_sort_paths.argtypes = [C.POINTER(C.c_uint64), C.c_int]
         L.oracle_debug_stages.restype = C.c_int
@@ -182,6 +184,18 @@ def scene_hit(scene, origin, direction):
     if rc < 0:
         raise RuntimeError(f"oracle_scene_hit failed: {rc}")
     return (rc == 1), out
+
+
+def scatter_ctr_batch(materials, records):
+    """oracle_scatter_ctr_batch: one Material::scatter in counter mode per record.  materials: ctypes array of abi.Material; records: uint32
+    [n, 16] (material, flags bit 0 = front face, direction, position, normal as float bits, k0, k1, x, s, ray).  Returns uint32 [n, 16]: the
+    float bits of did_scatter, origin, direction, attenuation, emitted, then the number of generator words drawn, then two zero words."""
+    rec = np.ascontiguousarray(records, np.uint32).reshape(-1, 16)
+    out = np.zeros((rec.shape[0], 16), np.uint32)
+    rc = lib().oracle_scatter_ctr_batch(materials, len(materials), rec.ctypes.data, rec.shape[0], out.ctypes.data)
+    if rc != 0:
+        raise RuntimeError(f"oracle_scatter_ctr_batch failed: {rc}")
+    return out
 
 
 SORT_PATHS = ("calls", "insertion_only", "run_ascending", "run_descending", "quicksort", "small_no_merge", "sort9", "sort13", "merge", "merge_odd",

@@ -1240,6 +1240,34 @@ int oracle_scatter_ctr(const mi355rt_material* m, const float* ray_o, const floa
     return MI355RT_OK;
 }
 
+// oracle_scatter_ctr over n records at once (tests/scatter_wave_cases.py: the per-call overhead of ctypes shows at 10^5 records).
+// records: 16 words each -- material index, flags (bit 0: front face), ray direction[3], position[3], normal[3], k0, k1, x, s, ray.
+// out: 16 words each -- did_scatter, origin[3], direction[3], attenuation[3] (+0 unless scattered), Material::emitted[3], and as an integer the
+// generator words the event drew (SamplerCtr::words_drawn: 3 per rejection try, 1 per random::<f32>()), then two words of +0.
+int oracle_scatter_ctr_batch(const mi355rt_material* mats, uint32_t n_mats, const uint32_t* records, uint32_t n, uint32_t* out) {
+    if (!mats || !records || !out) return MI355RT_ERR_INVALID;
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint32_t* r = records + 16 * (size_t)i;
+        if (r[0] >= n_mats) return MI355RT_ERR_INVALID;
+        float f[9]; std::memcpy(f, r + 2, sizeof f);
+        const mi355rt_material& m = mats[r[0]];
+        Ray rin{v3(0, 0, 0), v3(f[0], f[1], f[2])};
+        HitRecord h; h.position = v3(f[3], f[4], f[5]); h.normal = v3(f[6], f[7], f[8]); h.t = 0; h.material = 0;
+        h.front_face = (r[1] & 1u) != 0;
+        SamplerCtr rng; rng.k0 = r[11]; rng.k1 = r[12]; rng.x = r[13]; rng.s = r[14]; rng.ray = r[15];
+        Ray sc; Col at;
+        const bool ok = scatter(m, rin, h, rng, sc, at);
+        const Col em = emitted(m);
+        float o[16] = {ok ? 1.0f : 0.0f};
+        if (ok) { o[1] = sc.origin.x; o[2] = sc.origin.y; o[3] = sc.origin.z; o[4] = sc.direction.x; o[5] = sc.direction.y; o[6] = sc.direction.z;
+                  o[7] = at.r; o[8] = at.g; o[9] = at.b; }
+        o[10] = em.r; o[11] = em.g; o[12] = em.b;
+        std::memcpy(out + 16 * (size_t)i, o, sizeof o);
+        out[16 * (size_t)i + 13] = (uint32_t)rng.words_drawn;
+    }
+    return MI355RT_OK;
+}
+
 // BVH topology dump of the oracle's own builder, preorder.  Per node: bmin[3], bmax[3] in `bounds`
 // (6 floats), and in `info` (3 u32): is_leaf, n_tris, depth.  Leaf triangle ids are appended to
 // `leaf_ids` in visiting order.  Call with NULL arrays to get the counts.

@@ -46,6 +46,11 @@ DEVICE_DEPS = DEVICE_SRCS + DEVICE_HEADERS + [os.path.join(ROOT, "include", "mi3
 # mi355rt_debug_resolve / mi355rt_debug_gather, the shipped resolve and gather launchers on caller-supplied buffers (tests/test_gpu_resolve_stage.py);
 # mi355rt_debug_rng_block, one generator block through each form of the draw address at a chosen ray and try (tests/test_gpu_rng_stepped.py).
 REFS_SRCS = [os.path.join(CSRC, "refs", "rt_stages.hip"), os.path.join(CSRC, "refs", "rt_resolve_probe.hip"), os.path.join(CSRC, "refs", "rt_rng_probe.hip")]
+# ... and mi355rt_debug_scatter_wave, the bounce's shipped pieces on caller-chosen waves (tests/test_gpu_scatter_wave.py).  The probe has to live
+# in the kernels' translation unit (unit_ball_cooperative is defined there), so the reference build compiles REFS_KERNELS in the place of
+# rt_kernels.hip: that file, included unchanged, and the probe's header behind it.  No file that kernel_hash() covers is touched.
+REFS_KERNELS = os.path.join(CSRC, "refs", "rt_kernels_refs.hip")
+REFS_HEADERS = [os.path.join(CSRC, "refs", "rt_scatter_wave_probe.h")]
 
 
 def _host_srcs():
@@ -121,8 +126,10 @@ def build_device_variant(name, defines=(), force=False, verbose=False, flags=())
     """Diagnostic / A-B builds (e.g. cycle stamps) into their own library; never loaded by the product path."""
     os.makedirs(OUT, exist_ok=True)
     so = os.path.join(OUT, f"libmi355rt_{name}.so")
-    srcs = DEVICE_SRCS + (REFS_SRCS if "MI355RT_REFS" in defines else [])
-    if force or _stale(so, DEVICE_DEPS + srcs):
+    srcs = list(DEVICE_SRCS)
+    if "MI355RT_REFS" in defines:
+        srcs = [REFS_KERNELS if s == DEVICE_SRCS[0] else s for s in DEVICE_SRCS] + REFS_SRCS
+    if force or _stale(so, DEVICE_DEPS + srcs + REFS_HEADERS):
         cmd = [hipcc_path(), *HIPCC_FLAGS, *flags, *[f"-D{d}" for d in defines], "-o", so, *srcs]
         if verbose:
             print(" ".join(cmd))

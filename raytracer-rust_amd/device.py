@@ -37,7 +37,7 @@ def load(so):
 
 def refs():
     """The tests' reference build: the product sources plus the retired mesh kernel (the state machine), mi355rt_debug_stages and the
-    resolve / gather probe (mi355rt_debug_resolve, mi355rt_debug_gather) and the generator probe (mi355rt_debug_rng_block), -DMI355RT_REFS."""
+    resolve / gather probe (mi355rt_debug_resolve, mi355rt_debug_gather) and the generator probe (mi355rt_debug_rng_block) and the wave probe of the bounce (mi355rt_debug_scatter_wave), -DMI355RT_REFS."""
     L = load(build.build_device_variant("refs", ["MI355RT_REFS"]))
     L.mi355rt_debug_stages.restype = C.c_int
     L.mi355rt_debug_stages.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
@@ -47,6 +47,10 @@ def refs():
     L.mi355rt_debug_gather.argtypes = [C.c_void_p]
     L.mi355rt_debug_rng_block.restype = C.c_int
     L.mi355rt_debug_rng_block.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_int]
+    L.mi355rt_debug_scatter_wave.restype = C.c_int
+    L.mi355rt_debug_scatter_wave.argtypes = [C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_int]
+    L.mi355rt_debug_scatter_wave_form.restype = C.c_int
+    L.mi355rt_debug_scatter_wave_form.argtypes = [C.c_uint32, C.c_void_p, C.POINTER(C.c_char_p)]
     return L
 
 
@@ -91,6 +95,58 @@ def debug_rng_block(records, hip_device=0):
     out = np.zeros((rec.shape[0], 3, 4), np.uint32)
     _check(L.mi355rt_debug_rng_block(rec.ctypes.data, rec.shape[0], out.ctypes.data, hip_device), "mi355rt_debug_rng_block", L)
     return out
+
+
+WAVE_LIVE = 0x100            # flags word of a wave-probe record: bit 0 front face, bit 8 live (csrc/refs/rt_scatter_wave_probe.h)
+
+
+def scatter_wave_forms():
+    """Diagnostic (reference build, csrc/refs/rt_scatter_wave_probe.h): the forms of the bounce the library launches, in the probe's order.
+    A list of dicts: kernel (the kernel the form belongs to), mats (bit k: material kind k), wide, fastn, try1, terminal_done, stepped, in_place.
+    Needs no GPU."""
+    L = refs()
+    forms, count, i = [], 1, 0
+    while i < count:
+        w = np.zeros(8, np.uint32)
+        name = C.c_char_p()
+        _check(L.mi355rt_debug_scatter_wave_form(i, w.ctypes.data, C.byref(name)), "mi355rt_debug_scatter_wave_form", L)
+        count = int(w[7])
+        forms.append(dict(kernel=name.value.decode(), mats=int(w[0]), wide=bool(w[1]), fastn=bool(w[2]), try1=int(w[3]), terminal_done=bool(w[4]),
+                          stepped=bool(w[5]), in_place=bool(w[6])))
+        i += 1
+    return forms
+
+
+def debug_scatter_wave(form, materials, records, hip_device=0):
+    """Diagnostic (reference build): one scatter event per lane through the shipped pieces of the bounce -- scatter_pre, unit_ball_cooperative,
+    ball_finish, scatter_origin, ray_direction -- with the template arguments of form `form` (scatter_wave_forms()).  materials: ctypes array
+    of abi.Material; records: uint32 [n, 16] = (material, flags, direction[3], position[3], normal[3] as float bits, k0, k1, x, sample, ray),
+    64 to a wave in the order given; an idle lane (flags without WAVE_LIVE) passes false to the cooperative draw and its generator words are
+    the record's (k0, k1, x, sample).  Returns uint32 [n, 16]: the float bits of scattered, origin[3], direction[3], attenuation[3],
+    emitted[3] and the accepted unit-ball point[3]; what a lane did not produce is +0."""
+    L = refs()
+    rec = np.ascontiguousarray(records, np.uint32).reshape(-1, 16)
+    out = np.zeros((rec.shape[0], 16), np.uint32)
+    _check(L.mi355rt_debug_scatter_wave(int(form), materials, len(materials), rec.ctypes.data, rec.shape[0], out.ctypes.data, hip_device),
+           "mi355rt_debug_scatter_wave", L)
+    return out
+
+
+def debug_scatter_records(materials, records, hip_device=0):
+    """debug_scatter on packed records: uint32 [n, 16] = (material, front face, direction[3], position[3], normal[3] as float bits, k0, k1, x,
+    sample, ray).  Returns uint32 [n, 16]: the float bits of scattered, origin[3], direction[3], attenuation[3], emitted[3], then three zero words."""
+    sc = abi.Scene()
+    sc.materials, sc.n_materials = materials, len(materials)
+    sc.miss_color[:] = (0.5, 0.5, 0.5)
+    rec = np.ascontiguousarray(records, np.uint32).reshape(-1, 16)
+    out = np.zeros((rec.shape[0], 16), np.uint32)
+    ctx = Context(hip_device)
+    try:
+        ctx.set_scene(sc, abi.Camera(), abi.Settings(1, 1, 1, 1))
+        _check(lib().mi355rt_debug_scatter(ctx._h, C.c_void_p(rec.ctypes.data), rec.shape[0], C.c_void_p(out.ctypes.data)), "mi355rt_debug_scatter")
+        return out
+    finally:
+        ctx.close()
 
 
 # mi355rt_debug_stages (csrc/refs/rt_stages.hip; the oracle's twin is oracle_debug_stages): stage numbers and the argument record
