@@ -139,11 +139,22 @@ def build_device_variant(name, defines=(), force=False, verbose=False, flags=())
 
 # k_render_ctr_simple_qc as it was before it carried its path state in place (rt_kernels.hip, MI355RT_QC_*): every step's define at 0.  The tests render
 # with both libraries and compare bit for bit (tests/test_gpu_state_in_place.py); never loaded by the product path.
-QC_FORM0_DEFINES = ["MI355RT_QC_HIT_IN_PLACE=0", "MI355RT_QC_STATE_IN_PLACE=0", "MI355RT_QC_TERM_SELECT=0"]
+# (MI355RT_QC_EMPTY_PASS=0: the camera pass without its empty-pass shortcut, the fourth bit of FORM.)
+QC_FORM0_DEFINES = ["MI355RT_QC_HIT_IN_PLACE=0", "MI355RT_QC_STATE_IN_PLACE=0", "MI355RT_QC_TERM_SELECT=0", "MI355RT_QC_EMPTY_PASS=0"]
 
 
 def build_qc_form0(force=False, verbose=False):
     return build_device_variant("qc_form0", QC_FORM0_DEFINES, force=force, verbose=verbose)
+
+
+# The library that spends its full price on pixels that see nothing (rt_kernels.hip): the camera pass walks a pass whose masks are 0, the resolve reads
+# every sample.  Kernel for kernel the library before the two steps (tests/test_empty_pass_isa.py, profiles/isa_diff_empty_pass_vs_parent.txt); never
+# loaded by the product path.
+EMPTY_PASS_OFF_DEFINES = ["MI355RT_QC_EMPTY_PASS=0", "MI355RT_RESOLVE_SKIP=0"]
+
+
+def build_empty_pass_off(force=False, verbose=False):
+    return build_device_variant("empty_pass_off", EMPTY_PASS_OFF_DEFINES, force=force, verbose=verbose)
 
 
 def build_host(force=False, verbose=False):

@@ -64,6 +64,7 @@ struct mi355rt_context {
     // kernel gets no table.
     std::vector<uint32_t> cam_mask_abs, cam_mask_host; uint32_t cam_mask_w = 0, cam_mask_h = 0;
     int knob_cam_cull = -1;              // diagnostic knob "cam_cull": -1 / 1 on, 0 off (no table: the camera pass tests every primitive)
+    int knob_resolve_skip = 1;           // diagnostic knob "resolve_skip": 1 (the product) = k_resolve gets the band's camera masks and reads no sample of a pixel whose word is 0; 0 = it reads every sample
     bool rows_valid = false;             // ctx->rows already holds the tables of rows_host (same selection and grouping as the last call)
     // Processing order (an experiment of round 4, opt-in).  The persistent kernels hand out a band's samples front to back, and a
     // launch ends with the paths of the rows handed out LAST.  The idea: process the rows in order of DECREASING expected cost -- cheap rows
@@ -211,6 +212,7 @@ int apply_knob(mi355rt_context* ctx, const std::string& name, int v) {
     else if (name == "spin_entry") { if (v < 1) return fail(MI355RT_ERR_INVALID, "knob spin_entry"); ctx->spin_limit_entry = (uint32_t)v; }
     else if (name == "wave_times") ctx->want_wave_times = v != 0;
     else if (name == "cam_cull") { if (v < -1 || v > 1) return fail(MI355RT_ERR_INVALID, "knob cam_cull"); ctx->knob_cam_cull = v; }
+    else if (name == "resolve_skip") { if (v < 0 || v > 1) return fail(MI355RT_ERR_INVALID, "knob resolve_skip"); ctx->knob_resolve_skip = v; }
     else if (name == "denoise_staged") { if (v < 0 || v > 1) return fail(MI355RT_ERR_INVALID, "knob denoise_staged"); ctx->knob_denoise_staged = v; }
     else if (name == "ao_form") { if (v < 0 || v > 1) return fail(MI355RT_ERR_INVALID, "knob ao_form"); ctx->knob_ao_form = v; }
     else if (name == "row_order") { if (v < -1 || v > 1) return fail(MI355RT_ERR_INVALID, "knob row_order"); ctx->knob_row_order = v; }
@@ -225,7 +227,7 @@ extern "C" {
 // Diagnostic hook (not part of the public header).  ctx != NULL: set one knob of that context (before set_scene).  ctx == NULL: a
 // process-wide default applied to every context created afterwards -- also those the one-shot calls create; name == NULL clears
 // all defaults.  Knobs: kernel (KERNEL_* of rt_device.h, -1 = automatic), guided_mult, spin_idle, spin_entry, wave_times, row_order,
-// cam_cull (0: k_render_ctr_simple_qc gets no camera masks), and for the reference build's state machine inline_steps, trav_min.
+// cam_cull (0: k_render_ctr_simple_qc gets no camera masks), resolve_skip (0: k_resolve gets none), and for the reference build's state machine inline_steps, trav_min.
 int mi355rt_debug_set_knob(mi355rt_context* ctx, const char* name, int value) {
     return guard([&]() -> int {
     if (ctx) return name ? apply_knob(ctx, name, value) : fail(MI355RT_ERR_INVALID, "knob name is null");
@@ -492,6 +494,10 @@ static int render_samples(mi355rt_context* ctx, const mi355rt_options* opt, uint
         r.spp = plan.spp; r.inv_spp = plan.inv_spp;
         r.accum = (float*)d_accum; r.accum_load = plan.accum_load;
         r.out_row = d_out_row; r.width = st.width; r.width_mul = plan.width_mul; r.width_shift = plan.width_shift;
+        // The resolve reads no sample of a pixel that no camera ray leaves with a hit: there k_render_ctr_simple_qc stored 1 * miss for every sample (HitStock::append).
+        // Only that entry stores a constant -- the twin with the sky lookup stores a texel -- and the row-cost probe resolves nothing.
+        const bool resolve_skip = p.cam_mask_off != 0u && p.sky == nullptr && !d_row_counters && ctx->knob_resolve_skip != 0;
+        std::memcpy(r.miss, ctx->miss, 12);
         for (uint32_t b = 0; b < plan.n_bands; ++b) {
             const RenderBand band = render_band(plan, b);
             p.band_pixel0 = band.band_pixel0; p.band_samples = band.band_samples; p.shard_samples = band.shard_samples; p.guided_div = band.guided_div;
@@ -506,6 +512,7 @@ static int render_samples(mi355rt_context* ctx, const mi355rt_options* opt, uint
             }
             grid_blocks = std::max(grid_blocks, band.grid);
             r.band_pixel0 = band.band_pixel0; r.band_pixels = band.band_pixels;
+            r.cam_mask = resolve_skip ? p.rows + p.cam_mask_off + band.band_pixel0 : nullptr;   // (the words the render kernel reads for this band)
             hipEvent_t pe0 = nullptr, pe1 = nullptr, pe2 = nullptr;
             if (ctx->timing && !stats) { pe0 = ctx->pool_get(); pe1 = ctx->pool_get(); pe2 = ctx->pool_get(); if (!pe0 || !pe1 || !pe2) return fail(MI355RT_ERR_HIP, "event pool"); }
             if (stats) HIP_TRY(hipEventRecord(ctx->ev[0], stream));

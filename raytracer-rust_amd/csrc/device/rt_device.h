@@ -153,6 +153,10 @@ struct ResolveParams {
     float inv_spp;               // 1 / (samples accumulated so far including this launch)
     const uint32_t* out_row;     // processing row -> local output row (rt_prepare.cpp row_tables()); null: the band's pixels are in output order
     uint32_t width, width_mul, width_shift;   // image width and its magic pair (pixel -> processing row)
+    // (Last: the words above keep their offsets in the kernel argument.)
+    float miss[3];               // with cam_mask: the miss colour; every sample of a pixel whose word is 0 holds 1 * miss (k_render_ctr_simple_qc stored it)
+    const uint32_t* cam_mask;    // the band's camera-mask words in processing order, one per band pixel: RenderParams' rows + cam_mask_off + band_pixel0.
+                                 // A pixel whose word is 0 is resolved without reading its samples.  Null: no table, every sample is read
 };
 
 struct RefParams {               // MI355RT_RNG_REF: one lane per selected row

@@ -261,7 +261,12 @@ struct RayStock {
 //   FORM_TERM_SELECT     the terminal classification selects `term` by the comparison results: no defaults, no nested regions, one store region.
 //                        The shortest listing of all and slower on the GPU (+0.06 ms per step on cornell): its define stays at 0.
 // The first two ship together: cornell -1.35 % (DESIGN.md 4.1 "Path state carried in place", profiles/bench_state_in_place_vs_parent.txt).
-enum : uint32_t { FORM_HIT_IN_PLACE = 1u, FORM_STATE_IN_PLACE = 2u, FORM_TERM_SELECT = 4u };
+//   FORM_EMPTY_PASS      a refill pass whose camera-mask words are all 0 -- no camera ray of its pixels can hit anything -- builds no camera ray and walks
+//                        nothing (render_ctr_lockstep, `walk_cam`).  It still parks the rays and runs append(): no lane walked, so every `hit` is false and
+//                        append() stores 1 * miss for every camera path, as it does for any miss.  A form that gives the empty pass a store or an exit of its
+//                        own moves the loop's scalar allocation (profiles/isa_diff_empty_pass_vs_parent.txt); this one leaves it where it was.
+//                        Cornell -0.85 % (DESIGN.md 4.1 "Nothing for pixels that see nothing", profiles/bench_empty_pass_vs_parent.txt).
+enum : uint32_t { FORM_HIT_IN_PLACE = 1u, FORM_STATE_IN_PLACE = 2u, FORM_TERM_SELECT = 4u, FORM_EMPTY_PASS = 8u };
 // A path's terminal radiance by selects (FORM_TERM_SELECT): the miss colour where nothing was hit, the emitter's colour, 0 for a Null material;
 // returns whether the path ends here.  `q0` is read only where `hit` says it was written.
 DI bool terminal_select(const RenderParams& P, bool hit, const float4& q0, f3& term) {
@@ -635,7 +640,10 @@ DI bool shade_and_regenerate(const RenderParams& P, WC& wc, uint32_t lane, bool&
 #ifndef MI355RT_QC_TERM_SELECT
 #define MI355RT_QC_TERM_SELECT 0
 #endif
-#define MI355RT_QC_FORM ((MI355RT_QC_HIT_IN_PLACE != 0 ? FORM_HIT_IN_PLACE : 0u) | (MI355RT_QC_STATE_IN_PLACE != 0 ? FORM_STATE_IN_PLACE : 0u) | (MI355RT_QC_TERM_SELECT != 0 ? FORM_TERM_SELECT : 0u))
+#ifndef MI355RT_QC_EMPTY_PASS
+#define MI355RT_QC_EMPTY_PASS 1                              // the fourth bit of FORM; 0 (build.QC_FORM0_DEFINES, build.EMPTY_PASS_OFF_DEFINES) builds the camera pass as it was
+#endif
+#define MI355RT_QC_FORM ((MI355RT_QC_HIT_IN_PLACE != 0 ? FORM_HIT_IN_PLACE : 0u) | (MI355RT_QC_STATE_IN_PLACE != 0 ? FORM_STATE_IN_PLACE : 0u) | (MI355RT_QC_TERM_SELECT != 0 ? FORM_TERM_SELECT : 0u) | (MI355RT_QC_EMPTY_PASS != 0 ? FORM_EMPTY_PASS : 0u))
 #define MI355RT_OCC_NOSKY __attribute__((amdgpu_waves_per_eu(MI355RT_NOSKY_WAVES, MI355RT_NOSKY_WAVES)))
 #define MI355RT_OCC_SMK __attribute__((amdgpu_waves_per_eu(4, 4)))      // (reference build's state machine)
 
@@ -660,6 +668,8 @@ DI void render_ctr_lockstep(const RenderParams& P) {
     // without a sky, does not read the camera ray's direction.  16 KB of LDS per workgroup instead of 22: the eighth workgroup of a CU fits.
     constexpr bool PARK_IN_RING = NOSKY && PREHIT && (MI355RT_NOSKY_PARK_IN_RING != 0);
     static_assert(!PARK_IN_RING || MI355RT_PREHIT_LOW == 1, "rays are parked in the ring's slots: a refill must find the ring empty");
+    // An empty refill pass skips camera() and the walk (FORM_EMPTY_PASS, above HitStock).  Only without the sky lookup: there a miss is the constant P.miss.
+    constexpr bool EMPTY_PASS = NOSKY && PREHIT && (FORM & FORM_EMPTY_PASS) != 0u;
     // The mesh-free kernels are compiled for lists that hold something and for paths that may take a step: the host sends an empty list or max_depth == 0 to
     // k_render_ctr_mesh, the plain loop (rt_api.cpp render_samples).  Both are launch constants, and the compiler had turned `n_prims != 0` and `max_depth == 0`
     // into lane masks tested in every iteration (the masks spilled: four v_readlane, two mask operations, two branches): cornell -1.9 %.
@@ -704,6 +714,7 @@ DI void render_ctr_lockstep(const RenderParams& P) {
         __builtin_amdgcn_s_setprio(1);
         uint32_t n_cam = 0u;                               // PREHIT: camera rays walked in this iteration (a refill pass; wave-uniform)
         uint32_t pmask = ~0u;                              // PREHIT: the primitives this walk tests (walk_list); all of them in a bounce iteration
+        bool walk_cam = true;                              // EMPTY_PASS: false in a refill pass whose pixels' camera rays can hit nothing (wave-uniform)
         if constexpr (PREHIT) {
             n_cam = wc.template refill_size<MI355RT_PREHIT_LOW>(P, lane);
             if (n_cam != 0u) {                             // park the paths' rays; lane i takes the camera ray of sample next + i
@@ -712,15 +723,15 @@ DI void render_ctr_lockstep(const RenderParams& P) {
                 if (P.cam_mask_off != 0u) {
                     const uint32_t pix0 = fastdiv(wc.next, P.spp_mul, P.spp_shift), pix1 = fastdiv(wc.next + n_cam - 1u, P.spp_mul, P.spp_shift);
                     const __attribute__((address_space(4))) uint32_t* cm = (const __attribute__((address_space(4))) uint32_t*)(P.rows) + P.cam_mask_off + P.band_pixel0;
-                    if (pix1 - pix0 <= 1u) pmask = cm[pix0] | cm[pix1];
+                    if (pix1 - pix0 <= 1u) { pmask = cm[pix0] | cm[pix1]; if constexpr (EMPTY_PASS) walk_cam = pmask != 0u; }
                 }
                 wave_lds_handoff();                        // (camera() writes into slots whose entries other lanes were dealt)
                 if constexpr (PARK_IN_RING) { stock.e[4u * lane] = make_float4(ps.ro.x, ps.ro.y, ps.ro.z, ps.rd.x); *reinterpret_cast<float2*>(stock.e + 4u * lane + 1u) = make_float2(ps.rd.y, ps.rd.z); }
                 else { stock.park_a[lane] = make_float4(ps.ro.x, ps.ro.y, ps.ro.z, ps.rd.x); stock.park_b[lane] = make_float2(ps.rd.y, ps.rd.z); }
-                if (lane < n_cam) stock.template camera<RngCtrT<STEP>>(P, wc.next + lane, (wc.ring_head + wc.ring_count + lane) & 63u, ps.ro, ps.rd, /* here = 0: sample indices stay below 2^31 (band_samples) */ wc.next >> 31);
+                if (lane < n_cam && walk_cam) stock.template camera<RngCtrT<STEP>>(P, wc.next + lane, (wc.ring_head + wc.ring_count + lane) & 63u, ps.ro, ps.rd, /* here = 0: sample indices stay below 2^31 (band_samples) */ wc.next >> 31);
             }
         }
-        if (n_cam != 0u ? lane < n_cam : live) hit = hit_scene<HAS_MESH, true, KINDS, BOUNDED, RECIP_FIRST>(prims, P.n_prims, P.nodes, P.tris, ps.ro, ps.rd, h, pmask);     // renderer.rs:24
+        if (n_cam != 0u ? lane < n_cam && walk_cam : live) hit = hit_scene<HAS_MESH, true, KINDS, BOUNDED, RECIP_FIRST>(prims, P.n_prims, P.nodes, P.tris, ps.ro, ps.rd, h, pmask);     // renderer.rs:24
         prof.mark(1);
         if constexpr (PREHIT) {
             if (n_cam != 0u) {                             // finish or stock the camera paths, take the parked rays back, and walk them next
@@ -821,6 +832,9 @@ namespace mi355rt {
 // +0 is never -0).  Samples past spp enter as +0, which leaves a sum unchanged.  No LDS, 14 VGPRs: enough waves in
 // flight to keep the HBM read stream busy (6.4 TB/s; the LDS-transpose version it replaces reached 3.3).
 // ===================================================================================================
+#ifndef MI355RT_RESOLVE_SKIP
+#define MI355RT_RESOLVE_SKIP 1                               // 0 builds k_resolve as it was: ResolveParams.cam_mask is not looked at
+#endif
 DI float dpp_row_shr1_zero(float v) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x111, 0xF, 0xF, true)); }
 DI float dpp_row_ror1(float v) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x121, 0xF, 0xF, true)); }
 __global__ void __launch_bounds__(256) k_resolve(const ResolveParams P) {
@@ -838,11 +852,17 @@ __global__ void __launch_bounds__(256) k_resolve(const ResolveParams P) {
     float4* __restrict__ accum = reinterpret_cast<float4*>(P.accum);
     f3 acc = mk(0.f, 0.f, 0.f);                                  // meaningful in lane 0 of the row
     if (accum && P.accum_load && valid) { const float4 a = accum[o]; acc = mk(a.x, a.y, a.z); }
+    // A pixel that no camera ray can leave with a hit (its camera-mask word is 0, rt_prepare.cpp build_camera_masks): each of its samples is the
+    // constant the render kernel stored, so the row feeds that constant to the same chain and reads nothing.  The same instructions on the same values.
+    constexpr bool RESOLVE_SKIP = MI355RT_RESOLVE_SKIP != 0;
+    bool empty = false;
+    if constexpr (RESOLVE_SKIP) { if (P.cam_mask && valid) empty = P.cam_mask[p] == 0u; }
     for (uint32_t c = 0; c < P.spp; c += 16u) {
         f3 x = mk(0.f, 0.f, 0.f);
         if (valid && c + s < P.spp) {
             const float* q = rad + 3u * (c + s);
-            x = mk(__builtin_nontemporal_load(q), __builtin_nontemporal_load(q + 1), __builtin_nontemporal_load(q + 2));
+            if (RESOLVE_SKIP && empty) x = mk(1.f, 1.f, 1.f) * mk(P.miss[0], P.miss[1], P.miss[2]);      // what the render kernel stored there (HitStock::append, a miss at throughput 1)
+            else x = mk(__builtin_nontemporal_load(q), __builtin_nontemporal_load(q + 1), __builtin_nontemporal_load(q + 2));
         }
         if (s == 0u) x = acc + x;                                 // renderer.rs:100 goes on where the previous 16 samples stopped
         f3 t = x;

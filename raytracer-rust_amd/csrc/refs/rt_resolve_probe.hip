@@ -23,6 +23,13 @@ struct ResolveProbeArgs {                              // 64 B; device.ResolvePr
     uint32_t width;                                     // with out_row: the image width (its magic pair is computed here); else unused
 };
 static_assert(sizeof(ResolveProbeArgs) == 64, "ResolveProbeArgs");
+struct ResolveMaskedProbeArgs {                        // 88 B; device.ResolveMaskedProbeArgs has the same layout
+    ResolveProbeArgs plain;
+    uint64_t cam_mask;                                  // ResolveParams.cam_mask: band_pixels words, one per band pixel (0: no table)
+    float miss[3];                                      // ResolveParams.miss
+    uint32_t pad;
+};
+static_assert(sizeof(ResolveMaskedProbeArgs) == 88, "ResolveMaskedProbeArgs");
 struct GatherProbeArgs {                                // 64 B; device.GatherProbeArgs has the same layout
     uint64_t src_row;                                   // n_rows entries
     uint64_t src_packed, dst_packed, src_linear, dst_linear;     // GatherParams (src_packed 0: no k_gather_strips launch)
@@ -35,11 +42,26 @@ static_assert(sizeof(GatherProbeArgs) == 64, "GatherProbeArgs");
 
 using namespace mi355rt;
 
+// One k_resolve launch for both entries below; cam_mask / miss as ResolveParams takes them.
+static int resolve_probe(const ResolveProbeArgs& a, const uint32_t* cam_mask, const float* miss);
+
 // Not in the public header; the reference build's diagnostic entries.
 extern "C" int mi355rt_debug_resolve(const void* args) {
     return guard([&]() -> int {
     if (!args) return fail(MI355RT_ERR_INVALID, "debug_resolve: null");
-    const ResolveProbeArgs a = *static_cast<const ResolveProbeArgs*>(args);
+    return resolve_probe(*static_cast<const ResolveProbeArgs*>(args), nullptr, nullptr);
+    });
+}
+// ... and with the band's camera-mask words: a pixel whose word is 0 is resolved from `miss`, its samples are not read (k_resolve, RESOLVE_SKIP).
+extern "C" int mi355rt_debug_resolve_masked(const void* args) {
+    return guard([&]() -> int {
+    if (!args) return fail(MI355RT_ERR_INVALID, "debug_resolve_masked: null");
+    const ResolveMaskedProbeArgs m = *static_cast<const ResolveMaskedProbeArgs*>(args);
+    return resolve_probe(m.plain, reinterpret_cast<const uint32_t*>(m.cam_mask), m.miss);
+    });
+}
+static int resolve_probe(const ResolveProbeArgs& a, const uint32_t* cam_mask, const float* miss) {
+    {
     if (!a.radiance || !a.out_packed || !a.spp) return fail(MI355RT_ERR_INVALID, "debug_resolve: radiance, out_packed and spp are required");
     if ((uint64_t)a.band_pixel0 + a.band_pixels >= (1ull << 31)) return fail(MI355RT_ERR_INVALID, "debug_resolve: pixel numbers stay below 2^31");
     if (a.out_row && !a.width) return fail(MI355RT_ERR_INVALID, "debug_resolve: out_row needs the width");
@@ -56,10 +78,12 @@ extern "C" int mi355rt_debug_resolve(const void* args) {
     r.out_row = reinterpret_cast<const uint32_t*>(a.out_row);
     r.width = a.width;
     magic_div(a.width, r.width_mul, r.width_shift);
+    r.cam_mask = cam_mask;
+    if (miss) { r.miss[0] = miss[0]; r.miss[1] = miss[1]; r.miss[2] = miss[2]; }
     if (a.band_pixels && launch_resolve(r, nullptr) != 0) return fail(MI355RT_ERR_HIP, "debug_resolve: k_resolve launch failed");
     HIP_TRY(hipStreamSynchronize(nullptr));
     return MI355RT_OK;
-    });
+    }
 }
 
 extern "C" int mi355rt_debug_gather(const void* args) {

@@ -43,6 +43,8 @@ def refs():
     L.mi355rt_debug_stages.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
     L.mi355rt_debug_resolve.restype = C.c_int
     L.mi355rt_debug_resolve.argtypes = [C.c_void_p]
+    L.mi355rt_debug_resolve_masked.restype = C.c_int
+    L.mi355rt_debug_resolve_masked.argtypes = [C.c_void_p]
     L.mi355rt_debug_gather.restype = C.c_int
     L.mi355rt_debug_gather.argtypes = [C.c_void_p]
     L.mi355rt_debug_rng_block.restype = C.c_int
@@ -63,6 +65,10 @@ class ResolveProbeArgs(C.Structure):
                 ("inv_spp", C.c_float), ("width", C.c_uint32)]
 
 
+class ResolveMaskedProbeArgs(C.Structure):
+    _fields_ = [("plain", ResolveProbeArgs), ("cam_mask", C.c_uint64), ("miss", C.c_float * 3), ("pad", C.c_uint32)]
+
+
 class GatherProbeArgs(C.Structure):
     _fields_ = [("src_row", C.c_uint64), ("src_packed", C.c_uint64), ("dst_packed", C.c_uint64), ("src_linear", C.c_uint64), ("dst_linear", C.c_uint64),
                 ("accum_src", C.c_uint64), ("accum_dst", C.c_uint64), ("n_rows", C.c_uint32), ("width", C.c_uint32)]
@@ -75,6 +81,17 @@ def debug_resolve(radiance, out_packed, spp, inv_spp, band_pixels, band_pixel0=0
                          int(band_pixel0), int(band_pixels), int(spp), float(inv_spp), int(width))
     L = refs()
     _check(L.mi355rt_debug_resolve(C.addressof(a)), "mi355rt_debug_resolve", L)
+
+
+def debug_resolve_masked(radiance, out_packed, spp, inv_spp, band_pixels, cam_mask, miss, band_pixel0=0, out_linear=0, accum=0, accum_load=False,
+                         out_row=0, width=0):
+    """Diagnostic (reference build): debug_resolve with the band's camera-mask words (cam_mask: band_pixels uint32 on the device, 0 = no
+    table) and the miss colour (three floats): a pixel whose word is 0 is resolved from `miss` and its samples are not read."""
+    a = ResolveMaskedProbeArgs(ResolveProbeArgs(int(radiance), int(out_packed), int(out_linear), int(accum), int(out_row), 1 if accum_load else 0,
+                                                int(band_pixel0), int(band_pixels), int(spp), float(inv_spp), int(width)),
+                               int(cam_mask), (C.c_float * 3)(*[float(m) for m in miss]), 0)
+    L = refs()
+    _check(L.mi355rt_debug_resolve_masked(C.addressof(a)), "mi355rt_debug_resolve_masked", L)
 
 
 def debug_gather(src_row, n_rows, width, src_packed=0, dst_packed=0, src_linear=0, dst_linear=0, accum_src=0, accum_dst=0):
@@ -305,7 +322,7 @@ def _check(rc, what, library=None):
 
 def set_knob(name, value, library=None):
     """Diagnostic: process-wide default knob for every context created afterwards (also inside the one-shot calls).
-    Knobs: kernel, guided_mult, spin_idle, spin_entry, wave_times, row_order, cam_cull, denoise_staged, ao_form, inline_steps, trav_min (rt_api.cpp)."""
+    Knobs: kernel, guided_mult, spin_idle, spin_entry, wave_times, row_order, cam_cull, resolve_skip, denoise_staged, ao_form, inline_steps, trav_min (rt_api.cpp)."""
     L = library or lib()
     _check(L.mi355rt_debug_set_knob(None, name.encode(), int(value)), f"mi355rt_debug_set_knob({name})", L)
 
