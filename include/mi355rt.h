@@ -42,6 +42,7 @@ extern "C" {
                                     Likewise the ray queries: mi355rt_context_trace_rays, mi355rt_context_first_hits, mi355rt_trace_rays;
                                     and the denoiser: mi355rt_denoise_scratch_bytes, mi355rt_context_denoise, mi355rt_denoise;
                                     and the occlusion queries: mi355rt_context_occluded, mi355rt_occluded, mi355rt_context_ambient_occlusion;
+                                    and the radiance queries: mi355rt_radiance_scratch_bytes, mi355rt_context_trace_radiance, mi355rt_trace_radiance;
                                     and, in the host library, the noise estimate: mi355rt_noise_create, mi355rt_noise_free, mi355rt_noise_reset,
                                     mi355rt_noise_update, mi355rt_noise_evaluate;
                                     and, in the device library, the same estimate on device memory: mi355rt_noise_device_create, mi355rt_noise_device_destroy,
@@ -393,6 +394,59 @@ typedef struct mi355rt_ao_params {   /* 16 bytes */
 /* params_or_null == NULL: {16, 0, +inf, 0} */
 int  mi355rt_context_ambient_occlusion(mi355rt_context* ctx, const mi355rt_options* options_or_null, const mi355rt_ao_params* params_or_null,
                                        const void* d_hits, void* d_out_f32, void* hip_stream);
+
+/* ---- radiance queries: whole paths along caller-supplied rays (added within ABI version 5: probe for the symbols) ----
+ * The reference's trace_ray(ray, scene, depth, rng) (src/renderer.rs:19-65: hit, emit, scatter, recurse) for rays of the caller's own: a thin
+ * lens, a fisheye, a panorama or an orthographic view, a light probe, a lightmap texel, a virtual sensor -- or the resident scene from a moved
+ * camera without another mi355rt_context_set_scene.  The library has no camera model here: the caller makes the rays.
+ *
+ * DEFINITION.  Sample s of ray i is one path in MI355RT_RNG_CTR's addressing (mi355rt_options.rng_mode; the generator of ABI version 4):
+ *   ykey = (uint64)row + params.seed;  k0 = low word, k1 = high word;  the path's draws are those of rng.start(k0, k1, x, s) -- what the render
+ *   draws for sample s of the pixel in column x of image row `row`.  The path STANDS AT RAY 0.  The words of (ray 0, block 0) are NOT drawn by
+ *   the query: they belong to whoever made the ray.  Words 0 / 1 are the render's pixel jitter; words 2 / 3 are free, for a lens sample for
+ *   example.  The scatter event after ray r draws from ray r + 1, exactly as the render does.
+ *   The direction is normalised once (Ray::new, src/ray.rs:12-17; a length below 1e-4 is left alone); scattered rays are used as the
+ *   materials return them.  Every segment is HittableList::hit with t_min = EPSILON (the record of mi355rt_context_trace_rays).
+ *   The radiance is folded front to back, as the GPU render folds it: throughput * terminal, where terminal is the emitted colour of a
+ *   material that does not scatter, the miss colour of a ray that hits nothing (the sky texture's texel when the scene has one), or BLACK when
+ *   max_depth segments were traced -- so inf * 0 is NaN, as documented at mi355rt_scene.  max_depth == 0: every sample is 1 * BLACK = +0.
+ * CONSEQUENCE.  Given the render's own camera rays (camera.rs:33-42 with u = (x + word 0) / width, v = (row + word 1) / height, normalised
+ *   once) and x = the pixel's column, row = its image row, the result is the render's linear image bit for bit.
+ * SUMS.  d_accum holds n_rays float4 running sums (x, y, z; w is written 0).  It is READ only when sample_begin > 0 and is ALWAYS written.  The
+ *   samples [sample_begin, sample_end) of a ray are added in sample order, in float32, continuing from the stored sum (renderer.rs:100).
+ *   d_out_linear, if given, receives n_rays * 3 floats: sum * (1.0f / (float)sample_end) (renderer.rs:85,103).  Calls that cover 0 .. N in any
+ *   chunking are bit-identical to one call [0, N).
+ * SCRATCH is the caller's (the denoiser's pattern): mi355rt_radiance_scratch_bytes(n_rays, sample_end - sample_begin) bytes, 16-byte aligned --
+ *   12 bytes per (ray, sample) pair, rounded up to a multiple of 16.  Its contents mean nothing between calls.
+ * REFUSALS, all decided before any HIP call, MI355RT_ERR_INVALID with a text that names the argument: null params, flags != 0, reserved != 0,
+ *   sample_begin >= sample_end; with n_rays > 0 a null or misaligned (16 bytes) d_rays / d_accum / d_scratch, a d_out_linear off 4 bytes, or
+ *   n_rays * (sample_end - sample_begin) >= 2^32 (split the call); a null context, a context without a scene.  n_rays == 0 is MI355RT_OK and
+ *   does nothing.  mi355rt_radiance_scratch_bytes refuses a null out_bytes and the same overflow.
+ * PROTOCOL of the ray queries above: the call only reads the resident scene -- no workspace of the context, no counters, no error word --, may
+ *   be enqueued beside a render of the same context on another stream, ignores mi355rt_context_set_share, and returns a pending watchdog failure
+ *   of an EARLIER render the way mi355rt_context_render returns it.  Its work per sample is bounded by max_depth: it has no watchdog of its own.
+ *   One device only.  MI355RT_FLAG_FIXED_AABB and the reference stream (MI355RT_RNG_REF) have no form here. */
+typedef struct mi355rt_path_ray {     /* 32 bytes; arrays 16-byte aligned */
+    float origin[3];    uint32_t x;   /* stream address word "x" (the render uses the pixel column) */
+    float direction[3]; uint32_t row; /* stream key: row + params.seed, 64 bit (the render uses the image row y) */
+} mi355rt_path_ray;
+typedef struct mi355rt_radiance_params {  /* 32 bytes */
+    uint32_t sample_begin, sample_end;    /* samples [begin, end) of EVERY ray; begin < end */
+    uint32_t max_depth;                   /* renderer.rs:19-21; 0 = every sample is 1 * BLACK */
+    uint32_t flags;                       /* must be 0 */
+    uint64_t seed;                        /* as mi355rt_options.seed */
+    uint64_t reserved;                    /* must be 0 */
+} mi355rt_radiance_params;
+int  mi355rt_radiance_scratch_bytes(uint32_t n_rays, uint32_t samples, uint64_t* out_bytes);
+/* n_rays rays, DEVICE pointers; enqueues on hip_stream (NULL = default stream) and returns. */
+int  mi355rt_context_trace_radiance(mi355rt_context* ctx, const mi355rt_radiance_params* params,
+                                    const void* d_rays, uint32_t n_rays, void* d_accum, void* d_out_linear_or_null,
+                                    void* d_scratch, void* hip_stream);
+/* One-shot with HOST buffers (context on device 0, upload, query, copy back, destroy); it pays mi355rt_context_set_scene on every call.
+ * accum_in_out (n_rays * 4 floats) must not be null: it is uploaded when sample_begin > 0 and always copied back.  Without a device:
+ * MI355RT_ERR_NO_DEVICE (no CPU path), like mi355rt_trace_rays. */
+int  mi355rt_trace_radiance(const mi355rt_scene* scene, const mi355rt_radiance_params* params,
+                            const mi355rt_path_ray* rays, uint32_t n_rays, float* accum_in_out, float* out_linear_or_null);
 
 /* ---- denoising a preview: an edge-avoiding a-trous filter guided by first-hit records (added within ABI version 5: probe for the symbols) ----
  * For the first chunks of a progressive render: the noisy linear image and the records of mi355rt_context_first_hits for the same rows go in,

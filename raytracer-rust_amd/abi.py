@@ -109,7 +109,22 @@ class Segment(C.Structure):                               # mi355rt_segment, 32 
 SEGMENT_DTYPE = np.dtype([("origin", "<f4", 3), ("_pad0", "<f4"), ("direction", "<f4", 3), ("t_max", "<f4")])
 
 
-class AoParams(C.Structure):                              # mi355rt_ao_params, 16 bytes
+class PathRay(C.Structure):                               # mi355rt_path_ray, 32 bytes: a Ray whose pads are the stream address words
+    _fields_ = [("origin", f32 * 3), ("x", u32), ("direction", f32 * 3), ("row", u32)]
+
+
+PATH_RAY_DTYPE = np.dtype([("origin", "<f4", 3), ("x", "<u4"), ("direction", "<f4", 3), ("row", "<u4")])
+
+
+class RadianceParams(C.Structure):                        # mi355rt_radiance_params, 32 bytes
+    _fields_ = [("sample_begin", u32), ("sample_end", u32), ("max_depth", u32), ("flags", u32), ("seed", u64), ("reserved", u64)]
+
+    @classmethod
+    def make(cls, sample_begin, sample_end, max_depth, seed=0):
+        return cls(sample_begin, sample_end, max_depth, 0, seed, 0)
+
+
+class AoParams(C.Structure):                             # mi355rt_ao_params, 16 bytes
     _fields_ = [("samples", u32), ("seed", u32), ("radius", f32), ("_pad", u32)]
 
     @classmethod

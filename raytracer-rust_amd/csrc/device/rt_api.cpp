@@ -26,6 +26,7 @@
 #include "rt_query.h"
 #include "rt_denoise.h"
 #include "rt_occlusion.h"
+#include "rt_radiance.h"
 
 using namespace mi355rt;
 
@@ -74,6 +75,7 @@ struct mi355rt_context {
     std::vector<float> row_cost;
     int knob_denoise_staged = 1;         // diagnostic knob "denoise_staged": 1 (the product) = the denoiser's levels with step 1 and 2 stage their tile in LDS; 0 = they gather like the later levels (the A/B of DESIGN.md 4.7)
     int knob_ao_form = 0;                // diagnostic knob "ao_form": AO_FORM_* of rt_occlusion.h; 0 (the product) = a pixel's samples across the lanes of a wave, 1 = a pixel per lane (the A/B of DESIGN.md 4.8)
+    int knob_radiance_items = 0;         // diagnostic knob "radiance_items": K of rt_radiance.h, 1 .. 64 items per lane of k_radiance_paths; 0 (the product) = RADIANCE_ITEMS_DEFAULT (the A/B of DESIGN.md 4.12)
     int knob_row_order = -1;             // diagnostic knob "row_order": 1 on; -1 / 0 off (NOT shipped as a default: no measured gain, see set_scene)
     uint32_t order_groups = 0;           // how many groups the cached tables were dealt over (work shards x bands)
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
@@ -215,6 +217,7 @@ int apply_knob(mi355rt_context* ctx, const std::string& name, int v) {
     else if (name == "resolve_skip") { if (v < 0 || v > 1) return fail(MI355RT_ERR_INVALID, "knob resolve_skip"); ctx->knob_resolve_skip = v; }
     else if (name == "denoise_staged") { if (v < 0 || v > 1) return fail(MI355RT_ERR_INVALID, "knob denoise_staged"); ctx->knob_denoise_staged = v; }
     else if (name == "ao_form") { if (v < 0 || v > 1) return fail(MI355RT_ERR_INVALID, "knob ao_form"); ctx->knob_ao_form = v; }
+    else if (name == "radiance_items") { if (v < 0 || v > (int)RADIANCE_ITEMS_MAX) return fail(MI355RT_ERR_INVALID, "knob radiance_items"); ctx->knob_radiance_items = v; }
     else if (name == "row_order") { if (v < -1 || v > 1) return fail(MI355RT_ERR_INVALID, "knob row_order"); ctx->knob_row_order = v; }
     else return fail(MI355RT_ERR_INVALID, "unknown knob " + name);
     return MI355RT_OK;
@@ -227,7 +230,7 @@ extern "C" {
 // Diagnostic hook (not part of the public header).  ctx != NULL: set one knob of that context (before set_scene).  ctx == NULL: a
 // process-wide default applied to every context created afterwards -- also those the one-shot calls create; name == NULL clears
 // all defaults.  Knobs: kernel (KERNEL_* of rt_device.h, -1 = automatic), guided_mult, spin_idle, spin_entry, wave_times, row_order,
-// cam_cull (0: k_render_ctr_simple_qc gets no camera masks), resolve_skip (0: k_resolve gets none), and for the reference build's state machine inline_steps, trav_min.
+// cam_cull (0: k_render_ctr_simple_qc gets no camera masks), resolve_skip (0: k_resolve gets none), radiance_items (K of k_radiance_paths, 0 = the default), and for the reference build's state machine inline_steps, trav_min.
 int mi355rt_debug_set_knob(mi355rt_context* ctx, const char* name, int value) {
     return guard([&]() -> int {
     if (ctx) return name ? apply_knob(ctx, name, value) : fail(MI355RT_ERR_INVALID, "knob name is null");
@@ -695,6 +698,35 @@ int mi355rt_context_ambient_occlusion(mi355rt_context* ctx, const mi355rt_option
     return MI355RT_OK;
     });
 }
+
+// ---- radiance queries (rt_radiance.hip): whole paths along the caller's rays ----------------------------------------------------------------
+// What mi355rt_context_trace_radiance does with its context: the entry point itself stands with its kernels in rt_radiance.hip, behind the barrier, as
+// rt_noise.hip's do; this half needs the context struct.  The protocol of the ray queries: the call reads the scene arrays only, neither waits on
+// `done` nor records it, and does not consult set_share.  Every refusal, the item count and the grids are rt_prepare.cpp's (plan_radiance), before any HIP call.
+}  // extern "C"
+int mi355rt::context_trace_radiance(mi355rt_context* ctx, const mi355rt_radiance_params* params, const void* d_rays, uint32_t n_rays, void* d_accum,
+                                    void* d_out_linear, void* d_scratch, void* hip_stream) {
+    static_assert(sizeof(mi355rt_path_ray) == 32 && sizeof(mi355rt_radiance_params) == 32, "the kernel reads a ray as two 16-byte halves");
+    static_assert(RADIANCE_PLAN_BLOCK == RADIANCE_BLOCK_THREADS && RADIANCE_PLAN_ITEMS_MAX == RADIANCE_ITEMS_MAX, "plan_radiance cuts the grids the kernels are launched on");
+    RadiancePlan plan{};
+    if (int rc = plan_radiance(ctx != nullptr, ctx && ctx->have_scene, params, d_rays, n_rays, d_accum, d_out_linear, d_scratch,
+                               ctx ? (uint32_t)ctx->knob_radiance_items : 0u, RADIANCE_ITEMS_DEFAULT, plan)) return rc;
+    if (n_rays == 0) return MI355RT_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (int erc = report_device_error(ctx)) return erc;              // an earlier asynchronous render on this context failed
+    RadianceParams p{};
+    p.prims = ctx->prims.p; p.mats = ctx->mats.p; p.nodes = ctx->nodes.p; p.tris = ctx->tris.p; p.n_prims = ctx->n_prims;
+    p.sky = ctx->sky_w ? ctx->sky.p : nullptr; p.sky_w = ctx->sky_w; p.sky_h = ctx->sky_h; p.textures = ctx->textures.p;
+    std::memcpy(p.miss, ctx->miss, sizeof p.miss);
+    p.rays = d_rays; p.scratch = (float*)d_scratch; p.n_items = plan.n_items; p.samples = plan.samples; p.sample_begin = params->sample_begin;
+    p.max_depth = params->max_depth; p.items_per_lane = plan.items_per_lane; p.seed_lo = plan.seed_lo; p.seed_hi = plan.seed_hi;
+    RadianceSum s{};
+    s.scratch = (const float*)d_scratch; s.accum = (float*)d_accum; s.out_linear = (float*)d_out_linear; s.n_rays = n_rays; s.samples = plan.samples;
+    s.accum_load = plan.accum_load; s.inv_total = plan.inv_total;
+    if (launch_radiance(p, s, ctx->has_mesh, plan.grid_paths, plan.grid_sum, hip_stream) != 0) return fail(MI355RT_ERR_HIP, "k_radiance launch failed");
+    return MI355RT_OK;
+}
+extern "C" {
 
 // ---- the denoiser (rt_denoise.hip): an a-trous filter over a linear image, guided by first-hit records --------------------------------
 // The context names the device and carries the error word of its renders; nothing of it is read or written by the kernels, so the

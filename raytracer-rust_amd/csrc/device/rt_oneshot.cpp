@@ -1,9 +1,9 @@
 // rt_oneshot.cpp -- the calls of include/mi355rt.h that take host buffers and give host buffers back, part of libmi355rt.so:
-// mi355rt_render, mi355rt_render_multi, mi355rt_render_progressive, mi355rt_render_progressive_multi, mi355rt_trace_rays, mi355rt_occluded and
-// mi355rt_denoise.  Each is a client of the resident API and of nothing else (neither context struct is visible here): the checks that
+// mi355rt_render, mi355rt_render_multi, mi355rt_render_progressive, mi355rt_render_progressive_multi, mi355rt_trace_rays, mi355rt_occluded,
+// mi355rt_trace_radiance (its body: oneshot_trace_radiance) and mi355rt_denoise.  Each is a client of the resident API and of nothing else (neither context struct is visible here): the checks that
 // need no device, a context (or a multi context) of its own, device buffers, the resident call, the copy back.  What they share stands
 // once: Call owns the context and the buffers of one call and gives them up on every way out; upload / copy_back name the buffer that
-// failed; render_chunks is what the two progressive calls do once they hold their context, query what the two queries do; run_parts
+// failed; render_chunks is what the two progressive calls do once they hold their context, query what the queries do; run_parts
 // (rt_host.h) deals mi355rt_render_multi's devices over threads.
 #include <algorithm>
 #include <cstring>
@@ -12,6 +12,7 @@
 
 #include "../../../include/mi355rt.h"
 #include "rt_host.h"
+#include "rt_radiance.h"
 
 using namespace mi355rt;
 
@@ -97,19 +98,21 @@ int render_chunks(Call& call, int device, const mi355rt_scene* scene, const mi35
     return rc;
 }
 
-// The two queries: a context on device 0, the scene uploaded (set_scene wants a view; a query does not look at it), n records up, one query, n records back.
+// The queries: a context on device 0, the scene uploaded (set_scene wants a view; a query does not look at it), n records up, one query, n records back.
+// A record of the result is out_per elements of Out; in_out: the result's buffer is uploaded first (running sums).  `run` gets the call, for what else it holds on the device.
 template <class In, class Out, class Query>
-int query(const mi355rt_scene* scene, const In* in, const char* in_name, uint32_t n, Out* out, const char* out_name, Query&& run) {
+int query(const mi355rt_scene* scene, const In* in, const char* in_name, uint32_t n, Out* out, const char* out_name, Query&& run, size_t out_per = 1, bool in_out = false) {
     Call call;
     if (int rc = mi355rt_context_create(0, &call.ctx)) return rc;
     const mi355rt_camera no_camera{}; const mi355rt_settings one_pixel{1, 1, 1, 1};
     if (int rc = mi355rt_context_set_scene(call.ctx, scene, &no_camera, &one_pixel)) return rc;
     In* d_in = nullptr; Out* d_out = nullptr;
     if (int rc = call.alloc(d_in, n, in_name)) return rc;
-    if (int rc = call.alloc(d_out, n, out_name)) return rc;
+    if (int rc = call.alloc(d_out, n * out_per, out_name)) return rc;
     if (int rc = upload(d_in, in, n, in_name)) return rc;
-    if (int rc = run(call.ctx, d_in, d_out)) return rc;
-    return copy_back(out, d_out, n, out_name);
+    if (in_out) if (int rc = upload(d_out, out, n * out_per, out_name)) return rc;
+    if (int rc = run(call, d_in, d_out)) return rc;
+    return copy_back(out, d_out, n * out_per, out_name);
 }
 
 }  // namespace
@@ -250,8 +253,8 @@ int mi355rt_trace_rays(const mi355rt_scene* scene, const mi355rt_ray* rays, uint
     if (!scene) return fail(MI355RT_ERR_INVALID, "scene is null");
     if (n_rays && (!rays || !out_hits)) return fail(MI355RT_ERR_INVALID, "trace_rays: rays / out_hits is null");
     if (n_rays == 0) return MI355RT_OK;
-    return query(scene, rays, "rays", n_rays, out_hits, "hits", [&](mi355rt_context* ctx, const mi355rt_ray* d_rays, mi355rt_hit* d_hits) {
-        return mi355rt_context_trace_rays(ctx, d_rays, n_rays, d_hits, nullptr); });
+    return query(scene, rays, "rays", n_rays, out_hits, "hits", [&](Call& call, const mi355rt_ray* d_rays, mi355rt_hit* d_hits) {
+        return mi355rt_context_trace_rays(call.ctx, d_rays, n_rays, d_hits, nullptr); });
     });
 }
 
@@ -261,10 +264,35 @@ int mi355rt_occluded(const mi355rt_scene* scene, const mi355rt_segment* segments
     if (n && !segments) return fail(MI355RT_ERR_INVALID, "occluded: segments is null");
     if (n && !out) return fail(MI355RT_ERR_INVALID, "occluded: out is null");
     if (n == 0) return MI355RT_OK;
-    return query(scene, segments, "segments", n, out, "words", [&](mi355rt_context* ctx, const mi355rt_segment* d_seg, uint32_t* d_out) {
-        return mi355rt_context_occluded(ctx, d_seg, n, d_out, nullptr); });
+    return query(scene, segments, "segments", n, out, "words", [&](Call& call, const mi355rt_segment* d_seg, uint32_t* d_out) {
+        return mi355rt_context_occluded(call.ctx, d_seg, n, d_out, nullptr); });
     });
 }
+
+// What mi355rt_trace_radiance does (its entry point stands in rt_radiance.hip, behind the barrier): the rays go up, the running sums go up (when the
+// call continues them) and come back; the scratch and the optional means are the call's own.
+}  // extern "C"
+int mi355rt::oneshot_trace_radiance(const mi355rt_scene* scene, const mi355rt_radiance_params* params, const mi355rt_path_ray* rays, uint32_t n_rays,
+                                    float* accum_in_out, float* out_linear) {
+    if (!scene) return fail(MI355RT_ERR_INVALID, "trace_radiance: scene is null");
+    if (!params) return fail(MI355RT_ERR_INVALID, "trace_radiance: params is null");
+    if (params->flags != 0u) return fail(MI355RT_ERR_INVALID, "trace_radiance: params.flags must be 0");
+    if (params->reserved != 0u) return fail(MI355RT_ERR_INVALID, "trace_radiance: params.reserved must be 0");
+    if (params->sample_begin >= params->sample_end) return fail(MI355RT_ERR_INVALID, "trace_radiance: params.sample_begin must be below params.sample_end");
+    if (n_rays && !rays) return fail(MI355RT_ERR_INVALID, "trace_radiance: rays is null");
+    if (n_rays && !accum_in_out) return fail(MI355RT_ERR_INVALID, "trace_radiance: accum_in_out is null");
+    if (n_rays == 0) return MI355RT_OK;
+    uint64_t scratch_bytes = 0;
+    if (int rc = radiance_scratch_bytes(n_rays, params->sample_end - params->sample_begin, &scratch_bytes)) return rc;
+    return query(scene, rays, "rays", n_rays, accum_in_out, "accum", [&](Call& call, const mi355rt_path_ray* d_rays, float* d_accum) -> int {
+        unsigned char* d_scratch = nullptr; float* d_linear = nullptr;
+        if (int rc = call.alloc(d_scratch, (size_t)scratch_bytes, "scratch")) return rc;
+        if (out_linear) if (int rc = call.alloc(d_linear, (size_t)n_rays * 3, "out_linear")) return rc;
+        if (int rc = mi355rt_context_trace_radiance(call.ctx, params, d_rays, n_rays, d_accum, d_linear, d_scratch, nullptr)) return rc;
+        return out_linear ? copy_back(out_linear, d_linear, (size_t)n_rays * 3, "linear") : MI355RT_OK;
+    }, 4, params->sample_begin > 0u);
+}
+extern "C" {
 
 // Host buffers in, host buffers out: a context on device 0 (no scene), the image and the records uploaded, one call, the results copied back.
 int mi355rt_denoise(uint32_t width, uint32_t rows, const mi355rt_denoise_params* params, const float* linear_in, const mi355rt_hit* hits,

@@ -132,6 +132,47 @@ int plan_ambient_occlusion(bool have_ctx, bool have_scene, const mi355rt_setting
     return MI355RT_OK;
 }
 
+int radiance_scratch_bytes(uint32_t n_rays, uint32_t samples, uint64_t* out_bytes) {
+    if (!out_bytes) return fail(MI355RT_ERR_INVALID, "trace_radiance: out_bytes is null");
+    const uint64_t items = (uint64_t)n_rays * samples;
+    if (items >= (1ull << 32)) return fail(MI355RT_ERR_INVALID, "trace_radiance: n_rays * samples must stay below 2^32 (split the call)");
+    *out_bytes = (items * 12u + 15u) & ~15ull;
+    return MI355RT_OK;
+}
+
+int plan_radiance(bool have_ctx, bool have_scene, const mi355rt_radiance_params* params, const void* rays, uint32_t n_rays, const void* accum,
+                  const void* out_linear, const void* scratch, uint32_t items_knob, uint32_t default_items, RadiancePlan& plan) {
+    if (!params) return fail(MI355RT_ERR_INVALID, "trace_radiance: params is null");
+    if (params->flags != 0u) return fail(MI355RT_ERR_INVALID, "trace_radiance: params.flags must be 0");
+    if (params->reserved != 0u) return fail(MI355RT_ERR_INVALID, "trace_radiance: params.reserved must be 0");
+    if (params->sample_begin >= params->sample_end) return fail(MI355RT_ERR_INVALID, "trace_radiance: params.sample_begin must be below params.sample_end");
+    plan = RadiancePlan{};
+    plan.samples = params->sample_end - params->sample_begin;
+    if (n_rays != 0u) {
+        if (!rays) return fail(MI355RT_ERR_INVALID, "trace_radiance: d_rays is null");
+        if (!accum) return fail(MI355RT_ERR_INVALID, "trace_radiance: d_accum is null");
+        if (!scratch) return fail(MI355RT_ERR_INVALID, "trace_radiance: d_scratch is null");
+        if (misaligned_to(rays, 16)) return fail(MI355RT_ERR_INVALID, "trace_radiance: d_rays must be 16-byte aligned");
+        if (misaligned_to(accum, 16)) return fail(MI355RT_ERR_INVALID, "trace_radiance: d_accum must be 16-byte aligned");
+        if (misaligned_to(scratch, 16)) return fail(MI355RT_ERR_INVALID, "trace_radiance: d_scratch must be 16-byte aligned");
+        if (misaligned_to(out_linear, 4)) return fail(MI355RT_ERR_INVALID, "trace_radiance: d_out_linear must be 4-byte aligned");
+        if (int rc = radiance_scratch_bytes(n_rays, plan.samples, &plan.scratch_bytes)) return rc;
+    }
+    if (!have_ctx) return fail(MI355RT_ERR_INVALID, "trace_radiance: ctx is null");
+    if (!have_scene) return fail(MI355RT_ERR_INVALID, "trace_radiance: context has no scene");
+    const uint32_t k = items_knob ? items_knob : default_items;
+    if (k == 0u || k > RADIANCE_PLAN_ITEMS_MAX) return fail(MI355RT_ERR_INVALID, "trace_radiance: items per lane out of range");
+    plan.n_items = n_rays * plan.samples;                            // (< 2^32: checked above)
+    plan.items_per_lane = k;
+    const uint64_t per_block = (uint64_t)RADIANCE_PLAN_BLOCK * k;
+    plan.grid_paths = (uint32_t)(((uint64_t)plan.n_items + per_block - 1u) / per_block);
+    plan.grid_sum = (uint32_t)(((uint64_t)n_rays + RADIANCE_PLAN_BLOCK / 16u - 1u) / (RADIANCE_PLAN_BLOCK / 16u));
+    plan.seed_lo = (uint32_t)params->seed; plan.seed_hi = (uint32_t)(params->seed >> 32);
+    plan.accum_load = params->sample_begin > 0u ? 1u : 0u;
+    plan.inv_total = 1.0f / (float)params->sample_end;               // renderer.rs:85
+    return MI355RT_OK;
+}
+
 // s = ceil(log2 d), mul = ceil(2^(31+s) / d) < 2^32, shift = s - 1.
 void magic_div(uint32_t d, uint32_t& mul, uint32_t& shift) {
     if (d <= 1) { mul = 0; shift = 0; return; }

@@ -64,6 +64,24 @@ struct AoPlan { uint32_t samples, log2_samples, seed; float radius; };
 int plan_ambient_occlusion(bool have_ctx, bool have_scene, const mi355rt_settings& st, const mi355rt_options* options_or_null,
                            const mi355rt_ao_params* params_or_null, const void* hits, const void* out, RowSel& sel, AoPlan& plan);
 
+// The radiance query (mi355rt.h, mi355rt_context_trace_radiance): every refusal, the scratch size, the item count and the two grids,
+// decided before any HIP call.  Refusals in this order (MI355RT_ERR_INVALID and a text that names the argument): the parameters -- null, flags,
+// reserved, sample_begin >= sample_end --; with n_rays > 0 the pointers (d_rays / d_accum / d_scratch null or not 16-byte aligned, d_out_linear not
+// 4-byte aligned) and n_rays * samples >= 2^32; then the context and its scene.  n_rays == 0 passes with n_items == 0: nothing to launch.
+constexpr uint32_t RADIANCE_PLAN_BLOCK = 256, RADIANCE_PLAN_ITEMS_MAX = 64;      // (rt_radiance.h: RADIANCE_BLOCK_THREADS, RADIANCE_ITEMS_MAX; rt_api.cpp asserts it)
+struct RadiancePlan {
+    uint64_t scratch_bytes;                                          // what mi355rt_radiance_scratch_bytes(n_rays, samples) reports
+    uint32_t n_items, samples, items_per_lane;                       // n_rays * samples; sample_end - sample_begin; K
+    uint32_t grid_paths, grid_sum;                                   // workgroups of 256: ceil(n_items / (256 * K)); ceil(n_rays / 16)
+    uint32_t seed_lo, seed_hi, accum_load;                           // accum_load: sample_begin > 0
+    float inv_total;                                                 // 1.0f / (float)sample_end
+};
+// 12 bytes per (ray, sample) pair, rounded up to a multiple of 16; MI355RT_ERR_INVALID for a null out_bytes or n_rays * samples >= 2^32.
+int radiance_scratch_bytes(uint32_t n_rays, uint32_t samples, uint64_t* out_bytes);
+// items_knob: the diagnostic knob "radiance_items" (0 = default_items).
+int plan_radiance(bool have_ctx, bool have_scene, const mi355rt_radiance_params* params, const void* rays, uint32_t n_rays, const void* accum,
+                  const void* out_linear_or_null, const void* scratch, uint32_t items_knob, uint32_t default_items, RadiancePlan& plan);
+
 // The render call (mi355rt_context_render / mi355rt_context_render_progressive): every refusal, the variant that is launched, the
 // bands the radiance workspace is cycled through and the geometry of each band's launch, decided before any HIP call.
 // q = n / d for every n < 2^31 as umulhi(n, mul) >> shift (mul == 0 encodes d == 1).

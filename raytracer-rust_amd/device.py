@@ -20,6 +20,7 @@ EXPORTS = ["mi355rt_render", "mi355rt_render_multi", "mi355rt_render_progressive
            "mi355rt_context_trace_rays", "mi355rt_context_first_hits", "mi355rt_trace_rays",
            "mi355rt_denoise_scratch_bytes", "mi355rt_context_denoise", "mi355rt_denoise",
            "mi355rt_context_occluded", "mi355rt_occluded", "mi355rt_context_ambient_occlusion",
+           "mi355rt_radiance_scratch_bytes", "mi355rt_context_trace_radiance", "mi355rt_trace_radiance",
            "mi355rt_noise_device_create", "mi355rt_noise_device_destroy", "mi355rt_noise_device_reset", "mi355rt_noise_device_update",
            "mi355rt_noise_device_evaluate"]
 
@@ -279,6 +280,12 @@ def _bind(so):
         L.mi355rt_occluded.argtypes = [C.POINTER(abi.Scene), C.c_void_p, C.c_uint32, C.c_void_p]
         L.mi355rt_context_ambient_occlusion.restype = C.c_int
         L.mi355rt_context_ambient_occlusion.argtypes = [C.c_void_p, C.POINTER(abi.Options), C.POINTER(abi.AoParams), C.c_void_p, C.c_void_p, C.c_void_p]
+        L.mi355rt_radiance_scratch_bytes.restype = C.c_int
+        L.mi355rt_radiance_scratch_bytes.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]
+        L.mi355rt_context_trace_radiance.restype = C.c_int
+        L.mi355rt_context_trace_radiance.argtypes = [C.c_void_p, C.POINTER(abi.RadianceParams), C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.mi355rt_trace_radiance.restype = C.c_int
+        L.mi355rt_trace_radiance.argtypes = [C.POINTER(abi.Scene), C.POINTER(abi.RadianceParams), C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
         L.mi355rt_noise_device_create.restype = C.c_int
         L.mi355rt_noise_device_create.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
         L.mi355rt_noise_device_destroy.restype = None
@@ -322,7 +329,7 @@ def _check(rc, what, library=None):
 
 def set_knob(name, value, library=None):
     """Diagnostic: process-wide default knob for every context created afterwards (also inside the one-shot calls).
-    Knobs: kernel, guided_mult, spin_idle, spin_entry, wave_times, row_order, cam_cull, resolve_skip, denoise_staged, ao_form, inline_steps, trav_min (rt_api.cpp)."""
+    Knobs: kernel, guided_mult, spin_idle, spin_entry, wave_times, row_order, cam_cull, resolve_skip, denoise_staged, ao_form, radiance_items, inline_steps, trav_min (rt_api.cpp)."""
     L = library or lib()
     _check(L.mi355rt_debug_set_knob(None, name.encode(), int(value)), f"mi355rt_debug_set_knob({name})", L)
 
@@ -520,6 +527,36 @@ def occluded(scene, segments, library=None):
     return out
 
 
+def radiance_scratch_bytes(n_rays, samples, library=None):
+    """mi355rt_radiance_scratch_bytes: the size of Context.trace_radiance's d_scratch for n_rays rays and samples = sample_end - sample_begin."""
+    L = library or lib()
+    n = C.c_uint64()
+    _check(L.mi355rt_radiance_scratch_bytes(int(n_rays), int(samples), C.byref(n)), "mi355rt_radiance_scratch_bytes", L)
+    return n.value
+
+
+def trace_radiance(scene, rays, params, accum=None, want_linear=True, library=None):
+    """One-shot mi355rt_trace_radiance with host buffers: samples [params.sample_begin, params.sample_end) of a whole path along every ray of
+    `scene`, added to the running sums.  rays: a numpy array of abi.PATH_RAY_DTYPE; params: abi.RadianceParams; accum: float32 [n, 4] sums of the
+    samples before sample_begin (needed when sample_begin > 0; not changed).  Returns (accum float32 [n, 4], linear float32 [n, 3] or None)."""
+    L = library or lib()
+    sc = getattr(scene, "c", scene)
+    rays = np.ascontiguousarray(rays)
+    if rays.dtype != abi.PATH_RAY_DTYPE:
+        raise ValueError("trace_radiance: rays must be an array of abi.PATH_RAY_DTYPE")
+    n = rays.size
+    if accum is None:
+        if params.sample_begin > 0:
+            raise ValueError("trace_radiance: sample_begin > 0 continues running sums: pass accum")
+        accum = np.zeros((n, 4), np.float32)
+    else:
+        accum = np.array(accum, np.float32, order="C").reshape(n, 4)
+    linear = np.zeros((n, 3), np.float32) if want_linear else None
+    _check(L.mi355rt_trace_radiance(C.byref(sc), C.byref(params), C.c_void_p(rays.ctypes.data), n, C.c_void_p(accum.ctypes.data),
+                                    C.c_void_p(linear.ctypes.data) if want_linear else None), "mi355rt_trace_radiance", L)
+    return accum, linear
+
+
 def denoise_scratch_bytes(width, rows, library=None):
     """mi355rt_denoise_scratch_bytes: the size of Context.denoise's d_scratch for a window of rows x width pixels."""
     L = library or lib()
@@ -665,6 +702,15 @@ class Context:
                                                          C.byref(params) if params is not None else None, C.c_void_p(d_hits) if d_hits else None,
                                                          C.c_void_p(d_out) if d_out else None, C.c_void_p(stream) if stream else None),
                "mi355rt_context_ambient_occlusion", self._L)
+
+    def trace_radiance(self, params, d_rays, n, d_accum, d_scratch, d_out_linear=None, stream=None):
+        """mi355rt_context_trace_radiance: samples [params.sample_begin, params.sample_end) of a whole path along each of n rays of the resident
+        scene, enqueued on `stream`.  Integer device addresses (16-byte aligned): d_rays n abi.PathRay records, d_accum n float4 running sums (read
+        when sample_begin > 0, always written), d_scratch radiance_scratch_bytes(n, sample_end - sample_begin) bytes; d_out_linear: n * 3 floats,
+        sum / sample_end, or None.  params: abi.RadianceParams."""
+        p = lambda a: C.c_void_p(a) if a else None
+        _check(self._L.mi355rt_context_trace_radiance(self._h, C.byref(params) if params is not None else None, p(d_rays), int(n), p(d_accum),
+                                                      p(d_out_linear), p(d_scratch), p(stream)), "mi355rt_context_trace_radiance", self._L)
 
     def denoise(self, width, rows, d_linear_in, d_hits, d_scratch, d_out_linear=None, d_out_packed=None, params=None, stream=None):
         """mi355rt_context_denoise: the a-trous filter of mi355rt.h over a contiguous window of rows x width pixels, enqueued on `stream`.  Integer
