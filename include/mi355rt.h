@@ -43,6 +43,7 @@ extern "C" {
                                     and the denoiser: mi355rt_denoise_scratch_bytes, mi355rt_context_denoise, mi355rt_denoise;
                                     and the occlusion queries: mi355rt_context_occluded, mi355rt_occluded, mi355rt_context_ambient_occlusion;
                                     and the radiance queries: mi355rt_radiance_scratch_bytes, mi355rt_context_trace_radiance, mi355rt_trace_radiance;
+                                    and the camera views: mi355rt_view_scratch_bytes, mi355rt_context_view_rays, mi355rt_context_render_view;
                                     and, in the host library, the noise estimate: mi355rt_noise_create, mi355rt_noise_free, mi355rt_noise_reset,
                                     mi355rt_noise_update, mi355rt_noise_evaluate;
                                     and, in the device library, the same estimate on device memory: mi355rt_noise_device_create, mi355rt_noise_device_destroy,
@@ -447,6 +448,63 @@ int  mi355rt_context_trace_radiance(mi355rt_context* ctx, const mi355rt_radiance
  * MI355RT_ERR_NO_DEVICE (no CPU path), like mi355rt_trace_rays. */
 int  mi355rt_trace_radiance(const mi355rt_scene* scene, const mi355rt_radiance_params* params,
                             const mi355rt_path_ray* rays, uint32_t n_rays, float* accum_in_out, float* out_linear_or_null);
+
+/* ---- camera views: device-made rays for a pinhole and a thin lens (added within ABI version 5: probe for the symbols) ----
+ * A VIEW is a camera the caller describes per call, for the resident scene: a moved camera or a depth-of-field lens without another
+ * mi355rt_context_set_scene.  The rays are made on the device, in front of the path loop of the radiance queries above: no host-made rays, no
+ * upload per sample, one call for any range of samples.  For every other camera model the caller still makes the rays (mi355rt_context_trace_radiance).
+ *
+ * DEFINITION.  The view has its own width x height image, independent of the scene's settings.  Pixel (x, y) is pixel y * width + x (row-major,
+ *   row 0 = top) and carries the stream address x = x, row = y.  For sample s, w[0..3] are the words of (ray 0, block 0) of
+ *   rng.start(ykey lo, ykey hi, x, s) with ykey = (uint64)y + seed -- MI355RT_RNG_CTR's addressing, as above --, and f(w) = (w >> 8) * 2^-24.
+ *   All arithmetic is float32, one rounding per operation, in the order written, IEEE division and square root; normalized() is
+ *   src/vec3.rs:37-44 (a length below 1e-4 is left alone); camera_raw(cam, u, v) = forward + (right * ((2u - 1) * half_width) +
+ *   true_up * ((1 - 2v) * half_height)) (src/camera.rs:33-42).
+ *   u, v:       u = ((float)x + f(w[0])) / (float)width,  v = ((float)y + f(w[1])) / (float)height   (src/renderer.rs:96-99).
+ *               With MI355RT_VIEW_CENTRE both jitters are 0.5 and the lens point is (a, b) = (0, 0): the ray through the pixel centre, the ray of
+ *               mi355rt_context_first_hits.  Fed to mi355rt_context_trace_rays it gives the first-hit records the denoiser needs for a view.
+ *   PINHOLE:    origin = position;  direction = normalized(camera_raw(cam, u, v)).
+ *   THIN LENS:  the lens point (a, b) comes from rejection in the unit disk: try j = 0, 1, ... takes a = 2 f(w2) - 1, b = 2 f(w3) - 1 from the words
+ *               2 / 3 of (ray 0, block j) -- the render never draws the blocks >= 1 of ray 0 -- and is accepted on a*a + b*b < 1.  After 64 rejected
+ *               tries (a, b) = (0, 0): the work per item is bounded.  off = right * (lens_radius * a) + true_up * (lens_radius * b);
+ *               origin = position + off;  direction = normalized(camera_raw(cam, u, v) * focus_distance - off).
+ *   mi355rt_context_view_rays writes these rays for one sample index: width * height mi355rt_path_ray records {origin, x, direction, row = y}.
+ *   mi355rt_context_render_view IS, by definition, mi355rt_context_trace_radiance along the rays of view_rays(sample = s) for every s in
+ *   [params.sample_begin, params.sample_end): the query normalises the direction once more (Ray::new -- the render's double normalisation), the
+ *   same fold, the same sums in sample order continuing from d_accum (read only when sample_begin > 0, always written), the same
+ *   d_out_linear = sum * (1.0f / (float)sample_end); calls that cover 0 .. N in any chunking give the words of one call.  d_out_packed, if given,
+ *   receives width * height words 0x00RRGGBB of the mean, as the render packs a pixel (sqrt, clamp, * 255, truncate: src/color.rs:87-93).
+ * CONSEQUENCE.  A pinhole view with the camera and the size of set_scene gives mi355rt_context_render's images (MI355RT_RNG_CTR, the same seed)
+ *   bit for bit.
+ * SCRATCH is the caller's: mi355rt_view_scratch_bytes(view, sample_end - sample_begin) bytes, 16-byte aligned -- 12 bytes per (pixel, sample),
+ *   rounded up to a multiple of 16.
+ * REFUSALS, all decided before any HIP call, MI355RT_ERR_INVALID with a text that names the argument: a null view, an unknown model, width or
+ *   height 0, unknown flags, non-zero reserved words, a camera field that is not finite, a thin lens whose lens_radius is negative or not finite or
+ *   whose focus_distance is not positive and finite, a non-zero lens field on a pinhole, width * height * samples >= 2^32 (split the
+ *   call); a null or misaligned d_rays (16 bytes); everything mi355rt_context_trace_radiance refuses about its params and pointers (d_accum and
+ *   d_scratch 16 bytes, d_out_linear and d_out_packed 4 bytes); a null context, a context without a scene.  There is no host-buffer form: a view
+ *   is only worth having on a resident scene.
+ * PROTOCOL of the ray queries: the calls read the resident scene only, touch no workspace of the context, only enqueue, and may run on another
+ *   stream beside a render of the same context. */
+#define MI355RT_VIEW_PINHOLE   0u
+#define MI355RT_VIEW_THIN_LENS 1u
+#define MI355RT_VIEW_CENTRE    1u     /* mi355rt_view.flags */
+typedef struct mi355rt_view {          /* 96 bytes */
+    mi355rt_camera camera;             /* exactly what mi355rt_context_set_scene takes */
+    uint32_t model;                    /* MI355RT_VIEW_PINHOLE | _THIN_LENS */
+    uint32_t width, height;            /* the view's own image size */
+    uint32_t flags;                    /* MI355RT_VIEW_CENTRE or 0 */
+    float    lens_radius;              /* thin lens: >= 0, finite; 0 otherwise */
+    float    focus_distance;           /* thin lens: > 0, finite; 0 otherwise */
+    uint32_t reserved[4];              /* must be 0 */
+} mi355rt_view;
+/* samples = sample_end - sample_begin of the render_view call */
+int  mi355rt_view_scratch_bytes(const mi355rt_view* view, uint32_t samples, uint64_t* out_bytes);
+/* DEVICE pointers; both enqueue on hip_stream (NULL = default stream) and return.  d_rays: width * height mi355rt_path_ray. */
+int  mi355rt_context_view_rays(mi355rt_context* ctx, const mi355rt_view* view, uint32_t sample, uint64_t seed, void* d_rays, void* hip_stream);
+/* d_accum: width * height float4; d_out_linear: width * height * 3 floats; d_out_packed: width * height uint32. */
+int  mi355rt_context_render_view(mi355rt_context* ctx, const mi355rt_view* view, const mi355rt_radiance_params* params,
+                                 void* d_accum, void* d_out_linear_or_null, void* d_out_packed_or_null, void* d_scratch, void* hip_stream);
 
 /* ---- denoising a preview: an edge-avoiding a-trous filter guided by first-hit records (added within ABI version 5: probe for the symbols) ----
  * For the first chunks of a progressive render: the noisy linear image and the records of mi355rt_context_first_hits for the same rows go in,

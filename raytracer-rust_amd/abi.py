@@ -124,6 +124,22 @@ class RadianceParams(C.Structure):                        # mi355rt_radiance_par
         return cls(sample_begin, sample_end, max_depth, 0, seed, 0)
 
 
+VIEW_PINHOLE, VIEW_THIN_LENS = 0, 1
+VIEW_CENTRE = 1
+
+
+class View(C.Structure):                                  # mi355rt_view, 96 bytes
+    _fields_ = [("camera", Camera), ("model", u32), ("width", u32), ("height", u32), ("flags", u32), ("lens_radius", f32), ("focus_distance", f32),
+                ("reserved", u32 * 4)]
+
+    @classmethod
+    def make(cls, camera, width, height, model=VIEW_PINHOLE, flags=0, lens_radius=0.0, focus_distance=0.0):
+        v = cls()
+        C.memmove(C.byref(v.camera), C.byref(camera), C.sizeof(Camera))
+        v.model, v.width, v.height, v.flags, v.lens_radius, v.focus_distance = model, width, height, flags, lens_radius, focus_distance
+        return v
+
+
 class AoParams(C.Structure):                             # mi355rt_ao_params, 16 bytes
     _fields_ = [("samples", u32), ("seed", u32), ("radius", f32), ("_pad", u32)]
 

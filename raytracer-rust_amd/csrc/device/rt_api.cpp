@@ -27,6 +27,7 @@
 #include "rt_denoise.h"
 #include "rt_occlusion.h"
 #include "rt_radiance.h"
+#include "rt_view.h"
 
 using namespace mi355rt;
 
@@ -724,6 +725,47 @@ int mi355rt::context_trace_radiance(mi355rt_context* ctx, const mi355rt_radiance
     s.scratch = (const float*)d_scratch; s.accum = (float*)d_accum; s.out_linear = (float*)d_out_linear; s.n_rays = n_rays; s.samples = plan.samples;
     s.accum_load = plan.accum_load; s.inv_total = plan.inv_total;
     if (launch_radiance(p, s, ctx->has_mesh, plan.grid_paths, plan.grid_sum, hip_stream) != 0) return fail(MI355RT_ERR_HIP, "k_radiance launch failed");
+    return MI355RT_OK;
+}
+
+// ---- camera views (rt_view.hip): the rays of a pinhole or a thin lens made on the device, in front of the radiance queries' loop ----
+// The context halves of mi355rt_context_view_rays / mi355rt_context_render_view, whose entry points stand with their kernels in rt_view.hip, behind
+// the barrier.  The protocol of the ray queries; every refusal and the grids are rt_prepare.cpp's (plan_view_rays, plan_view), before any HIP call.
+static void view_params(const mi355rt_view* view, const ViewPlan& plan, ViewParams& v) {
+    static_assert(sizeof(DevCamera) == sizeof(mi355rt_camera) && sizeof(mi355rt_view) == 96 && sizeof(mi355rt_view) % 16 == 0, "a view carries set_scene's camera");
+    std::memcpy(&v.cam, &view->camera, sizeof v.cam);
+    v.width_f = (float)view->width; v.height_f = (float)view->height; v.width = view->width; v.centre = plan.centre;
+    v.lens_radius = view->lens_radius; v.focus_distance = view->focus_distance;
+}
+int mi355rt::context_view_rays(mi355rt_context* ctx, const mi355rt_view* view, uint32_t sample, uint64_t seed, void* d_rays, void* hip_stream) {
+    ViewPlan plan{};
+    if (int rc = plan_view_rays(ctx != nullptr, ctx && ctx->have_scene, view, d_rays, plan)) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (int erc = report_device_error(ctx)) return erc;              // an earlier asynchronous render on this context failed
+    ViewParams v{}; view_params(view, plan, v);
+    ViewRays r{};
+    r.rays = d_rays; r.n_pixels = plan.n_pixels; r.sample = sample; r.seed_lo = (uint32_t)seed; r.seed_hi = (uint32_t)(seed >> 32);
+    if (launch_view_rays(v, r, view->model, hip_stream) != 0) return fail(MI355RT_ERR_HIP, "k_view_rays launch failed");
+    return MI355RT_OK;
+}
+int mi355rt::context_render_view(mi355rt_context* ctx, const mi355rt_view* view, const mi355rt_radiance_params* params, void* d_accum, void* d_out_linear,
+                                 void* d_out_packed, void* d_scratch, void* hip_stream) {
+    ViewPlan plan{};
+    if (int rc = plan_view(ctx != nullptr, ctx && ctx->have_scene, view, params, d_accum, d_out_linear, d_out_packed, d_scratch,
+                           ctx ? (uint32_t)ctx->knob_radiance_items : 0u, RADIANCE_ITEMS_DEFAULT, plan)) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (int erc = report_device_error(ctx)) return erc;              // an earlier asynchronous render on this context failed
+    RadianceParams p{};
+    p.prims = ctx->prims.p; p.mats = ctx->mats.p; p.nodes = ctx->nodes.p; p.tris = ctx->tris.p; p.n_prims = ctx->n_prims;
+    p.sky = ctx->sky_w ? ctx->sky.p : nullptr; p.sky_w = ctx->sky_w; p.sky_h = ctx->sky_h; p.textures = ctx->textures.p;
+    std::memcpy(p.miss, ctx->miss, sizeof p.miss);
+    p.rays = nullptr; p.scratch = (float*)d_scratch; p.n_items = plan.r.n_items; p.samples = plan.r.samples; p.sample_begin = params->sample_begin;
+    p.max_depth = params->max_depth; p.items_per_lane = plan.r.items_per_lane; p.seed_lo = plan.r.seed_lo; p.seed_hi = plan.r.seed_hi;
+    ViewParams v{}; view_params(view, plan, v);
+    ViewSum s{};
+    s.sum.scratch = (const float*)d_scratch; s.sum.accum = (float*)d_accum; s.sum.out_linear = (float*)d_out_linear; s.sum.n_rays = plan.n_pixels;
+    s.sum.samples = plan.r.samples; s.sum.accum_load = plan.r.accum_load; s.sum.inv_total = plan.r.inv_total; s.out_packed = (uint32_t*)d_out_packed;
+    if (launch_view_paths(p, v, s, view->model, ctx->has_mesh, plan.r.grid_paths, plan.r.grid_sum, hip_stream) != 0) return fail(MI355RT_ERR_HIP, "k_view launch failed");
     return MI355RT_OK;
 }
 extern "C" {

@@ -132,44 +132,112 @@ int plan_ambient_occlusion(bool have_ctx, bool have_scene, const mi355rt_setting
     return MI355RT_OK;
 }
 
+// The radiance query's plan for `who` ("trace_radiance"; "render_view": the views run the same loop over made rays -- with_rays false, `rays` not looked at).
+static int radiance_items_bytes(const char* who, const char* what, uint64_t n_rays, uint32_t samples, uint64_t* out_bytes) {
+    if (!out_bytes) return fail(MI355RT_ERR_INVALID, std::string(who) + ": out_bytes is null");
+    if (n_rays >= (1ull << 32) || n_rays * samples >= (1ull << 32)) return fail(MI355RT_ERR_INVALID, std::string(who) + ": " + what + " must stay below 2^32 (split the call)");
+    *out_bytes = (n_rays * samples * 12u + 15u) & ~15ull;         // (n_rays < 2^32 is tested first, so the product of two 32-bit numbers does not wrap)
+    return MI355RT_OK;
+}
+
 int radiance_scratch_bytes(uint32_t n_rays, uint32_t samples, uint64_t* out_bytes) {
-    if (!out_bytes) return fail(MI355RT_ERR_INVALID, "trace_radiance: out_bytes is null");
-    const uint64_t items = (uint64_t)n_rays * samples;
-    if (items >= (1ull << 32)) return fail(MI355RT_ERR_INVALID, "trace_radiance: n_rays * samples must stay below 2^32 (split the call)");
-    *out_bytes = (items * 12u + 15u) & ~15ull;
+    return radiance_items_bytes("trace_radiance", "n_rays * samples", n_rays, samples, out_bytes);
+}
+
+static int plan_radiance_for(const char* who, const char* what, bool with_rays, bool have_ctx, bool have_scene, const mi355rt_radiance_params* params, const void* rays,
+                             uint64_t n_rays, const void* accum, const void* out_linear, const void* out_packed, const void* scratch, uint32_t items_knob,
+                             uint32_t default_items, RadiancePlan& plan) {
+    const auto bad = [who](const char* text) { return fail(MI355RT_ERR_INVALID, std::string(who) + ": " + text); };
+    if (!params) return bad("params is null");
+    if (params->flags != 0u) return bad("params.flags must be 0");
+    if (params->reserved != 0u) return bad("params.reserved must be 0");
+    if (params->sample_begin >= params->sample_end) return bad("params.sample_begin must be below params.sample_end");
+    plan = RadiancePlan{};
+    plan.samples = params->sample_end - params->sample_begin;
+    if (n_rays != 0u) {
+        if (with_rays && !rays) return bad("d_rays is null");
+        if (!accum) return bad("d_accum is null");
+        if (!scratch) return bad("d_scratch is null");
+        if (with_rays && misaligned_to(rays, 16)) return bad("d_rays must be 16-byte aligned");
+        if (misaligned_to(accum, 16)) return bad("d_accum must be 16-byte aligned");
+        if (misaligned_to(scratch, 16)) return bad("d_scratch must be 16-byte aligned");
+        if (misaligned_to(out_linear, 4)) return bad("d_out_linear must be 4-byte aligned");
+        if (misaligned_to(out_packed, 4)) return bad("d_out_packed must be 4-byte aligned");
+        if (int rc = radiance_items_bytes(who, what, n_rays, plan.samples, &plan.scratch_bytes)) return rc;
+    }
+    if (!have_ctx) return bad("ctx is null");
+    if (!have_scene) return bad("context has no scene");
+    const uint32_t k = items_knob ? items_knob : default_items;
+    if (k == 0u || k > RADIANCE_PLAN_ITEMS_MAX) return bad("items per lane out of range");
+    plan.n_items = (uint32_t)n_rays * plan.samples;                  // (< 2^32: checked above)
+    plan.items_per_lane = k;
+    const uint64_t per_block = (uint64_t)RADIANCE_PLAN_BLOCK * k;
+    plan.grid_paths = (uint32_t)(((uint64_t)plan.n_items + per_block - 1u) / per_block);
+    plan.grid_sum = (uint32_t)((n_rays + RADIANCE_PLAN_BLOCK / 16u - 1u) / (RADIANCE_PLAN_BLOCK / 16u));
+    plan.seed_lo = (uint32_t)params->seed; plan.seed_hi = (uint32_t)(params->seed >> 32);
+    plan.accum_load = params->sample_begin > 0u ? 1u : 0u;
+    plan.inv_total = 1.0f / (float)params->sample_end;               // renderer.rs:85
     return MI355RT_OK;
 }
 
 int plan_radiance(bool have_ctx, bool have_scene, const mi355rt_radiance_params* params, const void* rays, uint32_t n_rays, const void* accum,
                   const void* out_linear, const void* scratch, uint32_t items_knob, uint32_t default_items, RadiancePlan& plan) {
-    if (!params) return fail(MI355RT_ERR_INVALID, "trace_radiance: params is null");
-    if (params->flags != 0u) return fail(MI355RT_ERR_INVALID, "trace_radiance: params.flags must be 0");
-    if (params->reserved != 0u) return fail(MI355RT_ERR_INVALID, "trace_radiance: params.reserved must be 0");
-    if (params->sample_begin >= params->sample_end) return fail(MI355RT_ERR_INVALID, "trace_radiance: params.sample_begin must be below params.sample_end");
-    plan = RadiancePlan{};
-    plan.samples = params->sample_end - params->sample_begin;
-    if (n_rays != 0u) {
-        if (!rays) return fail(MI355RT_ERR_INVALID, "trace_radiance: d_rays is null");
-        if (!accum) return fail(MI355RT_ERR_INVALID, "trace_radiance: d_accum is null");
-        if (!scratch) return fail(MI355RT_ERR_INVALID, "trace_radiance: d_scratch is null");
-        if (misaligned_to(rays, 16)) return fail(MI355RT_ERR_INVALID, "trace_radiance: d_rays must be 16-byte aligned");
-        if (misaligned_to(accum, 16)) return fail(MI355RT_ERR_INVALID, "trace_radiance: d_accum must be 16-byte aligned");
-        if (misaligned_to(scratch, 16)) return fail(MI355RT_ERR_INVALID, "trace_radiance: d_scratch must be 16-byte aligned");
-        if (misaligned_to(out_linear, 4)) return fail(MI355RT_ERR_INVALID, "trace_radiance: d_out_linear must be 4-byte aligned");
-        if (int rc = radiance_scratch_bytes(n_rays, plan.samples, &plan.scratch_bytes)) return rc;
+    return plan_radiance_for("trace_radiance", "n_rays * samples", true, have_ctx, have_scene, params, rays, n_rays, accum, out_linear, nullptr, scratch, items_knob,
+                             default_items, plan);
+}
+
+// What a view itself can be refused for: everything but the buffers and the size of the call.
+static int check_view(const char* who, const mi355rt_view* v) {
+    const auto bad = [who](const char* text) { return fail(MI355RT_ERR_INVALID, std::string(who) + ": " + text); };
+    if (!v) return bad("view is null");
+    if (v->model != MI355RT_VIEW_PINHOLE && v->model != MI355RT_VIEW_THIN_LENS) return bad("view.model is unknown");
+    if (v->width == 0u) return bad("view.width is 0");
+    if (v->height == 0u) return bad("view.height is 0");
+    if ((v->flags & ~MI355RT_VIEW_CENTRE) != 0u) return bad("view.flags has unknown bits");
+    for (uint32_t r : v->reserved) if (r != 0u) return bad("view.reserved must be 0");
+    const mi355rt_camera& c = v->camera;
+    for (int i = 0; i < 3; ++i)
+        if (!std::isfinite(c.position[i]) || !std::isfinite(c.forward[i]) || !std::isfinite(c.right[i]) || !std::isfinite(c.true_up[i])) return bad("view.camera must be finite");
+    if (!std::isfinite(c.half_width) || !std::isfinite(c.half_height)) return bad("view.camera must be finite");
+    if (v->model == MI355RT_VIEW_THIN_LENS) {
+        if (!std::isfinite(v->lens_radius) || v->lens_radius < 0.0f) return bad("view.lens_radius must be finite and not negative");
+        if (!std::isfinite(v->focus_distance) || !(v->focus_distance > 0.0f)) return bad("view.focus_distance must be finite and positive");
+    } else {
+        if (v->lens_radius != 0.0f) return bad("view.lens_radius must be 0 unless the model is the thin lens");       // (NaN != 0: refused too)
+        if (v->focus_distance != 0.0f) return bad("view.focus_distance must be 0 unless the model is the thin lens");
     }
-    if (!have_ctx) return fail(MI355RT_ERR_INVALID, "trace_radiance: ctx is null");
-    if (!have_scene) return fail(MI355RT_ERR_INVALID, "trace_radiance: context has no scene");
-    const uint32_t k = items_knob ? items_knob : default_items;
-    if (k == 0u || k > RADIANCE_PLAN_ITEMS_MAX) return fail(MI355RT_ERR_INVALID, "trace_radiance: items per lane out of range");
-    plan.n_items = n_rays * plan.samples;                            // (< 2^32: checked above)
-    plan.items_per_lane = k;
-    const uint64_t per_block = (uint64_t)RADIANCE_PLAN_BLOCK * k;
-    plan.grid_paths = (uint32_t)(((uint64_t)plan.n_items + per_block - 1u) / per_block);
-    plan.grid_sum = (uint32_t)(((uint64_t)n_rays + RADIANCE_PLAN_BLOCK / 16u - 1u) / (RADIANCE_PLAN_BLOCK / 16u));
-    plan.seed_lo = (uint32_t)params->seed; plan.seed_hi = (uint32_t)(params->seed >> 32);
-    plan.accum_load = params->sample_begin > 0u ? 1u : 0u;
-    plan.inv_total = 1.0f / (float)params->sample_end;               // renderer.rs:85
+    return MI355RT_OK;
+}
+
+int view_scratch_bytes(const mi355rt_view* view, uint32_t samples, uint64_t* out_bytes) {
+    if (!out_bytes) return fail(MI355RT_ERR_INVALID, "view_scratch_bytes: out_bytes is null");
+    if (int rc = check_view("view_scratch_bytes", view)) return rc;
+    return radiance_items_bytes("view_scratch_bytes", "view.width * view.height * samples", (uint64_t)view->width * view->height, samples, out_bytes);
+}
+
+int plan_view_rays(bool have_ctx, bool have_scene, const mi355rt_view* view, const void* rays, ViewPlan& plan) {
+    if (int rc = check_view("view_rays", view)) return rc;
+    plan = ViewPlan{};
+    if (!rays) return fail(MI355RT_ERR_INVALID, "view_rays: d_rays is null");
+    if (misaligned_to(rays, 16)) return fail(MI355RT_ERR_INVALID, "view_rays: d_rays must be 16-byte aligned");
+    const uint64_t pixels = (uint64_t)view->width * view->height;
+    if (pixels >= (1ull << 32)) return fail(MI355RT_ERR_INVALID, "view_rays: view.width * view.height must stay below 2^32 (split the call)");
+    if (!have_ctx) return fail(MI355RT_ERR_INVALID, "view_rays: ctx is null");
+    if (!have_scene) return fail(MI355RT_ERR_INVALID, "view_rays: context has no scene");
+    plan.n_pixels = plan.r.n_items = (uint32_t)pixels; plan.r.samples = 1u;   // (launch_view_rays cuts its own grid: one lane per pixel)
+    plan.centre = view->flags & MI355RT_VIEW_CENTRE;
+    return MI355RT_OK;
+}
+
+int plan_view(bool have_ctx, bool have_scene, const mi355rt_view* view, const mi355rt_radiance_params* params, const void* accum, const void* out_linear,
+              const void* out_packed, const void* scratch, uint32_t items_knob, uint32_t default_items, ViewPlan& plan) {
+    if (int rc = check_view("render_view", view)) return rc;
+    plan = ViewPlan{};
+    const uint64_t pixels = (uint64_t)view->width * view->height;    // (> 0: check_view)
+    if (int rc = plan_radiance_for("render_view", "view.width * view.height * samples", false, have_ctx, have_scene, params, nullptr, pixels, accum, out_linear,
+                                   out_packed, scratch, items_knob, default_items, plan.r)) return rc;
+    plan.n_pixels = (uint32_t)pixels;
+    plan.centre = view->flags & MI355RT_VIEW_CENTRE;
     return MI355RT_OK;
 }
 

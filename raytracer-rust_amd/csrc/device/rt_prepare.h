@@ -82,6 +82,20 @@ int radiance_scratch_bytes(uint32_t n_rays, uint32_t samples, uint64_t* out_byte
 int plan_radiance(bool have_ctx, bool have_scene, const mi355rt_radiance_params* params, const void* rays, uint32_t n_rays, const void* accum,
                   const void* out_linear_or_null, const void* scratch, uint32_t items_knob, uint32_t default_items, RadiancePlan& plan);
 
+// The camera views (mi355rt.h, mi355rt_context_view_rays / mi355rt_context_render_view): every refusal, the scratch size and the grids,
+// decided before any HIP call.  Refusals in this order (MI355RT_ERR_INVALID and a text that names the argument): the view -- null, model, width /
+// height 0, flags, reserved, a camera field that is not finite, the lens fields --; then for view_rays d_rays (null, 16 bytes) and width * height >= 2^32,
+// for render_view everything plan_radiance refuses about the params and the pointers, d_out_packed off 4 bytes and width * height * samples >= 2^32;
+// then the context and its scene.
+struct ViewPlan {
+    RadiancePlan r;                                                  // of width * height "rays"; view_rays: n_items = the pixels, no grids
+    uint32_t n_pixels, centre;                                       // width * height; MI355RT_VIEW_CENTRE set
+};
+int view_scratch_bytes(const mi355rt_view* view, uint32_t samples, uint64_t* out_bytes);
+int plan_view_rays(bool have_ctx, bool have_scene, const mi355rt_view* view, const void* rays, ViewPlan& plan);
+int plan_view(bool have_ctx, bool have_scene, const mi355rt_view* view, const mi355rt_radiance_params* params, const void* accum, const void* out_linear_or_null,
+              const void* out_packed_or_null, const void* scratch, uint32_t items_knob, uint32_t default_items, ViewPlan& plan);
+
 // The render call (mi355rt_context_render / mi355rt_context_render_progressive): every refusal, the variant that is launched, the
 // bands the radiance workspace is cycled through and the geometry of each band's launch, decided before any HIP call.
 // q = n / d for every n < 2^31 as umulhi(n, mul) >> shift (mul == 0 encodes d == 1).

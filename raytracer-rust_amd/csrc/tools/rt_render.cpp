@@ -5,6 +5,7 @@
 //   rt_render <scene.json> [-o out.png] [--width W] [--height H] [--spp N] [--max-depth D]
 //             [--rng ctr|ref] [--seed S] [--skip-unknown] [--chunk N] [--pfm out.pfm] [--exr out.exr] [--gpus N | --devices a,b,..]
 //             [--denoise-out denoised.png]
+//             [--view-position x,y,z --view-target x,y,z [--view-fov deg] [--lens-radius r --focus-distance d]]
 //             [--noise-target T [--noise-floor F] [--noise-allow FRACTION] [--min-chunks K] [--max-spp N] [--noise-out map.pfm] [--noise-device]]
 // --fix-aabb / --fix-wo3 switch on the two opt-in fixes (MI355RT_FLAG_FIXED_AABB, wo3_four_index_stride): not the reference's image.
 // --gpus N deals row strips over HIP devices 0..N-1 from this one process (mi355rt_render_multi); --devices a,b,... names them
@@ -21,6 +22,12 @@
 // reports the stop (R >= S: what the device traced, the speculative chunk included; kernel_ms covers all of R).
 // --noise-device (only with --noise-target) takes the estimate on the device, beside the running sums (mi355rt_noise_device_*): the same images,
 // the same map and the same verdict, mean= equal up to the rounding of another order of summation; no copy of the sums leaves the device.
+// --view-position x,y,z --view-target x,y,z renders the loaded scene through a VIEW (mi355rt_context_render_view) after set_scene with the scene's own
+// camera: a pinhole at that position looking at that target (world up 0,1,0; Camera::new, src/camera.rs:14-31), with the scene's own field of view
+// or --view-fov degrees at the aspect width / height; --lens-radius r --focus-distance d make it a thin lens.  The image
+// keeps the scene's size, samples, depth and seed.  With the scene's own pose the PNG is the plain run's, byte for byte.  One GPU, the counter-mode
+// generator, no --chunk, --denoise-out or --noise-target.  With no view option nothing the tool does changes.
+#include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <limits>
@@ -72,6 +79,76 @@ static int denoise_image(int hip_device, const mi355rt_scene* sc, const mi355rt_
 //   mi355rt_noise_device_evaluate into the pinned summary [k & 1] (and the device error map [k & 1] with --noise-out);  event F_k
 //   host:           enqueue chunk k + 1 first, as above, then wait F_k and read the 56 bytes.
 // P_k .. F_k (timing events) bracket the estimate's kernels of chunk k: their sum over the chunks k >= 2 is the `noise device:` line.
+// --view-*: the scene through a view.  out_packed[width * height], out_linear_or_null[width * height * 3].  0, or 1 with the failure on stderr.
+// The samples go in chunks of at most 2^26 (pixel, sample) pairs -- any chunking of 0 .. N gives the words of one call --, so the scratch stays below 1 GB.
+static int render_through_view(int hip_device, const mi355rt_scene* sc, const mi355rt_camera* cam, const mi355rt_settings* st, const mi355rt_options* opt,
+                               const mi355rt_view* view, uint32_t* out_packed, float* out_linear_or_null, double* kernel_ms) {
+    const size_t n = (size_t)view->width * view->height;
+    const uint32_t spp = st->samples_per_pixel;
+    const uint32_t chunk = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(spp, (1ull << 26) / n));
+    uint64_t scratch_bytes = 0;
+    mi355rt_context* ctx = nullptr;
+    void *d_accum = nullptr, *d_lin = nullptr, *d_scratch = nullptr, *d_packed = nullptr;
+    const char* what = nullptr;
+    int rc = mi355rt_view_scratch_bytes(view, chunk, &scratch_bytes);
+    if (!rc) rc = mi355rt_context_create(hip_device, &ctx);
+    if (!rc && hipSetDevice(hip_device) != hipSuccess) what = "hipSetDevice";
+    if (!rc && !what) rc = mi355rt_context_set_scene(ctx, sc, cam, st);
+    if (!rc && !what && (hipMalloc(&d_accum, n * 16) != hipSuccess || hipMalloc(&d_lin, n * 12) != hipSuccess || hipMalloc(&d_scratch, scratch_bytes) != hipSuccess ||
+                         hipMalloc(&d_packed, n * 4) != hipSuccess)) what = "hipMalloc";
+    hipEvent_t e0 = nullptr, e1 = nullptr;                                          // device time of all the chunks' kernels
+    if (!rc && !what && (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess || hipEventRecord(e0, nullptr) != hipSuccess)) what = "hipEvent";
+    for (uint32_t s = 0; !rc && !what && s < spp; s += chunk) {
+        const mi355rt_radiance_params prm = {s, std::min(spp, s + chunk), st->max_depth, 0u, opt->seed, 0ull};
+        rc = mi355rt_context_render_view(ctx, view, &prm, d_accum, d_lin, d_packed, d_scratch, nullptr);
+    }
+    float ms = 0.0f;
+    if (!rc && !what && (hipEventRecord(e1, nullptr) != hipSuccess || hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess)) what = "hipEvent";
+    *kernel_ms = ms;
+    if (!rc && !what && hipMemcpy(out_packed, d_packed, n * 4, hipMemcpyDeviceToHost) != hipSuccess) what = "copy back";
+    if (!rc && !what && out_linear_or_null && hipMemcpy(out_linear_or_null, d_lin, n * 12, hipMemcpyDeviceToHost) != hipSuccess) what = "copy back";
+    if (!rc && !what) rc = mi355rt_context_check(ctx);
+    if (rc) std::fprintf(stderr, "render_view failed (%d): %s\n", rc, mi355rt_last_error());
+    else if (what) std::fprintf(stderr, "render_view failed: %s\n", what);
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    (void)hipFree(d_accum); (void)hipFree(d_lin); (void)hipFree(d_scratch); (void)hipFree(d_packed);
+    if (ctx) mi355rt_context_destroy(ctx);
+    return (rc || what) ? 1 : 0;
+}
+
+// Camera::new (src/camera.rs:14-31) as the scene loader states it (csrc/host/scene_loader.cpp, camera_new): float32, one rounding per operation, the
+// tangent correctly rounded through double.  fov_deg < 0: keep half_width / half_height of `own`.
+static mi355rt_camera view_camera(const float (&pos)[3], const float (&at)[3], float fov_deg, float aspect, const mi355rt_camera& own) {
+    struct V { float x, y, z; };
+    const auto norm = [](V a) { const float l = std::sqrt(a.x * a.x + a.y * a.y + a.z * a.z); if (l < 1e-4f) return a; const float r = 1.0f / l; return V{a.x * r, a.y * r, a.z * r}; };
+    const auto cross = [](V a, V b) { return V{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; };
+    const V forward = norm(V{at[0] - pos[0], at[1] - pos[1], at[2] - pos[2]});
+    const V right = norm(cross(forward, norm(V{0.0f, 1.0f, 0.0f})));
+    const V up = norm(cross(right, forward));
+    mi355rt_camera c = own;
+    c.position[0] = pos[0]; c.position[1] = pos[1]; c.position[2] = pos[2];
+    c.forward[0] = forward.x; c.forward[1] = forward.y; c.forward[2] = forward.z;
+    c.right[0] = right.x; c.right[1] = right.y; c.right[2] = right.z;
+    c.true_up[0] = up.x; c.true_up[1] = up.y; c.true_up[2] = up.z;
+    if (fov_deg >= 0.0f) {
+        const float fov_rad = fov_deg * 3.14159265358979323846f / 180.0f;
+        c.half_height = (float)std::tan((double)(fov_rad / 2.0f));
+        c.half_width = c.half_height * aspect;
+    }
+    return c;
+}
+
+static bool parse_xyz(const char* s, float (&out)[3]) {
+    for (int k = 0; k < 3; ++k) {
+        char* e = nullptr;
+        out[k] = (float)std::strtod(s, &e);
+        if (e == s || *e != (k < 2 ? ',' : '\0')) return false;
+        s = e + 1;
+    }
+    return true;
+}
+
 struct ConvergeArgs { uint32_t chunk, max_spp; mi355rt_noise_params params; std::string noise_out; bool on_device; };
 struct ConvergeResult { mi355rt_noise_summary summary; uint32_t rendered; double wall_ms, render_ms, resolve_ms, update_ms, evaluate_ms, pass_ms; uint32_t passes; };
 
@@ -209,6 +286,7 @@ static int render_converging(int hip_device, const mi355rt_scene* sc, const mi35
 }
 
 static const char USAGE[] = "usage: %s <scene.json> [-o out.png] [--width W] [--height H] [--spp N] [--max-depth D] [--rng ctr|ref] [--seed S] [--skip-unknown] [--chunk N] [--pfm out.pfm] [--exr out.exr] [--gpus N | --devices a,b,..] [--fix-aabb] [--fix-wo3] [--denoise-out denoised.png]"
+                            " [--view-position x,y,z --view-target x,y,z [--view-fov deg] [--lens-radius r --focus-distance d]]"
                             " [--noise-target T [--noise-floor F] [--noise-allow FRACTION] [--min-chunks K] [--max-spp N] [--noise-out map.pfm] [--noise-device]]\n";
 
 int main(int argc, char** argv) {
@@ -217,6 +295,8 @@ int main(int argc, char** argv) {
     mi355rt_load_overrides ov{}; mi355rt_options opt{}; uint32_t chunk = 0, gpus = 1; std::vector<int> device_list;
     opt.abi_version = MI355RT_ABI_VERSION; opt.rng_mode = MI355RT_RNG_CTR; opt.strip_rows = 1; opt.n_parts = 1;
     ConvergeArgs cv{}; cv.params = {0.02, 0.01, 4u, 0u, 0ull};                          // the library's defaults
+    float view_pos[3] = {}, view_at[3] = {}, view_fov = -1.0f, lens_radius = 0.0f, focus_distance = 0.0f;
+    bool have_view_pos = false, have_view_at = false, view_option = false, have_lens = false, have_focus = false;
     bool noise = false, noise_option = false, noise_device = false, multi_option = false; double noise_allow = 0.0;
     auto usage = [&](const char* why) { std::fprintf(stderr, USAGE, argv[0]); std::fprintf(stderr, "%s\n", why); return 2; };
     for (int i = 2; i < argc; ++i) {
@@ -247,6 +327,11 @@ int main(int argc, char** argv) {
                                                 device_list.push_back((int)d); q = (*e == ',') ? e + 1 : e; if (*e && *e != ',') { std::fprintf(stderr, "--devices wants a comma-separated list of device numbers\n"); return 2; } }
             gpus = (uint32_t)device_list.size();
         }
+        else if (!std::strcmp(argv[i], "--view-position")) { if (!parse_xyz(next(), view_pos)) return usage("--view-position wants x,y,z"); have_view_pos = true; }
+        else if (!std::strcmp(argv[i], "--view-target")) { if (!parse_xyz(next(), view_at)) return usage("--view-target wants x,y,z"); have_view_at = true; }
+        else if (!std::strcmp(argv[i], "--view-fov")) { view_fov = (float)std::atof(next()); view_option = true; if (!(view_fov > 0.0f && view_fov < 180.0f)) return usage("--view-fov wants degrees, 0 .. 180"); }
+        else if (!std::strcmp(argv[i], "--lens-radius")) { lens_radius = (float)std::atof(next()); view_option = have_lens = true; }
+        else if (!std::strcmp(argv[i], "--focus-distance")) { focus_distance = (float)std::atof(next()); view_option = have_focus = true; }
         else if (!std::strcmp(argv[i], "--fix-aabb")) opt.flags |= MI355RT_FLAG_FIXED_AABB;
         else if (!std::strcmp(argv[i], "--fix-wo3")) ov.wo3_four_index_stride = 1;
         else { std::fprintf(stderr, "unknown option %s\n", argv[i]); return 2; }
@@ -265,6 +350,13 @@ int main(int argc, char** argv) {
         if (!(cv.params.floor >= 0.0) || !(cv.params.floor < 1e300)) return usage("--noise-floor wants a number >= 0");
         if (cv.params.min_chunks < 2) return usage("--min-chunks wants at least 2: one chunk has no spread");
         cv.chunk = chunk ? chunk : 16;
+    }
+    const bool through_view = have_view_pos || have_view_at;
+    if (have_view_pos != have_view_at || (view_option && !through_view)) return usage("a view needs both --view-position and --view-target; --view-fov, --lens-radius and --focus-distance go with them");
+    if (through_view) {
+        if (have_lens != have_focus) return usage("--lens-radius and --focus-distance go together");
+        if (multi_option || chunk || noise || !denoise_path.empty() || opt.rng_mode == MI355RT_RNG_REF || opt.flags)
+            return usage("a view renders on one GPU with the counter-mode generator: it cannot be combined with --gpus, --devices, --chunk, --noise-target, --denoise-out, --rng ref or --fix-aabb");
     }
     const bool multi = gpus > 1 || !device_list.empty();
     if (multi && chunk) { std::fprintf(stderr, "--chunk (progressive preview) renders on one GPU: it cannot be combined with --gpus %u\n", gpus); return 2; }
@@ -307,7 +399,17 @@ int main(int argc, char** argv) {
         if (!cv.noise_out.empty()) std::printf("Noise map saved as '%s'\n", cv.noise_out.c_str());
         stats.samples = n_px * cr.rendered; stats.render_kernel_ms = cr.render_ms; stats.resolve_kernel_ms = cr.resolve_ms; stats.total_ms = cr.render_ms + cr.resolve_ms;
     }
-    int rc = noise ? MI355RT_OK : multi ? mi355rt_render_multi(sc, mi355rt_loaded_scene_camera(ls), st, &opt, devices.data(), gpus, buffer.data(), lin, &stats)
+    if (through_view) {
+        mi355rt_view view{};
+        view.camera = view_camera(view_pos, view_at, view_fov, (float)st->width / (float)st->height, *mi355rt_loaded_scene_camera(ls));
+        view.model = have_lens ? MI355RT_VIEW_THIN_LENS : MI355RT_VIEW_PINHOLE;
+        view.width = st->width; view.height = st->height; view.lens_radius = lens_radius; view.focus_distance = focus_distance;
+        double view_ms = 0.0;
+        if (render_through_view(devices[0], sc, mi355rt_loaded_scene_camera(ls), st, &opt, &view, buffer.data(), lin, &view_ms)) { mi355rt_scene_free(ls); return 1; }
+        // (the view's path and sum kernels together, by device events: it has no kernel of its own for the resolve, and counts no rays)
+        stats.samples = (uint64_t)st->width * st->height * st->samples_per_pixel; stats.render_kernel_ms = view_ms; stats.total_ms = view_ms;
+    }
+    int rc = (noise || through_view) ? MI355RT_OK : multi ? mi355rt_render_multi(sc, mi355rt_loaded_scene_camera(ls), st, &opt, devices.data(), gpus, buffer.data(), lin, &stats)
            : chunk ? mi355rt_render_progressive(sc, mi355rt_loaded_scene_camera(ls), st, &opt, chunk, on_chunk, &pv, buffer.data(), lin, &stats)
                    : mi355rt_render(sc, mi355rt_loaded_scene_camera(ls), st, &opt, buffer.data(), lin, &stats);   // <- src/main.rs:57
     if (rc != MI355RT_OK) { std::fprintf(stderr, "render failed (%d): %s\n", rc, mi355rt_last_error()); mi355rt_scene_free(ls); return 1; }

@@ -21,6 +21,7 @@ EXPORTS = ["mi355rt_render", "mi355rt_render_multi", "mi355rt_render_progressive
            "mi355rt_denoise_scratch_bytes", "mi355rt_context_denoise", "mi355rt_denoise",
            "mi355rt_context_occluded", "mi355rt_occluded", "mi355rt_context_ambient_occlusion",
            "mi355rt_radiance_scratch_bytes", "mi355rt_context_trace_radiance", "mi355rt_trace_radiance",
+           "mi355rt_view_scratch_bytes", "mi355rt_context_view_rays", "mi355rt_context_render_view",
            "mi355rt_noise_device_create", "mi355rt_noise_device_destroy", "mi355rt_noise_device_reset", "mi355rt_noise_device_update",
            "mi355rt_noise_device_evaluate"]
 
@@ -286,6 +287,12 @@ def _bind(so):
         L.mi355rt_context_trace_radiance.argtypes = [C.c_void_p, C.POINTER(abi.RadianceParams), C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.mi355rt_trace_radiance.restype = C.c_int
         L.mi355rt_trace_radiance.argtypes = [C.POINTER(abi.Scene), C.POINTER(abi.RadianceParams), C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+        L.mi355rt_view_scratch_bytes.restype = C.c_int
+        L.mi355rt_view_scratch_bytes.argtypes = [C.POINTER(abi.View), C.c_uint32, C.POINTER(C.c_uint64)]
+        L.mi355rt_context_view_rays.restype = C.c_int
+        L.mi355rt_context_view_rays.argtypes = [C.c_void_p, C.POINTER(abi.View), C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p]
+        L.mi355rt_context_render_view.restype = C.c_int
+        L.mi355rt_context_render_view.argtypes = [C.c_void_p, C.POINTER(abi.View), C.POINTER(abi.RadianceParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.mi355rt_noise_device_create.restype = C.c_int
         L.mi355rt_noise_device_create.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
         L.mi355rt_noise_device_destroy.restype = None
@@ -535,6 +542,14 @@ def radiance_scratch_bytes(n_rays, samples, library=None):
     return n.value
 
 
+def view_scratch_bytes(view, samples, library=None):
+    """mi355rt_view_scratch_bytes: the size of Context.render_view's d_scratch for `view` (abi.View) and samples = sample_end - sample_begin."""
+    L = library or lib()
+    n = C.c_uint64()
+    _check(L.mi355rt_view_scratch_bytes(C.byref(view) if view is not None else None, int(samples), C.byref(n)), "mi355rt_view_scratch_bytes", L)
+    return n.value
+
+
 def trace_radiance(scene, rays, params, accum=None, want_linear=True, library=None):
     """One-shot mi355rt_trace_radiance with host buffers: samples [params.sample_begin, params.sample_end) of a whole path along every ray of
     `scene`, added to the running sums.  rays: a numpy array of abi.PATH_RAY_DTYPE; params: abi.RadianceParams; accum: float32 [n, 4] sums of the
@@ -711,6 +726,22 @@ class Context:
         p = lambda a: C.c_void_p(a) if a else None
         _check(self._L.mi355rt_context_trace_radiance(self._h, C.byref(params) if params is not None else None, p(d_rays), int(n), p(d_accum),
                                                       p(d_out_linear), p(d_scratch), p(stream)), "mi355rt_context_trace_radiance", self._L)
+
+    def view_rays(self, view, sample, d_rays, seed=0, stream=None):
+        """mi355rt_context_view_rays: the rays of sample index `sample` of every pixel of `view` (abi.View), made on the device and written to d_rays
+        (integer device address, 16-byte aligned, view.width * view.height abi.PathRay records), enqueued on `stream`."""
+        p = lambda a: C.c_void_p(a) if a else None
+        _check(self._L.mi355rt_context_view_rays(self._h, C.byref(view) if view is not None else None, int(sample), int(seed), p(d_rays), p(stream)),
+               "mi355rt_context_view_rays", self._L)
+
+    def render_view(self, view, params, d_accum, d_scratch, d_out_linear=None, d_out_packed=None, stream=None):
+        """mi355rt_context_render_view: samples [params.sample_begin, params.sample_end) of every pixel of `view` (abi.View) of the resident scene,
+        the rays made on the device, enqueued on `stream`.  Integer device addresses: d_accum width * height float4 running sums (16-byte aligned; read
+        when sample_begin > 0, always written), d_scratch view_scratch_bytes(view, sample_end - sample_begin) bytes (16-byte aligned); d_out_linear:
+        width * height * 3 floats, sum / sample_end, or None; d_out_packed: width * height words 0x00RRGGBB, or None.  params: abi.RadianceParams."""
+        p = lambda a: C.c_void_p(a) if a else None
+        _check(self._L.mi355rt_context_render_view(self._h, C.byref(view) if view is not None else None, C.byref(params) if params is not None else None,
+                                                   p(d_accum), p(d_out_linear), p(d_out_packed), p(d_scratch), p(stream)), "mi355rt_context_render_view", self._L)
 
     def denoise(self, width, rows, d_linear_in, d_hits, d_scratch, d_out_linear=None, d_out_packed=None, params=None, stream=None):
         """mi355rt_context_denoise: the a-trous filter of mi355rt.h over a contiguous window of rows x width pixels, enqueued on `stream`.  Integer
