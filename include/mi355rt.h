@@ -44,6 +44,7 @@ extern "C" {
                                     and the occlusion queries: mi355rt_context_occluded, mi355rt_occluded, mi355rt_context_ambient_occlusion;
                                     and the radiance queries: mi355rt_radiance_scratch_bytes, mi355rt_context_trace_radiance, mi355rt_trace_radiance;
                                     and the camera views: mi355rt_view_scratch_bytes, mi355rt_context_view_rays, mi355rt_context_render_view;
+                                    and the surface probes: mi355rt_context_probe_rays, mi355rt_context_probe_radiance;
                                     and, in the host library, the noise estimate: mi355rt_noise_create, mi355rt_noise_free, mi355rt_noise_reset,
                                     mi355rt_noise_update, mi355rt_noise_evaluate;
                                     and, in the device library, the same estimate on device memory: mi355rt_noise_device_create, mi355rt_noise_device_destroy,
@@ -505,6 +506,49 @@ int  mi355rt_context_view_rays(mi355rt_context* ctx, const mi355rt_view* view, u
 /* d_accum: width * height float4; d_out_linear: width * height * 3 floats; d_out_packed: width * height uint32. */
 int  mi355rt_context_render_view(mi355rt_context* ctx, const mi355rt_view* view, const mi355rt_radiance_params* params,
                                  void* d_accum, void* d_out_linear_or_null, void* d_out_packed_or_null, void* d_scratch, void* hip_stream);
+
+/* ---- surface probes: device-made cosine-hemisphere rays for baking (added within ABI version 5: probe for the symbols) ----
+ * A PROBE is a surface point and its normal: a lightmap texel, a diffuse light probe.  The call answers with the cosine-weighted mean of the
+ * radiance arriving at each point -- the radiance form of mi355rt_context_ambient_occlusion.  The rays are made on the device, in front of the
+ * path loop of the radiance queries above: no host-made rays, no upload per sample, one call for any range of samples -- baking takes hundreds
+ * to thousands of samples per point.
+ *
+ * DEFINITION.  A probe record has the layout of mi355rt_path_ray; x and row are the stream address, as there.  The normal is USED AS GIVEN: a
+ *   unit normal is the caller's business (mi355rt_hit.normal is one).  For sample s of probe i, with ykey = (uint64)row + seed and the generator
+ *   of rng.start(ykey lo, ykey hi, x, s) standing at ray 0 -- MI355RT_RNG_CTR's addressing, as above.  All arithmetic is float32, one rounding
+ *   per operation, in the order written, IEEE division and square root; normalized() is src/vec3.rs:37-44 (a length below 1e-4 is left alone).
+ *   TRIES:      try j = 0, 1, ... takes p = (r(w1), r(w2), r(w3)) from the words 1 / 2 / 3 of (ray 0, block j), r(w) = (w >> 9) * 2^-22 - 1 (the
+ *               bounce's mapping, random_range(-1.0..1.0); not the lens's f(w)).  The render draws words 0 / 1 of block 0 of ray 0 and never its
+ *               blocks >= 1.  A try is accepted on (p.x*p.x + p.y*p.y) + p.z*p.z < 1.0f (src/vec3.rs:54-61).  After 64 rejected tries
+ *               p = (0, 0, 0): the work per item is bounded.
+ *   DIRECTION:  d = N + normalized(p); if every |component| of d is below 1e-8 (near_zero, src/vec3.rs:63-66) then d = N
+ *               (src/material.rs:54-62).  direction = normalized(d): normalised once.
+ *   ORIGIN:     P + N * EPSILON, EPSILON = 1e-4f (the reference's bounce origin).
+ *   mi355rt_context_probe_rays writes these rays for one sample index: n mi355rt_path_ray records {origin, x, direction, row}.
+ *   mi355rt_context_probe_radiance IS, by definition, mi355rt_context_trace_radiance along the rays of probe_rays(sample = s) for every s in
+ *   [params.sample_begin, params.sample_end): the query normalises the direction once more (Ray::new), the same fold, the same sums in sample
+ *   order continuing from d_accum (read only when sample_begin > 0, always written), the same d_out_linear = sum * (1.0f / (float)sample_end),
+ *   the same mi355rt_radiance_params; calls that cover 0 .. N in any chunking give the words of one call.
+ * CONSEQUENCE.  The probe ray is the bounce a white Lambert surface at (P, N) would make, if that event were addressed at ray 0.  With a unit
+ *   normal the directions are cosine-weighted about N, so d_out_linear is the COSINE-WEIGHTED MEAN RADIANCE at the point: the irradiance is pi
+ *   times it, and the radiosity of a diffuse texel its albedo times it.  The library does not multiply.
+ * SCRATCH is the caller's: mi355rt_radiance_scratch_bytes(n, sample_end - sample_begin) bytes, 16-byte aligned.
+ * REFUSALS, all decided before any HIP call, MI355RT_ERR_INVALID with a text that names the argument: everything
+ *   mi355rt_context_trace_radiance refuses, under the call's own name, with d_probes in the place of d_rays; for probe_rays with n > 0 a null
+ *   or misaligned (16 bytes) d_probes or d_rays, then a null context, a context without a scene.  n == 0 is MI355RT_OK and does nothing.  There
+ *   is no host-buffer form: the probes come from first-hit records that are already on the device, and a one-shot would pay
+ *   mi355rt_context_set_scene for every call -- a probe is only worth having on a resident scene.
+ * PROTOCOL of the ray queries: the calls read the resident scene only, touch no workspace of the context, only enqueue, may run on another
+ *   stream beside a render of the same context, and run on one device. */
+typedef struct mi355rt_probe {        /* 32 bytes; arrays 16-byte aligned */
+    float position[3]; uint32_t x;    /* stream address word "x", as mi355rt_path_ray.x */
+    float normal[3];   uint32_t row;  /* stream key: row + seed, 64 bit, as mi355rt_path_ray.row */
+} mi355rt_probe;
+/* DEVICE pointers; both enqueue on hip_stream (NULL = default stream) and return.  d_probes: n mi355rt_probe; d_rays: n mi355rt_path_ray. */
+int  mi355rt_context_probe_rays(mi355rt_context* ctx, const void* d_probes, uint32_t n, uint32_t sample, uint64_t seed, void* d_rays, void* hip_stream);
+/* d_accum: n float4; d_out_linear: n * 3 floats; d_scratch: mi355rt_radiance_scratch_bytes(n, sample_end - sample_begin) bytes. */
+int  mi355rt_context_probe_radiance(mi355rt_context* ctx, const mi355rt_radiance_params* params, const void* d_probes, uint32_t n,
+                                    void* d_accum, void* d_out_linear_or_null, void* d_scratch, void* hip_stream);
 
 /* ---- denoising a preview: an edge-avoiding a-trous filter guided by first-hit records (added within ABI version 5: probe for the symbols) ----
  * For the first chunks of a progressive render: the noisy linear image and the records of mi355rt_context_first_hits for the same rows go in,

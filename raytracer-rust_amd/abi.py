@@ -124,6 +124,28 @@ class RadianceParams(C.Structure):                        # mi355rt_radiance_par
         return cls(sample_begin, sample_end, max_depth, 0, seed, 0)
 
 
+class Probe(C.Structure):                                 # mi355rt_probe, 32 bytes: a PathRay whose vectors are a surface point and its normal
+    _fields_ = [("position", f32 * 3), ("x", u32), ("normal", f32 * 3), ("row", u32)]
+
+
+PROBE_DTYPE = np.dtype([("position", "<f4", 3), ("x", "<u4"), ("normal", "<f4", 3), ("row", "<u4")])
+
+
+def probes_from_hits(hits, width):
+    """abi.PROBE_DTYPE [hits that hit]: a probe at every first-hit record of `hits` (abi.HIT_DTYPE, row-major over an image `width` pixels across, as
+    Context.first_hits writes them), misses dropped: position and normal as the record holds them, x = i % width and row = i // width of record i."""
+    hits = np.asarray(hits).reshape(-1)
+    if hits.dtype != HIT_DTYPE:
+        raise ValueError("probes_from_hits: hits must be an array of abi.HIT_DTYPE")
+    if int(width) <= 0:
+        raise ValueError("probes_from_hits: width must be positive")
+    i = np.nonzero(hits["primitive"] != NO_HIT)[0]
+    out = np.zeros(i.size, PROBE_DTYPE)
+    out["position"], out["normal"] = hits["position"][i], hits["normal"][i]
+    out["x"], out["row"] = i % int(width), i // int(width)
+    return out
+
+
 VIEW_PINHOLE, VIEW_THIN_LENS = 0, 1
 VIEW_CENTRE = 1
 

@@ -3,7 +3,7 @@
   libmi355rt.so       hipcc: HIP kernels + the device half of the C ABI (csrc/device; rt_query.hip: the ray-query kernels, a translation unit
                              of their own; rt_denoise.hip: the denoiser's kernels, likewise; rt_occlusion.hip: the occlusion
                              and ambient-occlusion kernels, likewise; rt_noise.hip: the noise estimate's kernels and its five entry points; rt_radiance.hip: the radiance
-                             queries' kernels and their three entry points; rt_view.hip: the camera views' kernels and their three entry points; rt_prepare.cpp: scene preparation, no HIP in it; rt_multi.cpp: the multi-device context;
+                             queries' kernels and their three entry points; rt_view.hip: the camera views' kernels and their three entry points; rt_probe.hip: the surface probes' kernels and their two entry points; rt_prepare.cpp: scene preparation, no HIP in it; rt_multi.cpp: the multi-device context;
                              rt_oneshot.cpp: the calls with host buffers, clients of the other two)
   libmi355rt_host.so  g++:   CPU-side producers -- scene loader, mesh readers, BVH build, PNG (csrc/host)
   rt_render           g++:   CLI that stands in for the Rust `main` (csrc/tools)
@@ -38,6 +38,7 @@ CXX_FLAGS = ["-O2", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-fPIC"
 
 DEVICE_SRCS = [os.path.join(CSRC, "device", "rt_kernels.hip"), os.path.join(CSRC, "device", "rt_query.hip"), os.path.join(CSRC, "device", "rt_denoise.hip"),
                os.path.join(CSRC, "device", "rt_occlusion.hip"), os.path.join(CSRC, "device", "rt_noise.hip"), os.path.join(CSRC, "device", "rt_radiance.hip"), os.path.join(CSRC, "device", "rt_view.hip"),
+               os.path.join(CSRC, "device", "rt_probe.hip"),
                os.path.join(CSRC, "device", "rt_api.cpp"),
                os.path.join(CSRC, "device", "rt_prepare.cpp"), os.path.join(CSRC, "device", "rt_multi.cpp"),
                os.path.join(CSRC, "device", "rt_oneshot.cpp")]
@@ -94,7 +95,7 @@ def kernel_hash():
     profiles/pmc_counters.json records it, and bench.py refuses counters taken on another library."""
     import hashlib
     h = hashlib.sha256()
-    for f in DEVICE_SRCS + DEVICE_HEADERS:                  # rt_kernels.hip, rt_query.hip, rt_denoise.hip, rt_occlusion.hip, rt_noise.hip, rt_radiance.hip, rt_view.hip, rt_api.cpp, rt_prepare.cpp, rt_multi.cpp, rt_oneshot.cpp and every header they include (rt_device.h, rt_math.h, ...)
+    for f in DEVICE_SRCS + DEVICE_HEADERS:                  # rt_kernels.hip, rt_query.hip, rt_denoise.hip, rt_occlusion.hip, rt_noise.hip, rt_radiance.hip, rt_view.hip, rt_probe.hip, rt_api.cpp, rt_prepare.cpp, rt_multi.cpp, rt_oneshot.cpp and every header they include (rt_device.h, rt_math.h, ...)
         h.update(_code_only(open(f, encoding="utf-8").read()).encode())
     h.update(" ".join(HIPCC_FLAGS).encode())
     return h.hexdigest()[:16]

@@ -28,6 +28,7 @@
 #include "rt_occlusion.h"
 #include "rt_radiance.h"
 #include "rt_view.h"
+#include "rt_probe.h"
 
 using namespace mi355rt;
 
@@ -766,6 +767,43 @@ int mi355rt::context_render_view(mi355rt_context* ctx, const mi355rt_view* view,
     s.sum.scratch = (const float*)d_scratch; s.sum.accum = (float*)d_accum; s.sum.out_linear = (float*)d_out_linear; s.sum.n_rays = plan.n_pixels;
     s.sum.samples = plan.r.samples; s.sum.accum_load = plan.r.accum_load; s.sum.inv_total = plan.r.inv_total; s.out_packed = (uint32_t*)d_out_packed;
     if (launch_view_paths(p, v, s, view->model, ctx->has_mesh, plan.r.grid_paths, plan.r.grid_sum, hip_stream) != 0) return fail(MI355RT_ERR_HIP, "k_view launch failed");
+    return MI355RT_OK;
+}
+
+// ---- surface probes (rt_probe.hip): cosine-hemisphere rays made on the device from the caller's points and normals, in front of the same loop ----
+// The context halves of mi355rt_context_probe_rays / mi355rt_context_probe_radiance, whose entry points stand with their kernels in rt_probe.hip,
+// behind the barrier.  The protocol of the ray queries; every refusal and the grids are rt_prepare.cpp's (plan_probe_rays, plan_probe), before any HIP call.
+int mi355rt::context_probe_rays(mi355rt_context* ctx, const void* d_probes, uint32_t n, uint32_t sample, uint64_t seed, void* d_rays, void* hip_stream) {
+    static_assert(sizeof(mi355rt_probe) == 32 && sizeof(mi355rt_probe) == sizeof(mi355rt_path_ray), "the kernel reads a probe as two 16-byte halves");
+    if (int rc = plan_probe_rays(ctx != nullptr, ctx && ctx->have_scene, d_probes, n, d_rays)) return rc;
+    if (n == 0) return MI355RT_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (int erc = report_device_error(ctx)) return erc;              // an earlier asynchronous render on this context failed
+    ProbeParams b{}; b.probes = d_probes;
+    ProbeRaysOut r{};
+    r.rays = d_rays; r.n = n; r.sample = sample; r.seed_lo = (uint32_t)seed; r.seed_hi = (uint32_t)(seed >> 32);
+    if (launch_probe_rays(b, r, hip_stream) != 0) return fail(MI355RT_ERR_HIP, "k_probe_rays launch failed");
+    return MI355RT_OK;
+}
+int mi355rt::context_probe_radiance(mi355rt_context* ctx, const mi355rt_radiance_params* params, const void* d_probes, uint32_t n, void* d_accum,
+                                    void* d_out_linear, void* d_scratch, void* hip_stream) {
+    RadiancePlan plan{};
+    if (int rc = plan_probe(ctx != nullptr, ctx && ctx->have_scene, params, d_probes, n, d_accum, d_out_linear, d_scratch,
+                            ctx ? (uint32_t)ctx->knob_radiance_items : 0u, RADIANCE_ITEMS_DEFAULT, plan)) return rc;
+    if (n == 0) return MI355RT_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (int erc = report_device_error(ctx)) return erc;              // an earlier asynchronous render on this context failed
+    RadianceParams p{};
+    p.prims = ctx->prims.p; p.mats = ctx->mats.p; p.nodes = ctx->nodes.p; p.tris = ctx->tris.p; p.n_prims = ctx->n_prims;
+    p.sky = ctx->sky_w ? ctx->sky.p : nullptr; p.sky_w = ctx->sky_w; p.sky_h = ctx->sky_h; p.textures = ctx->textures.p;
+    std::memcpy(p.miss, ctx->miss, sizeof p.miss);
+    p.rays = nullptr; p.scratch = (float*)d_scratch; p.n_items = plan.n_items; p.samples = plan.samples; p.sample_begin = params->sample_begin;
+    p.max_depth = params->max_depth; p.items_per_lane = plan.items_per_lane; p.seed_lo = plan.seed_lo; p.seed_hi = plan.seed_hi;
+    ProbeParams b{}; b.probes = d_probes;
+    RadianceSum s{};
+    s.scratch = (const float*)d_scratch; s.accum = (float*)d_accum; s.out_linear = (float*)d_out_linear; s.n_rays = n; s.samples = plan.samples;
+    s.accum_load = plan.accum_load; s.inv_total = plan.inv_total;
+    if (launch_probe_paths(p, b, s, ctx->has_mesh, plan.grid_paths, plan.grid_sum, hip_stream) != 0) return fail(MI355RT_ERR_HIP, "k_probe launch failed");
     return MI355RT_OK;
 }
 extern "C" {

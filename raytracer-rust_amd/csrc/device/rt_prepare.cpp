@@ -132,7 +132,8 @@ int plan_ambient_occlusion(bool have_ctx, bool have_scene, const mi355rt_setting
     return MI355RT_OK;
 }
 
-// The radiance query's plan for `who` ("trace_radiance"; "render_view": the views run the same loop over made rays -- with_rays false, `rays` not looked at).
+// The radiance query's plan for `who` ("trace_radiance"; "render_view": the views run the same loop over made rays -- rays_name null, `rays` not looked at;
+// "probe_radiance": the probes run it over rays made from the caller's records -- rays_name "d_probes").
 static int radiance_items_bytes(const char* who, const char* what, uint64_t n_rays, uint32_t samples, uint64_t* out_bytes) {
     if (!out_bytes) return fail(MI355RT_ERR_INVALID, std::string(who) + ": out_bytes is null");
     if (n_rays >= (1ull << 32) || n_rays * samples >= (1ull << 32)) return fail(MI355RT_ERR_INVALID, std::string(who) + ": " + what + " must stay below 2^32 (split the call)");
@@ -144,7 +145,7 @@ int radiance_scratch_bytes(uint32_t n_rays, uint32_t samples, uint64_t* out_byte
     return radiance_items_bytes("trace_radiance", "n_rays * samples", n_rays, samples, out_bytes);
 }
 
-static int plan_radiance_for(const char* who, const char* what, bool with_rays, bool have_ctx, bool have_scene, const mi355rt_radiance_params* params, const void* rays,
+static int plan_radiance_for(const char* who, const char* what, const char* rays_name, bool have_ctx, bool have_scene, const mi355rt_radiance_params* params, const void* rays,
                              uint64_t n_rays, const void* accum, const void* out_linear, const void* out_packed, const void* scratch, uint32_t items_knob,
                              uint32_t default_items, RadiancePlan& plan) {
     const auto bad = [who](const char* text) { return fail(MI355RT_ERR_INVALID, std::string(who) + ": " + text); };
@@ -155,10 +156,10 @@ static int plan_radiance_for(const char* who, const char* what, bool with_rays, 
     plan = RadiancePlan{};
     plan.samples = params->sample_end - params->sample_begin;
     if (n_rays != 0u) {
-        if (with_rays && !rays) return bad("d_rays is null");
+        if (rays_name && !rays) return fail(MI355RT_ERR_INVALID, std::string(who) + ": " + rays_name + " is null");
         if (!accum) return bad("d_accum is null");
         if (!scratch) return bad("d_scratch is null");
-        if (with_rays && misaligned_to(rays, 16)) return bad("d_rays must be 16-byte aligned");
+        if (rays_name && misaligned_to(rays, 16)) return fail(MI355RT_ERR_INVALID, std::string(who) + ": " + rays_name + " must be 16-byte aligned");
         if (misaligned_to(accum, 16)) return bad("d_accum must be 16-byte aligned");
         if (misaligned_to(scratch, 16)) return bad("d_scratch must be 16-byte aligned");
         if (misaligned_to(out_linear, 4)) return bad("d_out_linear must be 4-byte aligned");
@@ -182,7 +183,7 @@ static int plan_radiance_for(const char* who, const char* what, bool with_rays, 
 
 int plan_radiance(bool have_ctx, bool have_scene, const mi355rt_radiance_params* params, const void* rays, uint32_t n_rays, const void* accum,
                   const void* out_linear, const void* scratch, uint32_t items_knob, uint32_t default_items, RadiancePlan& plan) {
-    return plan_radiance_for("trace_radiance", "n_rays * samples", true, have_ctx, have_scene, params, rays, n_rays, accum, out_linear, nullptr, scratch, items_knob,
+    return plan_radiance_for("trace_radiance", "n_rays * samples", "d_rays", have_ctx, have_scene, params, rays, n_rays, accum, out_linear, nullptr, scratch, items_knob,
                              default_items, plan);
 }
 
@@ -234,11 +235,31 @@ int plan_view(bool have_ctx, bool have_scene, const mi355rt_view* view, const mi
     if (int rc = check_view("render_view", view)) return rc;
     plan = ViewPlan{};
     const uint64_t pixels = (uint64_t)view->width * view->height;    // (> 0: check_view)
-    if (int rc = plan_radiance_for("render_view", "view.width * view.height * samples", false, have_ctx, have_scene, params, nullptr, pixels, accum, out_linear,
+    if (int rc = plan_radiance_for("render_view", "view.width * view.height * samples", nullptr, have_ctx, have_scene, params, nullptr, pixels, accum, out_linear,
                                    out_packed, scratch, items_knob, default_items, plan.r)) return rc;
     plan.n_pixels = (uint32_t)pixels;
     plan.centre = view->flags & MI355RT_VIEW_CENTRE;
     return MI355RT_OK;
+}
+
+// The surface probes: a probe record is read as a ray record is (two 16-byte loads), so probe_radiance is the radiance query's plan under its own name.
+int plan_probe_rays(bool have_ctx, bool have_scene, const void* probes, uint32_t n, const void* rays) {
+    const auto bad = [](const char* text) { return fail(MI355RT_ERR_INVALID, std::string("probe_rays: ") + text); };
+    if (n != 0u) {
+        if (!probes) return bad("d_probes is null");
+        if (!rays) return bad("d_rays is null");
+        if (misaligned_to(probes, 16)) return bad("d_probes must be 16-byte aligned");
+        if (misaligned_to(rays, 16)) return bad("d_rays must be 16-byte aligned");
+    }
+    if (!have_ctx) return bad("ctx is null");
+    if (!have_scene) return bad("context has no scene");
+    return MI355RT_OK;
+}
+
+int plan_probe(bool have_ctx, bool have_scene, const mi355rt_radiance_params* params, const void* probes, uint32_t n, const void* accum,
+               const void* out_linear, const void* scratch, uint32_t items_knob, uint32_t default_items, RadiancePlan& plan) {
+    return plan_radiance_for("probe_radiance", "n * samples", "d_probes", have_ctx, have_scene, params, probes, n, accum, out_linear, nullptr, scratch, items_knob,
+                             default_items, plan);
 }
 
 // s = ceil(log2 d), mul = ceil(2^(31+s) / d) < 2^32, shift = s - 1.

@@ -96,6 +96,13 @@ int plan_view_rays(bool have_ctx, bool have_scene, const mi355rt_view* view, con
 int plan_view(bool have_ctx, bool have_scene, const mi355rt_view* view, const mi355rt_radiance_params* params, const void* accum, const void* out_linear_or_null,
               const void* out_packed_or_null, const void* scratch, uint32_t items_knob, uint32_t default_items, ViewPlan& plan);
 
+// The surface probes (mi355rt.h, mi355rt_context_probe_rays / mi355rt_context_probe_radiance), decided before any HIP call.
+// plan_probe is plan_radiance under the call's own name, with d_probes in the place of d_rays.  plan_probe_rays refuses, with n > 0, a null or
+// misaligned (16 bytes) d_probes, then d_rays; then the context and its scene.  n == 0 passes: nothing to launch.
+int plan_probe_rays(bool have_ctx, bool have_scene, const void* probes, uint32_t n, const void* rays);
+int plan_probe(bool have_ctx, bool have_scene, const mi355rt_radiance_params* params, const void* probes, uint32_t n, const void* accum,
+               const void* out_linear_or_null, const void* scratch, uint32_t items_knob, uint32_t default_items, RadiancePlan& plan);
+
 // The render call (mi355rt_context_render / mi355rt_context_render_progressive): every refusal, the variant that is launched, the
 // bands the radiance workspace is cycled through and the geometry of each band's launch, decided before any HIP call.
 // q = n / d for every n < 2^31 as umulhi(n, mul) >> shift (mul == 0 encodes d == 1).

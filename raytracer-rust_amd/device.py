@@ -22,6 +22,7 @@ EXPORTS = ["mi355rt_render", "mi355rt_render_multi", "mi355rt_render_progressive
            "mi355rt_context_occluded", "mi355rt_occluded", "mi355rt_context_ambient_occlusion",
            "mi355rt_radiance_scratch_bytes", "mi355rt_context_trace_radiance", "mi355rt_trace_radiance",
            "mi355rt_view_scratch_bytes", "mi355rt_context_view_rays", "mi355rt_context_render_view",
+           "mi355rt_context_probe_rays", "mi355rt_context_probe_radiance",
            "mi355rt_noise_device_create", "mi355rt_noise_device_destroy", "mi355rt_noise_device_reset", "mi355rt_noise_device_update",
            "mi355rt_noise_device_evaluate"]
 
@@ -293,6 +294,10 @@ def _bind(so):
         L.mi355rt_context_view_rays.argtypes = [C.c_void_p, C.POINTER(abi.View), C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p]
         L.mi355rt_context_render_view.restype = C.c_int
         L.mi355rt_context_render_view.argtypes = [C.c_void_p, C.POINTER(abi.View), C.POINTER(abi.RadianceParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.mi355rt_context_probe_rays.restype = C.c_int
+        L.mi355rt_context_probe_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p]
+        L.mi355rt_context_probe_radiance.restype = C.c_int
+        L.mi355rt_context_probe_radiance.argtypes = [C.c_void_p, C.POINTER(abi.RadianceParams), C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.mi355rt_noise_device_create.restype = C.c_int
         L.mi355rt_noise_device_create.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
         L.mi355rt_noise_device_destroy.restype = None
@@ -742,6 +747,22 @@ class Context:
         p = lambda a: C.c_void_p(a) if a else None
         _check(self._L.mi355rt_context_render_view(self._h, C.byref(view) if view is not None else None, C.byref(params) if params is not None else None,
                                                    p(d_accum), p(d_out_linear), p(d_out_packed), p(d_scratch), p(stream)), "mi355rt_context_render_view", self._L)
+
+    def probe_rays(self, d_probes, n, sample, d_rays, seed=0, stream=None):
+        """mi355rt_context_probe_rays: the cosine-hemisphere ray of sample index `sample` of each of n probes (abi.Probe records at the integer device
+        address d_probes, 16-byte aligned), made on the device and written to d_rays (n abi.PathRay records, 16-byte aligned), enqueued on `stream`."""
+        p = lambda a: C.c_void_p(a) if a else None
+        _check(self._L.mi355rt_context_probe_rays(self._h, p(d_probes), int(n), int(sample), int(seed), p(d_rays), p(stream)),
+               "mi355rt_context_probe_rays", self._L)
+
+    def probe_radiance(self, params, d_probes, n, d_accum, d_scratch, d_out_linear=None, stream=None):
+        """mi355rt_context_probe_radiance: samples [params.sample_begin, params.sample_end) of the cosine-weighted mean radiance at each of n probes
+        of the resident scene (irradiance / pi), the rays made on the device, enqueued on `stream`.  Integer device addresses (16-byte aligned): d_probes
+        n abi.Probe records, d_accum n float4 running sums (read when sample_begin > 0, always written), d_scratch radiance_scratch_bytes(n,
+        sample_end - sample_begin) bytes; d_out_linear: n * 3 floats, sum / sample_end, or None.  params: abi.RadianceParams."""
+        p = lambda a: C.c_void_p(a) if a else None
+        _check(self._L.mi355rt_context_probe_radiance(self._h, C.byref(params) if params is not None else None, p(d_probes), int(n), p(d_accum),
+                                                      p(d_out_linear), p(d_scratch), p(stream)), "mi355rt_context_probe_radiance", self._L)
 
     def denoise(self, width, rows, d_linear_in, d_hits, d_scratch, d_out_linear=None, d_out_packed=None, params=None, stream=None):
         """mi355rt_context_denoise: the a-trous filter of mi355rt.h over a contiguous window of rows x width pixels, enqueued on `stream`.  Integer
