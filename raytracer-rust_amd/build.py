@@ -2,9 +2,11 @@
 
   libmi355rt.so       hipcc: HIP kernels + the device half of the C ABI (csrc/device; rt_query.hip: the ray-query kernels, a translation unit
                              of their own; rt_denoise.hip: the denoiser's kernels, likewise; rt_occlusion.hip: the occlusion
-                             and ambient-occlusion kernels, likewise; rt_noise.hip: the noise estimate's kernels and its five entry points; rt_radiance.hip: the radiance
-                             queries' kernels and their three entry points; rt_view.hip: the camera views' kernels and their three entry points; rt_probe.hip: the surface probes' kernels and their two entry points; rt_prepare.cpp: scene preparation, no HIP in it; rt_multi.cpp: the multi-device context;
-                             rt_oneshot.cpp: the calls with host buffers, clients of the other two)
+                             and ambient-occlusion kernels, likewise; rt_noise.hip: the noise estimate's kernels and its five entry points; rt_radiance.hip,
+                             rt_view.hip, rt_probe.hip: the kernels of the radiance queries, the camera views and the surface probes; rt_api.cpp: the context,
+                             set_scene and the renders; rt_queries.cpp: the calls that only read the resident scene; rt_debug.cpp: the debug hooks and
+                             the knobs; rt_prepare.cpp: scene preparation and the plans, no HIP in it; rt_multi.cpp: the multi-device context;
+                             rt_oneshot.cpp: the calls with host buffers, clients of the public functions)
   libmi355rt_host.so  g++:   CPU-side producers -- scene loader, mesh readers, BVH build, PNG (csrc/host)
   rt_render           g++:   CLI that stands in for the Rust `main` (csrc/tools)
 
@@ -39,7 +41,7 @@ CXX_FLAGS = ["-O2", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-fPIC"
 DEVICE_SRCS = [os.path.join(CSRC, "device", "rt_kernels.hip"), os.path.join(CSRC, "device", "rt_query.hip"), os.path.join(CSRC, "device", "rt_denoise.hip"),
                os.path.join(CSRC, "device", "rt_occlusion.hip"), os.path.join(CSRC, "device", "rt_noise.hip"), os.path.join(CSRC, "device", "rt_radiance.hip"), os.path.join(CSRC, "device", "rt_view.hip"),
                os.path.join(CSRC, "device", "rt_probe.hip"),
-               os.path.join(CSRC, "device", "rt_api.cpp"),
+               os.path.join(CSRC, "device", "rt_api.cpp"), os.path.join(CSRC, "device", "rt_queries.cpp"), os.path.join(CSRC, "device", "rt_debug.cpp"),
                os.path.join(CSRC, "device", "rt_prepare.cpp"), os.path.join(CSRC, "device", "rt_multi.cpp"),
                os.path.join(CSRC, "device", "rt_oneshot.cpp")]
 DEVICE_HEADERS = sorted(os.path.join(CSRC, "device", f) for f in os.listdir(os.path.join(CSRC, "device")) if f.endswith(".h"))
@@ -89,13 +91,13 @@ def _code_only(text):
 
 def kernel_hash():
     """sha256 over everything that decides the device code AND how it is launched: the kernel source, every header of csrc/device, the
-    host half (rt_api.cpp: the launches; rt_prepare.cpp: the scene records, the choice of the kernel variant, the plan of a render -- grid size, shard size, guided_div; rt_multi.cpp and rt_oneshot.cpp: the multi-device context and the calls with host buffers, built on rt_api.cpp's
+    host half (rt_api.cpp, rt_queries.cpp and rt_debug.cpp: the launches of the renders, of the queries and of the debug hooks; rt_prepare.cpp: the scene records, the choice of the kernel variant, the plan of a render -- grid size, shard size, guided_div; rt_multi.cpp and rt_oneshot.cpp: the multi-device context and the calls with host buffers, built on the public
     entry points) and the hipcc flags -- the CODE of those
     files: comments and whitespace are stripped first, so that correcting a comment does not orphan the committed counters.
     profiles/pmc_counters.json records it, and bench.py refuses counters taken on another library."""
     import hashlib
     h = hashlib.sha256()
-    for f in DEVICE_SRCS + DEVICE_HEADERS:                  # rt_kernels.hip, rt_query.hip, rt_denoise.hip, rt_occlusion.hip, rt_noise.hip, rt_radiance.hip, rt_view.hip, rt_probe.hip, rt_api.cpp, rt_prepare.cpp, rt_multi.cpp, rt_oneshot.cpp and every header they include (rt_device.h, rt_math.h, ...)
+    for f in DEVICE_SRCS + DEVICE_HEADERS:                  # rt_kernels.hip, rt_query.hip, rt_denoise.hip, rt_occlusion.hip, rt_noise.hip, rt_radiance.hip, rt_view.hip, rt_probe.hip, rt_api.cpp, rt_queries.cpp, rt_debug.cpp, rt_prepare.cpp, rt_multi.cpp, rt_oneshot.cpp and every header they include (rt_device.h, rt_math.h, ...)
         h.update(_code_only(open(f, encoding="utf-8").read()).encode())
     h.update(" ".join(HIPCC_FLAGS).encode())
     return h.hexdigest()[:16]

@@ -4,125 +4,22 @@
 // called from src/main.rs:57).  There is NO CPU fallback in this library: without a HIP device every
 // render entry point returns MI355RT_ERR_NO_DEVICE.  What happens to a scene before a device is involved -- validation, the BVH re-lay, the
 // primitive records, the choice of the kernel variant -- and what a render call launches -- its refusals, the variant, the bands and their grids -- is
-// rt_prepare.cpp, which has no HIP in it; this file uploads and launches: the context, its renders, its queries and the debug hooks.  The
-// calls with host buffers (mi355rt_render and its kin) are clients of this file's public functions and live in rt_oneshot.cpp.
-#include <hip/hip_runtime_api.h>
-
+// rt_prepare.cpp, which has no HIP in it; this file uploads and launches: the context's life cycle, set_scene with its probes, the renders, the
+// share, timing and check.  The context struct is rt_context.h's; the calls that only read the resident scene (queries, views, probes, the denoiser)
+// are rt_queries.cpp, the mi355rt_debug_* hooks and the knobs rt_debug.cpp.  The calls with host buffers (mi355rt_render and its kin) are clients of
+// the public functions and live in rt_oneshot.cpp.
 #include <algorithm>
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <map>
-#include <mutex>
 #include <new>
-#include <stdexcept>
 #include <string>
-#include <vector>
 
-#include "../../../include/mi355rt.h"
-#include "rt_device.h"
-#include "rt_host.h"
-#include "rt_query.h"
-#include "rt_denoise.h"
-#include "rt_occlusion.h"
-#include "rt_radiance.h"
-#include "rt_view.h"
-#include "rt_probe.h"
-
-using namespace mi355rt;
-
-struct mi355rt_context;
-static int report_device_error(mi355rt_context* ctx, bool this_render = false);
-
-struct mi355rt_context {
-    int device = 0;
-    int cu_count = 0;
-    int blocks_per_cu[KERNEL_ENTRIES][KERNEL_VARIANTS] = {}, vgprs[KERNEL_ENTRIES][KERNEL_VARIANTS] = {}, sgprs = 0;   // per entry point (rt_device.h ENTRY_*): with / without a sky texture
-    uint32_t entry() const { return variant_entry(variant, sky_w != 0); }   // the entry point the resident scene is launched on
-    uint32_t variant = KERNEL_LOCKSTEP;  // chosen per scene in set_scene
-    bool has_mesh = false;
-    bool occlusion_may_exit = false;     // every number the hit tests read from the scene lies inside OCCLUSION_BOUND: the occlusion kernels may leave the list early (rt_prepare.h)
-    uint32_t grid_div = 1;               // this context launches 1 / grid_div of the grid that fills the device: the caller keeps grid_div frames in flight, each on its own
-                                         // context and stream, so that their persistent kernels are co-resident (see render_samples; mi355rt_context_set_share)
-    uint32_t guided_mult = 16;           // run length = (left in shard) / (guided_mult * waves per shard); 16 measured best at 1/8-image launches
-    uint32_t inline_steps = 0;           // 1 when several meshes share the list (many rays miss a mesh's root box: teapot +5..12 %), 0 for a single mesh (semesterbild -10 % otherwise)
-    uint32_t trav_min = 24;              // measured optimum 24-32 on semesterbild / teapot (tools/ab_kernel.py)
-    bool have_scene = false;
-    mi355rt_settings settings{};
-    DevCamera cam{};
-    float miss[3] = {0.5f, 0.5f, 0.5f};
-    uint32_t n_prims = 0, n_mats = 0; size_t n_nodes = 0;
-    DevBuf<DevPrim> prims; DevBuf<DevMat> mats; DevBuf<DevNode> nodes; DevBuf<DevTri> tris;
-    DevBuf<uint32_t> rows; DevBuf<float> radiance; DevBuf<uint32_t> counters; DevBuf<unsigned long long> stats;
-    DevBuf<float> fold_stack;
-    DevBuf<float> sky; uint32_t sky_w = 0, sky_h = 0;      // equirect HDR skybox (renderer.rs:40-54); sky_w == 0: none
-    DevBuf<DevTexture> textures; DevBuf<uint32_t> texels;  // MI355RT_MAT_TEXTURE images: table + all texels in one buffer
-    DevBuf<unsigned long long> wave_times; uint32_t wave_times_n = 0;   // diagnostics (MI355RT_WAVE_TIMES=1)
-    std::vector<uint32_t> rows_host;     // the selected rows (absolute y, ascending = the order of the output buffer)
-    std::vector<uint32_t> tables_host;   // source of the async upload of the three row tables (rt_prepare.h row_tables()); must outlive the copy
-    // Camera masks (rt_prepare.h build_camera_masks; k_render_ctr_simple_qc's camera pass).  cam_mask_abs: the table of the scene, the camera and the
-    // settings of set_scene, one word per pixel of the image (empty: none -- another kernel, more than 32 primitives, or the knob); cam_mask_host: its rows
-    // in the processing order of rows_host, rebuilt with the row tables and uploaded behind them into `rows` (same lifetime as tables_host); empty: the
-    // kernel gets no table.
-    std::vector<uint32_t> cam_mask_abs, cam_mask_host; uint32_t cam_mask_w = 0, cam_mask_h = 0;
-    int knob_cam_cull = -1;              // diagnostic knob "cam_cull": -1 / 1 on, 0 off (no table: the camera pass tests every primitive)
-    int knob_resolve_skip = 1;           // diagnostic knob "resolve_skip": 1 (the product) = k_resolve gets the band's camera masks and reads no sample of a pixel whose word is 0; 0 = it reads every sample
-    bool rows_valid = false;             // ctx->rows already holds the tables of rows_host (same selection and grouping as the last call)
-    // Processing order (an experiment of round 4, opt-in).  The persistent kernels hand out a band's samples front to back, and a
-    // launch ends with the paths of the rows handed out LAST.  The idea: process the rows in order of DECREASING expected cost -- cheap rows
-    // (sky) last -- dealt over the work shards so that every shard ends with cheap rows, and a launch does not end on its longest paths.  The image cannot change: draws are keyed by absolute row / x /
-    // sample, the resolve kernel writes each pixel where it belongs (ResolveParams.out_row).  `row_cost` = rays per path of each image
-    // row, measured by set_scene with a small probe render of the same view; empty = natural order.
-    std::vector<float> row_cost;
-    int knob_denoise_staged = 1;         // diagnostic knob "denoise_staged": 1 (the product) = the denoiser's levels with step 1 and 2 stage their tile in LDS; 0 = they gather like the later levels (the A/B of DESIGN.md 4.7)
-    int knob_ao_form = 0;                // diagnostic knob "ao_form": AO_FORM_* of rt_occlusion.h; 0 (the product) = a pixel's samples across the lanes of a wave, 1 = a pixel per lane (the A/B of DESIGN.md 4.8)
-    int knob_radiance_items = 0;         // diagnostic knob "radiance_items": K of rt_radiance.h, 1 .. 64 items per lane of k_radiance_paths; 0 (the product) = RADIANCE_ITEMS_DEFAULT (the A/B of DESIGN.md 4.12)
-    int knob_row_order = -1;             // diagnostic knob "row_order": 1 on; -1 / 0 off (NOT shipped as a default: no measured gain, see set_scene)
-    uint32_t order_groups = 0;           // how many groups the cached tables were dealt over (work shards x bands)
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-    // The workspaces (rows, radiance, counters, stats) belong to one render at a time.  `done` is recorded behind the last
-    // operation of every render; a render enqueued on ANOTHER stream waits on it first, so two streams can never touch
-    // the workspaces concurrently (same stream: in-order execution already guarantees it).
-    hipEvent_t done = nullptr; hipStream_t last_stream = nullptr; bool have_last = false;
-    bool want_wave_times = false;        // diagnostic knob "wave_times" (stamps builds)
-    // Sticky error word.  A wave of the wavefront kernel that gives up a bounded wait (RenderParams.spin_limit_*) adds 1 to `errword`
-    // and leaves paths unfinished.  The word is never reset by a render; its value is copied into the pinned host word `h_err`
-    // behind the kernels of EVERY render (8 bytes, in stream order, before `done`), and whichever entry point looks next --
-    // the same call when it synchronises for stats, mi355rt_context_check, mi355rt_context_read_timing, or the next render on
-    // this context -- compares it with what has been reported and returns MI355RT_ERR_HIP once per failed render.
-    DevBuf<unsigned long long> errword; unsigned long long* h_err = nullptr; unsigned long long err_reported = 0;
-    uint32_t spin_limit_idle = SPIN_LIMIT_IDLE, spin_limit_entry = SPIN_LIMIT_ENTRY;   // diagnostic knobs "spin_idle" / "spin_entry"
-    uint32_t launched_variants = 0;      // bit v: kernel variant v was launched since the last failure report (names the kernel in the message)
-    uint32_t launched_sky_entries = 0;   // bit v: ... on its entry point for scenes with a sky texture
-    int forced_variant = -1;             // diagnostic knob "kernel": applied by set_scene when the scene allows it
-    int knob_inline_steps = -1;          // diagnostic knob "inline_steps" (reference build's state machine)
-    // timing pool (mi355rt_context_set_timing): event triples recorded around every kernel pair without
-    // synchronising; mi355rt_context_read_timing sums them after the caller's own stream sync.
-    bool timing = false;
-    std::vector<hipEvent_t> pool; size_t pool_used = 0;
-    uint32_t timed_launches = 0;
-    // Row tables of mi355rt_context_first_hits (local output row -> absolute y), one per row selection seen since set_scene.  They are the queries' own:
-    // a query never touches `rows` above, which belongs to the render in flight.  A table is written once (its host copy outlives the upload) and
-    // never changed, so queries on any streams may read it; `ready` orders the upload before a query on another stream.
-    struct QueryRows { std::vector<uint32_t> rows; uint32_t* d = nullptr; hipEvent_t ready = nullptr; hipStream_t stream = nullptr; };
-    std::vector<QueryRows> query_rows;
-    void query_rows_release() {                                      // (hipFree waits for the device: no query still reads a table)
-        for (auto& t : query_rows) { if (t.d) (void)hipFree(t.d); if (t.ready) (void)hipEventDestroy(t.ready); }
-        query_rows.clear();
-    }
-    hipEvent_t pool_get() {
-        if (pool_used == pool.size()) { hipEvent_t e = nullptr; if (hipEventCreate(&e) != hipSuccess) return nullptr; pool.push_back(e); }
-        return pool[pool_used++];
-    }
-};
+#include "rt_context.h"
 
 // Compares the host copy of the context's error word with what has already been reported.  The copy is refreshed in stream order
 // behind every render, so after a wait on `done` it covers every render enqueued so far; without a wait it covers those that
 // have finished.
 // `this_render`: the caller has just waited for the render it enqueued itself (the stats path), so the failure is that render's; otherwise it
 // belongs to an earlier, asynchronous render on this context.  The word names the kernel(s) and the wait(s) that gave up (rt_device.h, err_tag).
-static int report_device_error(mi355rt_context* ctx, bool this_render) {
+int mi355rt::report_device_error(mi355rt_context* ctx, bool this_render) {
     if (!ctx->h_err) return MI355RT_OK;
     const unsigned long long now = *(volatile unsigned long long*)ctx->h_err;
     const unsigned long long count = now & 0xFFFFFFFFull;
@@ -143,13 +40,6 @@ static int report_device_error(mi355rt_context* ctx, bool this_render) {
 }
 
 namespace {
-
-// 1 bit per counter-mode variant this library holds (rt_kernels.hip): what choose_variant (rt_prepare.h) may be made to force.
-uint32_t built_variants() {
-    uint32_t mask = 0u;
-    for (uint32_t v = 0; v < KERNEL_VARIANTS; ++v) if (render_ctr_variant_built(v)) mask |= 1u << v;
-    return mask;
-}
 
 // The upload of a prepared scene (rt_prepare.h: validated and laid out without HIP) and what the context keeps of it.
 int build_device_scene(mi355rt_context* ctx, const mi355rt_scene* sc, const mi355rt_camera* camera, const mi355rt_settings* st) {
@@ -202,50 +92,9 @@ int build_device_scene(mi355rt_context* ctx, const mi355rt_scene* sc, const mi35
     return MI355RT_OK;
 }
 
-// Diagnostic knobs (mi355rt_debug_set_knob; not part of the public header).  They replace the environment variables earlier
-// rounds read at set_scene: a product library should not change behaviour with the caller's environment.
-std::mutex g_knob_mutex;
-std::map<std::string, int> g_default_knobs;
-int apply_knob(mi355rt_context* ctx, const std::string& name, int v) {
-    if (name == "kernel") { if (v < -1 || v >= (int)KERNEL_VARIANTS) return fail(MI355RT_ERR_INVALID, "knob kernel"); ctx->forced_variant = v; }
-    else if (name == "inline_steps") { if (v < -1 || v > 8) return fail(MI355RT_ERR_INVALID, "knob inline_steps"); ctx->knob_inline_steps = v; }
-    else if (name == "grid_div") { if (v < 1 || v > 16) return fail(MI355RT_ERR_INVALID, "knob grid_div"); ctx->grid_div = (uint32_t)v; }
-    else if (name == "guided_mult") { if (v < 1 || v > 64) return fail(MI355RT_ERR_INVALID, "knob guided_mult"); ctx->guided_mult = (uint32_t)v; }
-    else if (name == "trav_min") { if (v < 1 || v > 64) return fail(MI355RT_ERR_INVALID, "knob trav_min"); ctx->trav_min = (uint32_t)v; }
-    else if (name == "spin_idle") { if (v < 1) return fail(MI355RT_ERR_INVALID, "knob spin_idle"); ctx->spin_limit_idle = (uint32_t)v; }
-    else if (name == "spin_entry") { if (v < 1) return fail(MI355RT_ERR_INVALID, "knob spin_entry"); ctx->spin_limit_entry = (uint32_t)v; }
-    else if (name == "wave_times") ctx->want_wave_times = v != 0;
-    else if (name == "cam_cull") { if (v < -1 || v > 1) return fail(MI355RT_ERR_INVALID, "knob cam_cull"); ctx->knob_cam_cull = v; }
-    else if (name == "resolve_skip") { if (v < 0 || v > 1) return fail(MI355RT_ERR_INVALID, "knob resolve_skip"); ctx->knob_resolve_skip = v; }
-    else if (name == "denoise_staged") { if (v < 0 || v > 1) return fail(MI355RT_ERR_INVALID, "knob denoise_staged"); ctx->knob_denoise_staged = v; }
-    else if (name == "ao_form") { if (v < 0 || v > 1) return fail(MI355RT_ERR_INVALID, "knob ao_form"); ctx->knob_ao_form = v; }
-    else if (name == "radiance_items") { if (v < 0 || v > (int)RADIANCE_ITEMS_MAX) return fail(MI355RT_ERR_INVALID, "knob radiance_items"); ctx->knob_radiance_items = v; }
-    else if (name == "row_order") { if (v < -1 || v > 1) return fail(MI355RT_ERR_INVALID, "knob row_order"); ctx->knob_row_order = v; }
-    else return fail(MI355RT_ERR_INVALID, "unknown knob " + name);
-    return MI355RT_OK;
-}
-
 }  // namespace
 
 extern "C" {
-
-// Diagnostic hook (not part of the public header).  ctx != NULL: set one knob of that context (before set_scene).  ctx == NULL: a
-// process-wide default applied to every context created afterwards -- also those the one-shot calls create; name == NULL clears
-// all defaults.  Knobs: kernel (KERNEL_* of rt_device.h, -1 = automatic), guided_mult, spin_idle, spin_entry, wave_times, row_order,
-// cam_cull (0: k_render_ctr_simple_qc gets no camera masks), resolve_skip (0: k_resolve gets none), radiance_items (K of k_radiance_paths, 0 = the default), and for the reference build's state machine inline_steps, trav_min.
-int mi355rt_debug_set_knob(mi355rt_context* ctx, const char* name, int value) {
-    return guard([&]() -> int {
-    if (ctx) return name ? apply_knob(ctx, name, value) : fail(MI355RT_ERR_INVALID, "knob name is null");
-    std::lock_guard<std::mutex> g(g_knob_mutex);
-    if (!name) { g_default_knobs.clear(); return MI355RT_OK; }
-    mi355rt_context probe;                                            // validate name and range on a scratch context
-    const int rc = apply_knob(&probe, name, value);
-    if (rc == MI355RT_OK) g_default_knobs[name] = value;
-    return rc;
-    });
-}
-// 1 when this library holds the counter-mode kernel `variant` (the retired mesh kernels exist in the reference build only)
-int mi355rt_debug_has_variant(uint32_t variant) { return render_ctr_variant_built(variant) ? 1 : 0; }
 
 const char* mi355rt_last_error(void) { return last_error().c_str(); }
 uint32_t mi355rt_abi_version(void) { return MI355RT_ABI_VERSION; }
@@ -286,8 +135,7 @@ int mi355rt_context_create(int hip_device, mi355rt_context** out_ctx) {
     if (ctx->errword.ensure(1) != MI355RT_OK || hipMemset(ctx->errword.p, 0, sizeof(unsigned long long)) != hipSuccess ||
         hipHostMalloc((void**)&ctx->h_err, sizeof(unsigned long long), hipHostMallocDefault) != hipSuccess) { mi355rt_context_destroy(ctx); return fail(MI355RT_ERR_HIP, "error word allocation"); }
     *ctx->h_err = 0ull;
-    {   std::lock_guard<std::mutex> g(g_knob_mutex);                    // process-wide diagnostic defaults (mi355rt_debug_set_knob(NULL, ...))
-        for (const auto& kv : g_default_knobs) (void)apply_knob(ctx, kv.first, kv.second); }
+    apply_default_knobs(ctx);                                        // process-wide diagnostic defaults (mi355rt_debug_set_knob(NULL, ...): rt_debug.cpp)
     *out_ctx = ctx;
     return MI355RT_OK;
     });
@@ -450,11 +298,9 @@ static int render_samples(mi355rt_context* ctx, const mi355rt_options* opt, uint
     if (plan.rng_mode == MI355RT_RNG_REF) {
         if ((rc = ctx->fold_stack.ensure((size_t)n_rows * std::max(st.max_depth, 1u) * 3))) return rc;
         RefParams rp{};
-        rp.prims = ctx->prims.p; rp.mats = ctx->mats.p; rp.nodes = ctx->nodes.p; rp.tris = ctx->tris.p; rp.rows = d_rows_natural;
-        rp.sky = ctx->sky_w ? ctx->sky.p : nullptr; rp.sky_w = ctx->sky_w; rp.sky_h = ctx->sky_h; rp.textures = ctx->textures.p;
-        rp.out_packed = (uint32_t*)d_out_packed; rp.out_linear = (float*)d_out_linear; rp.fold_stack = ctx->fold_stack.p; rp.stats = ctx->stats.p;
-        rp.n_prims = ctx->n_prims; rp.n_mats = ctx->n_mats; rp.n_rows = n_rows;
-        std::memcpy(rp.miss, ctx->miss, 12); rp.cam = ctx->cam;
+        bind_geometry(ctx, rp); bind_shading(ctx, rp);
+        rp.rows = d_rows_natural; rp.out_packed = (uint32_t*)d_out_packed; rp.out_linear = (float*)d_out_linear; rp.fold_stack = ctx->fold_stack.p; rp.stats = ctx->stats.p;
+        rp.n_mats = ctx->n_mats; rp.n_rows = n_rows; rp.cam = ctx->cam;
         rp.width = st.width; rp.height = st.height; rp.spp = st.samples_per_pixel; rp.max_depth = st.max_depth;
         rp.seed_lo = plan.seed_lo; rp.seed_hi = plan.seed_hi;
         if (stats) HIP_TRY(hipEventRecord(ctx->ev[0], stream));
@@ -480,11 +326,9 @@ static int render_samples(mi355rt_context* ctx, const mi355rt_options* opt, uint
         HIP_TRY(hipMemsetAsync(ctx->counters.p, 0, (size_t)plan.n_bands * ctr_words * sizeof(uint32_t), stream));
 
         RenderParams p{};
-        p.prims = ctx->prims.p; p.mats = ctx->mats.p; p.nodes = ctx->nodes.p; p.tris = ctx->tris.p; p.rows = d_rows_processing;
-        p.sky = ctx->sky_w ? ctx->sky.p : nullptr; p.sky_w = ctx->sky_w; p.sky_h = ctx->sky_h; p.textures = ctx->textures.p;
-        p.radiance = ctx->radiance.p; p.stats = ctx->stats.p;
-        p.n_prims = ctx->n_prims; p.n_mats = ctx->n_mats;
-        std::memcpy(p.miss, ctx->miss, 12); p.cam = ctx->cam;
+        bind_geometry(ctx, p); bind_shading(ctx, p);
+        p.rows = d_rows_processing; p.radiance = ctx->radiance.p; p.stats = ctx->stats.p;
+        p.n_mats = ctx->n_mats; p.cam = ctx->cam;
         p.width = st.width; p.height = st.height; p.spp = plan.spp; p.max_depth = st.max_depth;
         p.width_f = plan.width_f; p.height_f = plan.height_f; p.inv_width_rn = plan.inv_width_rn; p.inv_height_rn = plan.inv_height_rn;
         p.seed_lo = plan.seed_lo; p.seed_hi = plan.seed_hi; p.sample0 = plan.sample0;
@@ -578,441 +422,6 @@ int mi355rt_context_render_progressive(mi355rt_context* ctx, const mi355rt_optio
     if (!d_accum) return fail(MI355RT_ERR_INVALID, "d_accum is null");
     if (sample_end <= sample_begin) return fail(MI355RT_ERR_INVALID, "sample_end must be greater than sample_begin");
     return render_samples(ctx, opt, sample_begin, sample_end, d_accum, d_out_packed, d_out_linear, hip_stream, stats);
-    });
-}
-
-// ---- ray queries (rt_query.hip): what does a ray hit in the resident scene? ------------------------------------------------------
-// They read the scene arrays only -- no workspace, no counters, no error word of their own -- so they neither wait on `done` nor
-// record it, and may run beside a render of the same context on another stream.  mi355rt_context_set_share is not consulted: the
-// kernels are plain grids that end with their rays.
-static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0u; }
-static void query_scene(const mi355rt_context* ctx, QueryParams& q) {
-    q.prims = ctx->prims.p; q.nodes = ctx->nodes.p; q.tris = ctx->tris.p; q.n_prims = ctx->n_prims;
-}
-
-int mi355rt_context_trace_rays(mi355rt_context* ctx, const void* d_rays, uint32_t n_rays, void* d_hits, void* hip_stream) {
-    return guard([&]() -> int {
-    static_assert(sizeof(mi355rt_ray) == 32 && sizeof(mi355rt_hit) == 48, "the query kernels read a ray as two 16-byte halves and write a record as three 16-byte words");
-    if (!ctx || !ctx->have_scene) return fail(MI355RT_ERR_INVALID, "context has no scene");
-    if (n_rays == 0) return MI355RT_OK;
-    if (!d_rays || !d_hits) return fail(MI355RT_ERR_INVALID, "trace_rays: d_rays / d_hits is null");
-    if (!aligned16(d_rays) || !aligned16(d_hits)) return fail(MI355RT_ERR_INVALID, "trace_rays: d_rays / d_hits must be 16-byte aligned");
-    HIP_TRY(hipSetDevice(ctx->device));
-    if (int erc = report_device_error(ctx)) return erc;              // an earlier asynchronous render on this context failed
-    QueryParams q{};
-    query_scene(ctx, q);
-    q.rays = d_rays; q.hits = d_hits; q.n = n_rays;
-    if (launch_query(q, ctx->has_mesh, hip_stream) != 0) return fail(MI355RT_ERR_HIP, "k_query_rays launch failed");
-    return MI355RT_OK;
-    });
-}
-
-// The device table (local output row -> absolute y) of a row selection, one per selection seen since set_scene; `sel.rows` is taken when a new one is made.
-// On return the table's upload is ordered before what is enqueued on `stream` next.
-static int query_row_table(mi355rt_context* ctx, RowSel& sel, hipStream_t stream, mi355rt_context::QueryRows*& table) {
-    table = nullptr;
-    for (auto& t : ctx->query_rows) if (t.rows == sel.rows) { table = &t; break; }
-    if (!table) {
-        if (ctx->query_rows.size() >= 16) { HIP_TRY(hipDeviceSynchronize()); ctx->query_rows_release(); }   // a caller that keeps changing its selection: start over
-        mi355rt_context::QueryRows t;
-        t.rows.swap(sel.rows); t.stream = stream;
-        if (hipMalloc((void**)&t.d, t.rows.size() * sizeof(uint32_t)) != hipSuccess) return fail(MI355RT_ERR_OOM, "hipMalloc(first_hits row table)");
-        ctx->query_rows.push_back(std::move(t));                     // (the vector's storage moves with it: the upload's source stays where it is)
-        table = &ctx->query_rows.back();
-        if (hipEventCreateWithFlags(&table->ready, hipEventDisableTiming) != hipSuccess ||
-            hipMemcpyAsync(table->d, table->rows.data(), table->rows.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream) != hipSuccess ||
-            hipEventRecord(table->ready, stream) != hipSuccess) {
-            (void)hipDeviceSynchronize();                            // a table that may not have arrived is not kept
-            (void)hipFree(table->d); if (table->ready) (void)hipEventDestroy(table->ready);
-            ctx->query_rows.pop_back();
-            return fail(MI355RT_ERR_HIP, "first_hits: row table upload failed");
-        }
-    } else if (table->stream != stream) HIP_TRY(hipStreamWaitEvent(stream, table->ready, 0));
-    return MI355RT_OK;
-}
-
-int mi355rt_context_first_hits(mi355rt_context* ctx, const mi355rt_options* opt, void* d_hits, void* hip_stream) {
-    return guard([&]() -> int {
-    if (!ctx || !ctx->have_scene) return fail(MI355RT_ERR_INVALID, "context has no scene");
-    if (!d_hits) return fail(MI355RT_ERR_INVALID, "first_hits: d_hits is null");
-    if (!aligned16(d_hits)) return fail(MI355RT_ERR_INVALID, "first_hits: d_hits must be 16-byte aligned");
-    if (opt && (opt->flags & ~MI355RT_FLAG_FIXED_AABB) != 0u) return fail(MI355RT_ERR_INVALID, "options.flags has unknown bits");
-    const mi355rt_settings& st = ctx->settings;
-    RowSel sel;
-    {   mi355rt_options rows_only{};                                 // rng_mode, seed and workspace_bytes are not this call's business
-        if (opt) { rows_only = *opt; rows_only.rng_mode = MI355RT_RNG_CTR; }
-        const int rc = select_rows(st, opt ? &rows_only : nullptr, sel); if (rc) return rc; }
-    if (opt && (opt->flags & MI355RT_FLAG_FIXED_AABB) != 0u)
-        return fail(MI355RT_ERR_UNSUPPORTED, "first_hits: MI355RT_FLAG_FIXED_AABB is not built for ray queries (they answer as the reference does)");
-    if (sel.rows.empty()) return MI355RT_OK;
-    HIP_TRY(hipSetDevice(ctx->device));
-    if (int erc = report_device_error(ctx)) return erc;              // an earlier asynchronous render on this context failed
-    mi355rt_context::QueryRows* table = nullptr;
-    if (int rc = query_row_table(ctx, sel, (hipStream_t)hip_stream, table)) return rc;
-    QueryParams q{};
-    query_scene(ctx, q);
-    q.rays = nullptr; q.hits = d_hits; q.rows = table->d; q.n = (uint32_t)(table->rows.size() * (size_t)st.width);   // (< 2^31: check_settings)
-    q.cam = ctx->cam; q.width = st.width; q.width_f = (float)st.width; q.height_f = (float)st.height;
-    magic_div(st.width, q.width_mul, q.width_shift);
-    if (launch_query(q, ctx->has_mesh, hip_stream) != 0) return fail(MI355RT_ERR_HIP, "k_query_pixels launch failed");
-    return MI355RT_OK;
-    });
-}
-
-// ---- occlusion queries (rt_occlusion.hip): does anything lie in front of t_max? -----------------------------------------------------------
-// The protocol of the ray queries: they read the scene arrays only, neither wait on `done` nor record it, and do not consult set_share.
-// Every refusal is rt_prepare.cpp's, before any HIP call.
-int mi355rt_context_occluded(mi355rt_context* ctx, const void* d_segments, uint32_t n, void* d_out, void* hip_stream) {
-    return guard([&]() -> int {
-    static_assert(sizeof(mi355rt_segment) == 32, "the kernel reads a segment as two 16-byte halves");
-    if (int rc = check_occluded_args(ctx != nullptr, ctx && ctx->have_scene, d_segments, n, d_out)) return rc;
-    if (n == 0) return MI355RT_OK;
-    HIP_TRY(hipSetDevice(ctx->device));
-    if (int erc = report_device_error(ctx)) return erc;              // an earlier asynchronous render on this context failed
-    OcclusionParams q{};
-    q.prims = ctx->prims.p; q.nodes = ctx->nodes.p; q.tris = ctx->tris.p; q.n_prims = ctx->n_prims;
-    q.segments = d_segments; q.out = (uint32_t*)d_out; q.n = n; q.may_exit = ctx->occlusion_may_exit ? 1u : 0u;
-    if (launch_occluded(q, ctx->has_mesh, hip_stream) != 0) return fail(MI355RT_ERR_HIP, "k_occluded launch failed");
-    return MI355RT_OK;
-    });
-}
-
-int mi355rt_context_ambient_occlusion(mi355rt_context* ctx, const mi355rt_options* opt, const mi355rt_ao_params* params, const void* d_hits, void* d_out,
-                                      void* hip_stream) {
-    return guard([&]() -> int {
-    static_assert(sizeof(mi355rt_hit) == 48 && sizeof(mi355rt_ao_params) == 16, "the kernel reads a hit record as three 16-byte words");
-    RowSel sel; AoPlan plan{};
-    const mi355rt_settings no_settings{};
-    if (int rc = plan_ambient_occlusion(ctx != nullptr, ctx && ctx->have_scene, ctx ? ctx->settings : no_settings, opt, params, d_hits, d_out, sel, plan)) return rc;
-    if (sel.rows.empty()) return MI355RT_OK;
-    const mi355rt_settings& st = ctx->settings;
-    HIP_TRY(hipSetDevice(ctx->device));
-    if (int erc = report_device_error(ctx)) return erc;              // an earlier asynchronous render on this context failed
-    mi355rt_context::QueryRows* table = nullptr;
-    if (int rc = query_row_table(ctx, sel, (hipStream_t)hip_stream, table)) return rc;
-    AoLaunch a{};
-    a.prims = ctx->prims.p; a.nodes = ctx->nodes.p; a.tris = ctx->tris.p; a.n_prims = ctx->n_prims;
-    a.hits = d_hits; a.out = (float*)d_out; a.rows = table->d; a.n = (uint32_t)(table->rows.size() * (size_t)st.width);   // (< 2^31: check_settings)
-    a.width = st.width; magic_div(st.width, a.width_mul, a.width_shift);
-    a.samples = plan.samples; a.log2_samples = plan.log2_samples; a.seed = plan.seed; a.radius = plan.radius;
-    a.may_exit = ctx->occlusion_may_exit ? 1u : 0u; a.form = (uint32_t)ctx->knob_ao_form;
-    if (launch_ambient_occlusion(a, ctx->has_mesh, hip_stream) != 0) return fail(MI355RT_ERR_HIP, "k_ao launch failed");
-    return MI355RT_OK;
-    });
-}
-
-// ---- radiance queries (rt_radiance.hip): whole paths along the caller's rays ----------------------------------------------------------------
-// What mi355rt_context_trace_radiance does with its context: the entry point itself stands with its kernels in rt_radiance.hip, behind the barrier, as
-// rt_noise.hip's do; this half needs the context struct.  The protocol of the ray queries: the call reads the scene arrays only, neither waits on
-// `done` nor records it, and does not consult set_share.  Every refusal, the item count and the grids are rt_prepare.cpp's (plan_radiance), before any HIP call.
-}  // extern "C"
-int mi355rt::context_trace_radiance(mi355rt_context* ctx, const mi355rt_radiance_params* params, const void* d_rays, uint32_t n_rays, void* d_accum,
-                                    void* d_out_linear, void* d_scratch, void* hip_stream) {
-    static_assert(sizeof(mi355rt_path_ray) == 32 && sizeof(mi355rt_radiance_params) == 32, "the kernel reads a ray as two 16-byte halves");
-    static_assert(RADIANCE_PLAN_BLOCK == RADIANCE_BLOCK_THREADS && RADIANCE_PLAN_ITEMS_MAX == RADIANCE_ITEMS_MAX, "plan_radiance cuts the grids the kernels are launched on");
-    RadiancePlan plan{};
-    if (int rc = plan_radiance(ctx != nullptr, ctx && ctx->have_scene, params, d_rays, n_rays, d_accum, d_out_linear, d_scratch,
-                               ctx ? (uint32_t)ctx->knob_radiance_items : 0u, RADIANCE_ITEMS_DEFAULT, plan)) return rc;
-    if (n_rays == 0) return MI355RT_OK;
-    HIP_TRY(hipSetDevice(ctx->device));
-    if (int erc = report_device_error(ctx)) return erc;              // an earlier asynchronous render on this context failed
-    RadianceParams p{};
-    p.prims = ctx->prims.p; p.mats = ctx->mats.p; p.nodes = ctx->nodes.p; p.tris = ctx->tris.p; p.n_prims = ctx->n_prims;
-    p.sky = ctx->sky_w ? ctx->sky.p : nullptr; p.sky_w = ctx->sky_w; p.sky_h = ctx->sky_h; p.textures = ctx->textures.p;
-    std::memcpy(p.miss, ctx->miss, sizeof p.miss);
-    p.rays = d_rays; p.scratch = (float*)d_scratch; p.n_items = plan.n_items; p.samples = plan.samples; p.sample_begin = params->sample_begin;
-    p.max_depth = params->max_depth; p.items_per_lane = plan.items_per_lane; p.seed_lo = plan.seed_lo; p.seed_hi = plan.seed_hi;
-    RadianceSum s{};
-    s.scratch = (const float*)d_scratch; s.accum = (float*)d_accum; s.out_linear = (float*)d_out_linear; s.n_rays = n_rays; s.samples = plan.samples;
-    s.accum_load = plan.accum_load; s.inv_total = plan.inv_total;
-    if (launch_radiance(p, s, ctx->has_mesh, plan.grid_paths, plan.grid_sum, hip_stream) != 0) return fail(MI355RT_ERR_HIP, "k_radiance launch failed");
-    return MI355RT_OK;
-}
-
-// ---- camera views (rt_view.hip): the rays of a pinhole or a thin lens made on the device, in front of the radiance queries' loop ----
-// The context halves of mi355rt_context_view_rays / mi355rt_context_render_view, whose entry points stand with their kernels in rt_view.hip, behind
-// the barrier.  The protocol of the ray queries; every refusal and the grids are rt_prepare.cpp's (plan_view_rays, plan_view), before any HIP call.
-static void view_params(const mi355rt_view* view, const ViewPlan& plan, ViewParams& v) {
-    static_assert(sizeof(DevCamera) == sizeof(mi355rt_camera) && sizeof(mi355rt_view) == 96 && sizeof(mi355rt_view) % 16 == 0, "a view carries set_scene's camera");
-    std::memcpy(&v.cam, &view->camera, sizeof v.cam);
-    v.width_f = (float)view->width; v.height_f = (float)view->height; v.width = view->width; v.centre = plan.centre;
-    v.lens_radius = view->lens_radius; v.focus_distance = view->focus_distance;
-}
-int mi355rt::context_view_rays(mi355rt_context* ctx, const mi355rt_view* view, uint32_t sample, uint64_t seed, void* d_rays, void* hip_stream) {
-    ViewPlan plan{};
-    if (int rc = plan_view_rays(ctx != nullptr, ctx && ctx->have_scene, view, d_rays, plan)) return rc;
-    HIP_TRY(hipSetDevice(ctx->device));
-    if (int erc = report_device_error(ctx)) return erc;              // an earlier asynchronous render on this context failed
-    ViewParams v{}; view_params(view, plan, v);
-    ViewRays r{};
-    r.rays = d_rays; r.n_pixels = plan.n_pixels; r.sample = sample; r.seed_lo = (uint32_t)seed; r.seed_hi = (uint32_t)(seed >> 32);
-    if (launch_view_rays(v, r, view->model, hip_stream) != 0) return fail(MI355RT_ERR_HIP, "k_view_rays launch failed");
-    return MI355RT_OK;
-}
-int mi355rt::context_render_view(mi355rt_context* ctx, const mi355rt_view* view, const mi355rt_radiance_params* params, void* d_accum, void* d_out_linear,
-                                 void* d_out_packed, void* d_scratch, void* hip_stream) {
-    ViewPlan plan{};
-    if (int rc = plan_view(ctx != nullptr, ctx && ctx->have_scene, view, params, d_accum, d_out_linear, d_out_packed, d_scratch,
-                           ctx ? (uint32_t)ctx->knob_radiance_items : 0u, RADIANCE_ITEMS_DEFAULT, plan)) return rc;
-    HIP_TRY(hipSetDevice(ctx->device));
-    if (int erc = report_device_error(ctx)) return erc;              // an earlier asynchronous render on this context failed
-    RadianceParams p{};
-    p.prims = ctx->prims.p; p.mats = ctx->mats.p; p.nodes = ctx->nodes.p; p.tris = ctx->tris.p; p.n_prims = ctx->n_prims;
-    p.sky = ctx->sky_w ? ctx->sky.p : nullptr; p.sky_w = ctx->sky_w; p.sky_h = ctx->sky_h; p.textures = ctx->textures.p;
-    std::memcpy(p.miss, ctx->miss, sizeof p.miss);
-    p.rays = nullptr; p.scratch = (float*)d_scratch; p.n_items = plan.r.n_items; p.samples = plan.r.samples; p.sample_begin = params->sample_begin;
-    p.max_depth = params->max_depth; p.items_per_lane = plan.r.items_per_lane; p.seed_lo = plan.r.seed_lo; p.seed_hi = plan.r.seed_hi;
-    ViewParams v{}; view_params(view, plan, v);
-    ViewSum s{};
-    s.sum.scratch = (const float*)d_scratch; s.sum.accum = (float*)d_accum; s.sum.out_linear = (float*)d_out_linear; s.sum.n_rays = plan.n_pixels;
-    s.sum.samples = plan.r.samples; s.sum.accum_load = plan.r.accum_load; s.sum.inv_total = plan.r.inv_total; s.out_packed = (uint32_t*)d_out_packed;
-    if (launch_view_paths(p, v, s, view->model, ctx->has_mesh, plan.r.grid_paths, plan.r.grid_sum, hip_stream) != 0) return fail(MI355RT_ERR_HIP, "k_view launch failed");
-    return MI355RT_OK;
-}
-
-// ---- surface probes (rt_probe.hip): cosine-hemisphere rays made on the device from the caller's points and normals, in front of the same loop ----
-// The context halves of mi355rt_context_probe_rays / mi355rt_context_probe_radiance, whose entry points stand with their kernels in rt_probe.hip,
-// behind the barrier.  The protocol of the ray queries; every refusal and the grids are rt_prepare.cpp's (plan_probe_rays, plan_probe), before any HIP call.
-int mi355rt::context_probe_rays(mi355rt_context* ctx, const void* d_probes, uint32_t n, uint32_t sample, uint64_t seed, void* d_rays, void* hip_stream) {
-    static_assert(sizeof(mi355rt_probe) == 32 && sizeof(mi355rt_probe) == sizeof(mi355rt_path_ray), "the kernel reads a probe as two 16-byte halves");
-    if (int rc = plan_probe_rays(ctx != nullptr, ctx && ctx->have_scene, d_probes, n, d_rays)) return rc;
-    if (n == 0) return MI355RT_OK;
-    HIP_TRY(hipSetDevice(ctx->device));
-    if (int erc = report_device_error(ctx)) return erc;              // an earlier asynchronous render on this context failed
-    ProbeParams b{}; b.probes = d_probes;
-    ProbeRaysOut r{};
-    r.rays = d_rays; r.n = n; r.sample = sample; r.seed_lo = (uint32_t)seed; r.seed_hi = (uint32_t)(seed >> 32);
-    if (launch_probe_rays(b, r, hip_stream) != 0) return fail(MI355RT_ERR_HIP, "k_probe_rays launch failed");
-    return MI355RT_OK;
-}
-int mi355rt::context_probe_radiance(mi355rt_context* ctx, const mi355rt_radiance_params* params, const void* d_probes, uint32_t n, void* d_accum,
-                                    void* d_out_linear, void* d_scratch, void* hip_stream) {
-    RadiancePlan plan{};
-    if (int rc = plan_probe(ctx != nullptr, ctx && ctx->have_scene, params, d_probes, n, d_accum, d_out_linear, d_scratch,
-                            ctx ? (uint32_t)ctx->knob_radiance_items : 0u, RADIANCE_ITEMS_DEFAULT, plan)) return rc;
-    if (n == 0) return MI355RT_OK;
-    HIP_TRY(hipSetDevice(ctx->device));
-    if (int erc = report_device_error(ctx)) return erc;              // an earlier asynchronous render on this context failed
-    RadianceParams p{};
-    p.prims = ctx->prims.p; p.mats = ctx->mats.p; p.nodes = ctx->nodes.p; p.tris = ctx->tris.p; p.n_prims = ctx->n_prims;
-    p.sky = ctx->sky_w ? ctx->sky.p : nullptr; p.sky_w = ctx->sky_w; p.sky_h = ctx->sky_h; p.textures = ctx->textures.p;
-    std::memcpy(p.miss, ctx->miss, sizeof p.miss);
-    p.rays = nullptr; p.scratch = (float*)d_scratch; p.n_items = plan.n_items; p.samples = plan.samples; p.sample_begin = params->sample_begin;
-    p.max_depth = params->max_depth; p.items_per_lane = plan.items_per_lane; p.seed_lo = plan.seed_lo; p.seed_hi = plan.seed_hi;
-    ProbeParams b{}; b.probes = d_probes;
-    RadianceSum s{};
-    s.scratch = (const float*)d_scratch; s.accum = (float*)d_accum; s.out_linear = (float*)d_out_linear; s.n_rays = n; s.samples = plan.samples;
-    s.accum_load = plan.accum_load; s.inv_total = plan.inv_total;
-    if (launch_probe_paths(p, b, s, ctx->has_mesh, plan.grid_paths, plan.grid_sum, hip_stream) != 0) return fail(MI355RT_ERR_HIP, "k_probe launch failed");
-    return MI355RT_OK;
-}
-extern "C" {
-
-// ---- the denoiser (rt_denoise.hip): an a-trous filter over a linear image, guided by first-hit records --------------------------------
-// The context names the device and carries the error word of its renders; nothing of it is read or written by the kernels, so the
-// call neither waits on `done` nor records it.  What is decided before a device is involved -- the arguments, the per-level constants -- is
-// rt_prepare.cpp's.
-int mi355rt_denoise_scratch_bytes(uint32_t width, uint32_t rows, uint64_t* out_bytes) {
-    return guard([&]() -> int { return denoise_scratch_bytes(width, rows, out_bytes); });
-}
-
-int mi355rt_context_denoise(mi355rt_context* ctx, uint32_t width, uint32_t rows, const mi355rt_denoise_params* params, const void* d_linear_in,
-                            const void* d_hits, void* d_scratch, void* d_out_linear, void* d_out_packed, void* hip_stream) {
-    return guard([&]() -> int {
-    static_assert(sizeof(mi355rt_hit) == 48 && sizeof(mi355rt_denoise_params) == 16, "the prepass reads a hit record as three 16-byte words");
-    if (!ctx) return fail(MI355RT_ERR_INVALID, "denoise: ctx is null");
-    DenoiseLaunch d{};
-    if (int rc = check_denoise_buffers(d_linear_in, d_hits, d_scratch, d_out_linear, d_out_packed)) return rc;
-    if (int rc = plan_denoise(width, rows, params, d.plan)) return rc;
-    HIP_TRY(hipSetDevice(ctx->device));
-    if (int erc = report_device_error(ctx)) return erc;              // an earlier asynchronous render on this context failed
-    d.in = (const float*)d_linear_in; d.hits = d_hits; d.scratch = d_scratch;
-    d.out_linear = (float*)d_out_linear; d.out_packed = (uint32_t*)d_out_packed; d.width = width; d.rows = rows; d.staged = ctx->knob_denoise_staged;
-    if (launch_denoise(d, hip_stream) != 0) return fail(MI355RT_ERR_HIP, "k_denoise launch failed");
-    return MI355RT_OK;
-    });
-}
-
-// Diagnostic hook (not part of the public header): which counter-mode kernel set_scene selected (KERNEL_* in rt_device.h).
-int mi355rt_debug_kernel_variant(mi355rt_context* ctx, uint32_t* out) {
-    return guard([&]() -> int {
-    if (!ctx || !out || !ctx->have_scene) return fail(MI355RT_ERR_INVALID, "context has no scene");
-    *out = ctx->variant;
-    return MI355RT_OK;
-    });
-}
-
-// Diagnostic hook (not part of the public header): the entry point the resident scene is launched on -- its kernel's name (a static string), how many of
-// its workgroups the device holds per CU, and its VGPRs.  Variant 14 has two (rt_device.h ENTRY_*): with and without a sky texture.  Returns the name, or
-// null for a context without a scene (nothing in here allocates or throws).
-const char* mi355rt_debug_kernel_entry(mi355rt_context* ctx, uint32_t* out_blocks_per_cu, uint32_t* out_vgprs) {
-    if (!ctx || !out_blocks_per_cu || !out_vgprs || !ctx->have_scene) return nullptr;
-    const uint32_t e = ctx->entry();
-    *out_blocks_per_cu = (uint32_t)ctx->blocks_per_cu[e][ctx->variant]; *out_vgprs = (uint32_t)ctx->vgprs[e][ctx->variant];
-    return entry_kernel_name(ctx->variant, e);
-}
-// ... and the same choice without a device or a context: the name of the kernel a scene on `variant` is launched on, with or without a sky texture.
-const char* mi355rt_debug_entry_kernel(uint32_t variant, int has_sky) {
-    return variant < KERNEL_VARIANTS ? entry_kernel_name(variant, variant_entry(variant, has_sky != 0)) : nullptr;
-}
-
-// Diagnostic hook (not part of the public header): what set_scene would upload and choose for `scene`, without a device -- no HIP call, no
-// context.  forced_variant: the "kernel" knob, -1 = the automatic choice.  Two calls, as mi355rt_bvh_build: with the arrays null it only
-// counts; with an array given, its n_* holds the capacity on entry.  prims / nodes / tris: DevPrim / DevNode / DevTri records (rt_device.h).
-int mi355rt_debug_prepare_scene(const mi355rt_scene* scene, int forced_variant, uint32_t* out_variant, uint32_t* out_inline_steps,
-                                void* prims, uint32_t* n_prims, void* nodes, uint32_t* n_nodes, void* tris, uint32_t* n_tris) {
-    return guard([&]() -> int {
-    if (!out_variant || !out_inline_steps || !n_prims || !n_nodes || !n_tris) return fail(MI355RT_ERR_INVALID, "debug_prepare_scene: null");
-    if (forced_variant < -1 || forced_variant >= (int)KERNEL_VARIANTS) return fail(MI355RT_ERR_INVALID, "knob kernel");
-    PreparedScene s;
-    const int rc = prepare_scene(scene, s); if (rc) return rc;
-    if ((prims && *n_prims < s.prims.size()) || (nodes && *n_nodes < s.nodes.size()) || (tris && *n_tris < s.tris.size())) return fail(MI355RT_ERR_INVALID, "debug_prepare_scene: capacity");
-    if (prims && !s.prims.empty()) std::memcpy(prims, s.prims.data(), s.prims.size() * sizeof(DevPrim));
-    if (nodes && !s.nodes.empty()) std::memcpy(nodes, s.nodes.data(), s.nodes.size() * sizeof(DevNode));
-    if (tris && !s.tris.empty()) std::memcpy(tris, s.tris.data(), s.tris.size() * sizeof(DevTri));
-    *n_prims = (uint32_t)s.prims.size(); *n_nodes = (uint32_t)s.nodes.size(); *n_tris = (uint32_t)s.tris.size();
-    *out_variant = choose_variant(s, forced_variant, built_variants());
-    *out_inline_steps = choose_inline_steps(s, -1);
-    return MI355RT_OK;
-    });
-}
-
-// Diagnostic hook (not part of the public header): the camera masks set_scene would build for `scene` under `camera` and `settings`, without a device.
-// options null: the absolute table, one word per pixel of the image; otherwise the table a render with those options reads, the selected rows in
-// processing order (image order: the processing-order experiment needs a device).  Two calls: with `out` null it only counts.  *n == 0: no table
-// (more than 32 primitives, or a scene that another kernel than forced_variant / the automatic choice's k_render_ctr_simple_qc serves).
-int mi355rt_debug_camera_masks(const mi355rt_scene* scene, const mi355rt_camera* camera, const mi355rt_settings* settings, const mi355rt_options* options,
-                               int forced_variant, uint32_t* out, uint64_t capacity, uint64_t* n) {
-    return guard([&]() -> int {
-    if (!camera || !n) return fail(MI355RT_ERR_INVALID, "debug_camera_masks: null");
-    if (forced_variant < -1 || forced_variant >= (int)KERNEL_VARIANTS) return fail(MI355RT_ERR_INVALID, "knob kernel");
-    int rc = check_settings(settings); if (rc) return rc;
-    PreparedScene s;
-    rc = prepare_scene(scene, s); if (rc) return rc;
-    std::vector<uint32_t> table, gathered;
-    if (choose_variant(s, forced_variant, built_variants()) == KERNEL_LOCKSTEP_SIMPLE_QC) {
-        DevCamera cam; std::memcpy(&cam, camera, sizeof cam);
-        build_camera_masks(s, cam, settings->width, settings->height, table);
-    }
-    if (options && !table.empty()) {
-        RowSel sel; rc = select_rows(*settings, options, sel); if (rc) return rc;
-        gather_camera_masks(table, settings->width, sel.rows.data(), sel.rows.size(), gathered);
-        table.swap(gathered);
-    }
-    *n = table.size();
-    if (out) { if (capacity < table.size()) return fail(MI355RT_ERR_INVALID, "debug_camera_masks: capacity"); if (!table.empty()) std::memcpy(out, table.data(), table.size() * sizeof(uint32_t)); }
-    return MI355RT_OK;
-    });
-}
-
-// Diagnostic hook (not part of the public header): what a render with these inputs would launch, without a device -- no HIP call, no context -- by the
-// plan_render, halve_bands, render_band and row_tables that render_samples calls.  args: the context's side of RenderPlanIn (device.PlanProbeArgs has
-// the same layout); row_cost: a per-image-row cost of the caller's (n_cost entries, 0 = none: image order).  `halvings` "the band did not fit" steps
-// are taken first; *halved = how many of them existed.  out_plan: a RenderPlan.  Two calls, as mi355rt_debug_prepare_scene: with bands / tables null
-// it only counts (*n_bands RenderBand records, 3 x *n_rows table entries); with an array given, its n_* holds the capacity on entry.
-struct PlanProbeArgs { uint32_t s0, s1, have_accum, variant, has_mesh, n_prims, row_probe, grid_div, guided_mult, block_slots[KERNEL_VARIANTS]; };
-int mi355rt_debug_plan_render(const mi355rt_settings* settings, const mi355rt_options* options, const void* args, const float* row_cost, uint32_t n_cost,
-                              uint32_t halvings, void* out_plan, uint32_t* halved, void* bands, uint32_t* n_bands, uint32_t* tables, uint32_t* n_rows) {
-    return guard([&]() -> int {
-    if (!args || !out_plan || !halved || !n_bands || !n_rows || (n_cost && !row_cost)) return fail(MI355RT_ERR_INVALID, "debug_plan_render: null");
-    int rc = check_settings(settings); if (rc) return rc;
-    const PlanProbeArgs a = *static_cast<const PlanProbeArgs*>(args);
-    if (a.variant >= KERNEL_VARIANTS) return fail(MI355RT_ERR_INVALID, "knob kernel");
-    if (a.s1 <= a.s0) return fail(MI355RT_ERR_INVALID, "sample_end must be greater than sample_begin");
-    if (a.grid_div < 1u || a.grid_div > 16u) return fail(MI355RT_ERR_INVALID, "share_of must be 1 .. 16");
-    if (a.guided_mult < 1u || a.guided_mult > 64u) return fail(MI355RT_ERR_INVALID, "knob guided_mult");
-    const RenderPlanIn in{settings, options, a.s0, a.s1, a.have_accum != 0u, a.variant, a.has_mesh != 0u, a.n_prims, n_cost != 0u, a.row_probe != 0u,
-                          a.block_slots, a.grid_div, a.guided_mult};
-    RowSel sel; RenderPlan plan;
-    rc = plan_render(in, sel, plan); if (rc) return rc;
-    for (*halved = 0; *halved < halvings && halve_bands(plan); ) ++*halved;
-    const bool counter_mode = plan.rng_mode == MI355RT_RNG_CTR;      // (the replay mode's one launch has no band record)
-    if (bands && counter_mode && plan.n_bands) {
-        if (*n_bands < plan.n_bands) return fail(MI355RT_ERR_INVALID, "debug_plan_render: capacity");
-        if (plan.block_threads == 0u) return fail(MI355RT_ERR_INVALID, "debug_plan_render: a retired variant has no launch");
-        for (uint32_t b = 0; b < plan.n_bands; ++b) static_cast<RenderBand*>(bands)[b] = render_band(plan, b);
-    }
-    *n_bands = counter_mode ? plan.n_bands : 0u;
-    if (tables) {
-        if (*n_rows < sel.rows.size()) return fail(MI355RT_ERR_INVALID, "debug_plan_render: capacity");
-        std::vector<uint32_t> t;
-        row_tables(sel.rows, plan.order_groups ? std::vector<float>(row_cost, row_cost + n_cost) : std::vector<float>(), plan.order_groups, t);
-        if (!t.empty()) std::memcpy(tables, t.data(), t.size() * sizeof(uint32_t));
-    }
-    *n_rows = (uint32_t)sel.rows.size();
-    std::memcpy(out_plan, &plan, sizeof plan);
-    return MI355RT_OK;
-    });
-}
-
-// Diagnostic hook (not part of the public header): the STATS_WORDS (40) raw device counters of the last render.
-int mi355rt_debug_read_counters(mi355rt_context* ctx, unsigned long long* out40) {
-    return guard([&]() -> int {
-    if (!ctx || !out40 || !ctx->stats.p) return fail(MI355RT_ERR_INVALID, "no counters");
-    HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(hipMemcpy(out40, ctx->stats.p, STATS_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    return MI355RT_OK;
-    });
-}
-
-// Diagnostic hook (not part of the public header): the row tables of the last render on this context -- 3 x n entries (natural, processing,
-// out_row; see rt_prepare.h row_tables()) -- and the per-image-row cost the processing order was built from (`cost`, `height` entries; may be null).
-int mi355rt_debug_read_row_tables(mi355rt_context* ctx, uint32_t* tables, uint32_t capacity_entries, uint32_t* n_rows, float* cost, uint32_t cost_capacity, uint32_t* n_cost) {
-    return guard([&]() -> int {
-    if (!ctx || !n_rows) return fail(MI355RT_ERR_INVALID, "null");
-    const size_t n = ctx->rows_host.size();
-    *n_rows = (uint32_t)n;
-    if (tables) { if (capacity_entries < 3 * n || ctx->tables_host.size() != 3 * n) return fail(MI355RT_ERR_INVALID, "row tables: capacity"); std::memcpy(tables, ctx->tables_host.data(), 3 * n * sizeof(uint32_t)); }
-    if (n_cost) *n_cost = (uint32_t)ctx->row_cost.size();
-    if (cost) { if (cost_capacity < ctx->row_cost.size()) return fail(MI355RT_ERR_INVALID, "row cost: capacity"); std::memcpy(cost, ctx->row_cost.data(), ctx->row_cost.size() * sizeof(float)); }
-    return MI355RT_OK;
-    });
-}
-
-int mi355rt_debug_read_wave_times(mi355rt_context* ctx, unsigned long long* out, uint32_t capacity_waves, uint32_t* n_waves) {
-    return guard([&]() -> int {
-    if (!ctx || !out || !n_waves) return fail(MI355RT_ERR_INVALID, "null");
-    HIP_TRY(hipSetDevice(ctx->device));
-    const uint32_t n = std::min(capacity_waves, ctx->wave_times_n);
-    if (n) HIP_TRY(hipMemcpy(out, ctx->wave_times.p, (size_t)n * WAVE_TIME_WORDS * 8, hipMemcpyDeviceToHost));
-    *n_waves = n;
-    return MI355RT_OK;
-    });
-}
-
-// Diagnostic hooks (not part of the public header): one Material::scatter / one HittableList::hit per record through the
-// device functions of the render kernels, on the context's resident scene.  Host pointers in and out; records are the
-// 16- / 6- / 12-word PODs of rt_device.h.
-int mi355rt_debug_scatter(mi355rt_context* ctx, const void* in_records, uint32_t n, void* out_records) {
-    return guard([&]() -> int {
-    if (!ctx || !ctx->have_scene || !in_records || !out_records) return fail(MI355RT_ERR_INVALID, "debug_scatter: null / no scene");
-    HIP_TRY(hipSetDevice(ctx->device));
-    const DebugScatterIn* in = static_cast<const DebugScatterIn*>(in_records);
-    for (uint32_t i = 0; i < n; ++i) if (in[i].material >= ctx->n_mats) return fail(MI355RT_ERR_INVALID, "debug_scatter: material index");
-    DevBuf<DebugScatterIn> d_in; DevBuf<DebugScatterOut> d_out;
-    int rc = d_in.ensure(n); if (!rc) rc = d_out.ensure(n);
-    if (!rc && n) {
-        if (hipMemcpy(d_in.p, in, n * sizeof(DebugScatterIn), hipMemcpyHostToDevice) != hipSuccess || launch_debug_scatter(ctx->mats.p, ctx->textures.p, d_in.p, d_out.p, n, nullptr) != 0 ||
-            hipMemcpy(out_records, d_out.p, n * sizeof(DebugScatterOut), hipMemcpyDeviceToHost) != hipSuccess) rc = fail(MI355RT_ERR_HIP, "debug_scatter");
-    }
-    d_in.release(); d_out.release();
-    return rc;
-    });
-}
-
-int mi355rt_debug_hit(mi355rt_context* ctx, const void* in_rays, uint32_t n, void* out_records) {
-    return guard([&]() -> int {
-    if (!ctx || !ctx->have_scene || !in_rays || !out_records) return fail(MI355RT_ERR_INVALID, "debug_hit: null / no scene");
-    HIP_TRY(hipSetDevice(ctx->device));
-    DevBuf<DebugHitIn> d_in; DevBuf<DebugHitOut> d_out;
-    int rc = d_in.ensure(n); if (!rc) rc = d_out.ensure(n);
-    if (!rc && n) {
-        if (hipMemcpy(d_in.p, in_rays, n * sizeof(DebugHitIn), hipMemcpyHostToDevice) != hipSuccess ||
-            launch_debug_hit(ctx->prims.p, ctx->n_prims, ctx->nodes.p, ctx->tris.p, d_in.p, d_out.p, n, nullptr) != 0 ||
-            hipMemcpy(out_records, d_out.p, n * sizeof(DebugHitOut), hipMemcpyDeviceToHost) != hipSuccess) rc = fail(MI355RT_ERR_HIP, "debug_hit");
-    }
-    d_in.release(); d_out.release();
-    return rc;
     });
 }
 

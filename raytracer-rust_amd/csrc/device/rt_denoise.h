@@ -1,5 +1,5 @@
 // rt_denoise.h -- launch interface of the denoise kernels (rt_denoise.hip): mi355rt_context_denoise / mi355rt_denoise.
-// Internal to libmi355rt.so, shared by rt_denoise.hip and rt_api.cpp.  The filter itself is defined in include/mi355rt.h.
+// Internal to libmi355rt.so, shared by rt_denoise.hip and rt_queries.cpp.  The filter itself is defined in include/mi355rt.h.
 #pragma once
 #include "rt_prepare.h"
 

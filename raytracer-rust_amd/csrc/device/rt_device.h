@@ -174,7 +174,7 @@ struct RefParams {               // MI355RT_RNG_REF: one lane per selected row
     uint32_t seed_lo, seed_hi;
 };
 
-// Diagnostic per-function entry points (tests only; mi355rt_debug_scatter / mi355rt_debug_hit in rt_api.cpp): one record per lane
+// Diagnostic per-function entry points (tests only; mi355rt_debug_scatter / mi355rt_debug_hit in rt_debug.cpp): one record per lane
 // through exactly the device functions the render kernels call.
 struct DebugScatterIn { uint32_t material, front_face; float rd[3], p[3], n[3]; uint32_t k0, k1, x, s, ray; };     // 16 words
 struct DebugScatterOut { float scattered, o[3], d[3], atten[3], emitted[3], pad[3]; };                              // 16 words

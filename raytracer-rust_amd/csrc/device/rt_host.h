@@ -1,5 +1,5 @@
-// rt_host.h -- the HIP-side pieces shared by the C-ABI sources of libmi355rt.so (rt_api.cpp: the context, its renders, queries and debug
-// hooks; rt_multi.cpp: the multi-device context; rt_oneshot.cpp: the calls with host buffers): HIP_TRY, device buffers, the scope that
+// rt_host.h -- the HIP-side pieces shared by the C-ABI sources of libmi355rt.so (rt_api.cpp: the context and its renders; rt_queries.cpp: the calls that
+// only read the resident scene; rt_debug.cpp: the debug hooks; rt_multi.cpp: the multi-device context; rt_oneshot.cpp: the calls with host buffers): HIP_TRY, device buffers, the scope that
 // puts the calling thread's device back, the options of a call that deals the strips itself, and the deal of a call's parts over host
 // threads.  The thread-local last error, the exception barrier of every extern "C" entry point and the row-selection rule of
 // mi355rt_options come with rt_prepare.h, the HIP-free half.  Not part of the public header.

@@ -39,7 +39,7 @@
 
 using namespace mi355rt;
 
-extern "C" int mi355rt_debug_read_counters(mi355rt_context* ctx, unsigned long long* out40);   // rt_api.cpp: the device counters of the last render
+extern "C" int mi355rt_debug_read_counters(mi355rt_context* ctx, unsigned long long* out40);   // rt_debug.cpp: the device counters of the last render
 
 namespace {
 

@@ -1,5 +1,5 @@
 // rt_occlusion.h -- launch interface of the occlusion kernels (rt_occlusion.hip): mi355rt_context_occluded / mi355rt_context_ambient_occlusion.
-// Internal to libmi355rt.so, shared by rt_occlusion.hip and rt_api.cpp.  Both queries are defined in include/mi355rt.h.
+// Internal to libmi355rt.so, shared by rt_occlusion.hip and rt_queries.cpp.  Both queries are defined in include/mi355rt.h.
 #pragma once
 #include "rt_device.h"
 

@@ -1,6 +1,6 @@
 // rt_oneshot.cpp -- the calls of include/mi355rt.h that take host buffers and give host buffers back, part of libmi355rt.so:
 // mi355rt_render, mi355rt_render_multi, mi355rt_render_progressive, mi355rt_render_progressive_multi, mi355rt_trace_rays, mi355rt_occluded,
-// mi355rt_trace_radiance (its body: oneshot_trace_radiance) and mi355rt_denoise.  Each is a client of the resident API and of nothing else (neither context struct is visible here): the checks that
+// mi355rt_trace_radiance and mi355rt_denoise.  Each is a client of the resident API and of nothing else (neither context struct is visible here): the checks that
 // need no device, a context (or a multi context) of its own, device buffers, the resident call, the copy back.  What they share stands
 // once: Call owns the context and the buffers of one call and gives them up on every way out; upload / copy_back name the buffer that
 // failed; render_chunks is what the two progressive calls do once they hold their context, query what the queries do; run_parts
@@ -12,7 +12,6 @@
 
 #include "../../../include/mi355rt.h"
 #include "rt_host.h"
-#include "rt_radiance.h"
 
 using namespace mi355rt;
 
@@ -269,11 +268,10 @@ int mi355rt_occluded(const mi355rt_scene* scene, const mi355rt_segment* segments
     });
 }
 
-// What mi355rt_trace_radiance does (its entry point stands in rt_radiance.hip, behind the barrier): the rays go up, the running sums go up (when the
-// call continues them) and come back; the scratch and the optional means are the call's own.
-}  // extern "C"
-int mi355rt::oneshot_trace_radiance(const mi355rt_scene* scene, const mi355rt_radiance_params* params, const mi355rt_path_ray* rays, uint32_t n_rays,
-                                    float* accum_in_out, float* out_linear) {
+// The rays go up, the running sums go up (when the call continues them) and come back; the scratch and the optional means are the call's own.
+int mi355rt_trace_radiance(const mi355rt_scene* scene, const mi355rt_radiance_params* params, const mi355rt_path_ray* rays, uint32_t n_rays,
+                           float* accum_in_out, float* out_linear) {
+    return guard([&]() -> int {
     if (!scene) return fail(MI355RT_ERR_INVALID, "trace_radiance: scene is null");
     if (!params) return fail(MI355RT_ERR_INVALID, "trace_radiance: params is null");
     if (params->flags != 0u) return fail(MI355RT_ERR_INVALID, "trace_radiance: params.flags must be 0");
@@ -291,8 +289,8 @@ int mi355rt::oneshot_trace_radiance(const mi355rt_scene* scene, const mi355rt_ra
         if (int rc = mi355rt_context_trace_radiance(call.ctx, params, d_rays, n_rays, d_accum, d_linear, d_scratch, nullptr)) return rc;
         return out_linear ? copy_back(out_linear, d_linear, (size_t)n_rays * 3, "linear") : MI355RT_OK;
     }, 4, params->sample_begin > 0u);
+    });
 }
-extern "C" {
 
 // Host buffers in, host buffers out: a context on device 0 (no scene), the image and the records uploaded, one call, the results copied back.
 int mi355rt_denoise(uint32_t width, uint32_t rows, const mi355rt_denoise_params* params, const float* linear_in, const mi355rt_hit* hits,

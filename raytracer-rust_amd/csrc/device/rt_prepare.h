@@ -68,7 +68,7 @@ int plan_ambient_occlusion(bool have_ctx, bool have_scene, const mi355rt_setting
 // decided before any HIP call.  Refusals in this order (MI355RT_ERR_INVALID and a text that names the argument): the parameters -- null, flags,
 // reserved, sample_begin >= sample_end --; with n_rays > 0 the pointers (d_rays / d_accum / d_scratch null or not 16-byte aligned, d_out_linear not
 // 4-byte aligned) and n_rays * samples >= 2^32; then the context and its scene.  n_rays == 0 passes with n_items == 0: nothing to launch.
-constexpr uint32_t RADIANCE_PLAN_BLOCK = 256, RADIANCE_PLAN_ITEMS_MAX = 64;      // (rt_radiance.h: RADIANCE_BLOCK_THREADS, RADIANCE_ITEMS_MAX; rt_api.cpp asserts it)
+constexpr uint32_t RADIANCE_PLAN_BLOCK = 256, RADIANCE_PLAN_ITEMS_MAX = 64;      // (rt_radiance.h: RADIANCE_BLOCK_THREADS, RADIANCE_ITEMS_MAX; rt_queries.cpp asserts it)
 struct RadiancePlan {
     uint64_t scratch_bytes;                                          // what mi355rt_radiance_scratch_bytes(n_rays, samples) reports
     uint32_t n_items, samples, items_per_lane;                       // n_rays * samples; sample_end - sample_begin; K

@@ -12,9 +12,9 @@
 //   k_probe_sum           radiance_sum<false>: k_radiance_sum's chain, instantiated here (no new branch in an old kernel).
 // The work per item is bounded: max_depth segments and at most PROBE_TRIES generator blocks, so there is no watchdog here either.
 // Every formula below is include/mi355rt.h's definition, in float32 in the order written (-ffp-contract=off); + - * / sqrt and compares only.
+// Kernels and launch_* functions only: the entry points stand in rt_queries.cpp, which binds the context's scene to these launches.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include "rt_host.h"
 #include "rt_device.h"
 #include "rt_probe.h"
 
@@ -102,23 +102,3 @@ int launch_probe_paths(const RadianceParams& p, const ProbeParams& b, const Radi
 }
 
 }  // namespace mi355rt
-
-using namespace mi355rt;
-
-// The two entry points of include/mi355rt.h, beside their kernels and behind the exception barrier.  What each does is the context's
-// (context_probe_rays, context_probe_radiance: rt_api.cpp) behind the HIP-free half's refusals (plan_probe_rays, plan_probe: rt_prepare.cpp).
-extern "C" {
-
-int mi355rt_context_probe_rays(mi355rt_context* ctx, const void* d_probes, uint32_t n, uint32_t sample, uint64_t seed, void* d_rays, void* hip_stream) {
-    return guard([&]() -> int {
-    return context_probe_rays(ctx, d_probes, n, sample, seed, d_rays, hip_stream);
-    });
-}
-
-int mi355rt_context_probe_radiance(mi355rt_context* ctx, const mi355rt_radiance_params* params, const void* d_probes, uint32_t n, void* d_accum, void* d_out_linear, void* d_scratch, void* hip_stream) {
-    return guard([&]() -> int {
-    return context_probe_radiance(ctx, params, d_probes, n, d_accum, d_out_linear, d_scratch, hip_stream);
-    });
-}
-
-}  // extern "C"

@@ -1,5 +1,5 @@
 // rt_query.h -- launch interface of the ray-query kernels (rt_query.hip): mi355rt_context_trace_rays / mi355rt_context_first_hits.
-// Internal to libmi355rt.so, shared by rt_query.hip and rt_api.cpp.
+// Internal to libmi355rt.so, shared by rt_query.hip and rt_queries.cpp.
 #pragma once
 #include "rt_device.h"
 

@@ -1,5 +1,5 @@
 // rt_radiance.h -- launch interface of the radiance-query kernels (rt_radiance.hip): mi355rt_context_trace_radiance.
-// Internal to libmi355rt.so, shared by rt_radiance.hip and rt_api.cpp.
+// Internal to libmi355rt.so, shared by rt_radiance.hip and rt_queries.cpp (the entry points; mi355rt_trace_radiance, the host-buffer call: rt_oneshot.cpp).
 #pragma once
 #include "rt_device.h"
 
@@ -38,13 +38,5 @@ constexpr uint32_t RADIANCE_ITEMS_DEFAULT = 8;
 // has_mesh: the list holds a mesh (set_scene knows) -- k_radiance_paths_mesh walks the BVHs per lane, k_radiance_paths is hit_scene's mesh-free instantiation.
 // grid_paths / grid_sum: plan_radiance's (rt_prepare.h).  The sum is enqueued behind the paths on the same stream.
 int launch_radiance(const RadianceParams& p, const RadianceSum& s, bool has_mesh, uint32_t grid_paths, uint32_t grid_sum, void* stream);
-
-// The host halves of the entry points, which stand in rt_radiance.hip behind the exception barrier (the layout of rt_noise.hip: entry points beside
-// their kernels).  context_trace_radiance needs the context struct (rt_api.cpp); oneshot_trace_radiance is a client of the public context calls on
-// rt_oneshot.cpp's query scaffold.  Neither may be called outside a guard().
-int context_trace_radiance(mi355rt_context* ctx, const mi355rt_radiance_params* params, const void* d_rays, uint32_t n_rays, void* d_accum,
-                           void* d_out_linear_or_null, void* d_scratch, void* hip_stream);
-int oneshot_trace_radiance(const mi355rt_scene* scene, const mi355rt_radiance_params* params, const mi355rt_path_ray* rays, uint32_t n_rays,
-                           float* accum_in_out, float* out_linear_or_null);
 
 }  // namespace mi355rt

@@ -22,9 +22,9 @@
 // were with the bodies in this file (profiles/isa_diff_views_vs_parent.txt).
 // ADDRESSING (MI355RT_RNG_CTR): ykey = row + seed (64 bit), rng.start(ykey lo, ykey hi, x, s); the path stands at ray 0, whose block 0 is NOT
 // drawn here (it belongs to whoever made the ray: words 0 / 1 are the render's pixel jitter); the scatter event after ray r draws from ray r + 1.
+// Kernels and launch_* functions only: the entry points stand in rt_queries.cpp, which binds the context's scene to these launches.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include "rt_host.h"
 #include "rt_device.h"
 #include "rt_radiance.h"
 
@@ -48,29 +48,3 @@ int launch_radiance(const RadianceParams& p, const RadianceSum& s, bool has_mesh
 }
 
 }  // namespace mi355rt
-
-using namespace mi355rt;
-
-// The three entry points of include/mi355rt.h, beside their kernels and behind the exception barrier.  What each does is the HIP-free half's
-// (radiance_scratch_bytes, rt_prepare.cpp), the context's (context_trace_radiance, rt_api.cpp) and the host-buffer scaffold's (oneshot_trace_radiance, rt_oneshot.cpp).
-extern "C" {
-
-int mi355rt_radiance_scratch_bytes(uint32_t n_rays, uint32_t samples, uint64_t* out_bytes) {
-    return guard([&]() -> int {
-    return radiance_scratch_bytes(n_rays, samples, out_bytes);
-    });
-}
-
-int mi355rt_context_trace_radiance(mi355rt_context* ctx, const mi355rt_radiance_params* params, const void* d_rays, uint32_t n_rays, void* d_accum, void* d_out_linear, void* d_scratch, void* hip_stream) {
-    return guard([&]() -> int {
-    return context_trace_radiance(ctx, params, d_rays, n_rays, d_accum, d_out_linear, d_scratch, hip_stream);
-    });
-}
-
-int mi355rt_trace_radiance(const mi355rt_scene* scene, const mi355rt_radiance_params* params, const mi355rt_path_ray* rays, uint32_t n_rays, float* accum_in_out, float* out_linear) {
-    return guard([&]() -> int {
-    return oneshot_trace_radiance(scene, params, rays, n_rays, accum_in_out, out_linear);
-    });
-}
-
-}  // extern "C"

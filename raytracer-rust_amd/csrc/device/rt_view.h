@@ -1,5 +1,5 @@
 // rt_view.h -- launch interface of the view kernels (rt_view.hip): mi355rt_context_view_rays, mi355rt_context_render_view.
-// Internal to libmi355rt.so, shared by rt_view.hip and rt_api.cpp.
+// Internal to libmi355rt.so, shared by rt_view.hip and rt_queries.cpp (the entry points).
 #pragma once
 #include "rt_device.h"
 #include "rt_radiance.h"
@@ -31,11 +31,5 @@ constexpr uint32_t VIEW_LENS_TRIES = 64;           // rejected tries of the lens
 // model: MI355RT_VIEW_* (plan_view refused every other value).  The path kernels are instantiated per model and per has_mesh; p.rays is not read.
 int launch_view_rays(const ViewParams& v, const ViewRays& r, uint32_t model, void* stream);
 int launch_view_paths(const RadianceParams& p, const ViewParams& v, const ViewSum& s, uint32_t model, bool has_mesh, uint32_t grid_paths, uint32_t grid_sum, void* stream);
-
-// The host halves of the entry points, which stand in rt_view.hip behind the exception barrier (as rt_radiance.hip's do).  Both need the context
-// struct (rt_api.cpp); neither may be called outside a guard().
-int context_view_rays(mi355rt_context* ctx, const mi355rt_view* view, uint32_t sample, uint64_t seed, void* d_rays, void* hip_stream);
-int context_render_view(mi355rt_context* ctx, const mi355rt_view* view, const mi355rt_radiance_params* params, void* d_accum, void* d_out_linear_or_null,
-                        void* d_out_packed_or_null, void* d_scratch, void* hip_stream);
 
 }  // namespace mi355rt

@@ -13,9 +13,9 @@
 // The view arrives as kernel arguments (ViewParams: scalar loads of launch constants); nothing of the caller's is read for it.  The work per item is
 // bounded: max_depth segments and at most VIEW_LENS_TRIES generator blocks, so there is no watchdog here either.
 // Every formula below is include/mi355rt.h's definition, in float32 in the order written (-ffp-contract=off).
+// Kernels and launch_* functions only: the entry points stand in rt_queries.cpp, which binds the context's scene to these launches.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include "rt_host.h"
 #include "rt_device.h"
 #include "rt_view.h"
 
@@ -124,29 +124,3 @@ int launch_view_paths(const RadianceParams& p, const ViewParams& v, const ViewSu
 }
 
 }  // namespace mi355rt
-
-using namespace mi355rt;
-
-// The three entry points of include/mi355rt.h, beside their kernels and behind the exception barrier.  What each does is the HIP-free half's
-// (view_scratch_bytes, rt_prepare.cpp) and the context's (context_view_rays, context_render_view: rt_api.cpp).
-extern "C" {
-
-int mi355rt_view_scratch_bytes(const mi355rt_view* view, uint32_t samples, uint64_t* out_bytes) {
-    return guard([&]() -> int {
-    return view_scratch_bytes(view, samples, out_bytes);
-    });
-}
-
-int mi355rt_context_view_rays(mi355rt_context* ctx, const mi355rt_view* view, uint32_t sample, uint64_t seed, void* d_rays, void* hip_stream) {
-    return guard([&]() -> int {
-    return context_view_rays(ctx, view, sample, seed, d_rays, hip_stream);
-    });
-}
-
-int mi355rt_context_render_view(mi355rt_context* ctx, const mi355rt_view* view, const mi355rt_radiance_params* params, void* d_accum, void* d_out_linear, void* d_out_packed, void* d_scratch, void* hip_stream) {
-    return guard([&]() -> int {
-    return context_render_view(ctx, view, params, d_accum, d_out_linear, d_out_packed, d_scratch, hip_stream);
-    });
-}
-
-}  // extern "C"

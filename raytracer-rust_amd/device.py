@@ -341,7 +341,7 @@ def _check(rc, what, library=None):
 
 def set_knob(name, value, library=None):
     """Diagnostic: process-wide default knob for every context created afterwards (also inside the one-shot calls).
-    Knobs: kernel, guided_mult, spin_idle, spin_entry, wave_times, row_order, cam_cull, resolve_skip, denoise_staged, ao_form, radiance_items, inline_steps, trav_min (rt_api.cpp)."""
+    Knobs: kernel, guided_mult, spin_idle, spin_entry, wave_times, row_order, cam_cull, resolve_skip, denoise_staged, ao_form, radiance_items, inline_steps, trav_min (rt_debug.cpp)."""
     L = library or lib()
     _check(L.mi355rt_debug_set_knob(None, name.encode(), int(value)), f"mi355rt_debug_set_knob({name})", L)
 
@@ -407,7 +407,7 @@ def camera_masks(scene, camera, settings, options=None, forced_variant=-1, libra
 KERNEL_VARIANTS, WORK_SHARDS = 15, 8                                  # rt_device.h
 
 
-class PlanProbeArgs(C.Structure):                                     # the context's side of a render's inputs (rt_api.cpp PlanProbeArgs)
+class PlanProbeArgs(C.Structure):                                     # the context's side of a render's inputs (rt_debug.cpp PlanProbeArgs)
     _fields_ = [(n, C.c_uint32) for n in ("s0", "s1", "have_accum", "variant", "has_mesh", "n_prims", "row_probe", "grid_div", "guided_mult")] + \
                [("block_slots", C.c_uint32 * KERNEL_VARIANTS)]
 

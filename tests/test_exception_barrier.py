@@ -50,24 +50,40 @@ def test_allocation_failures_come_back_as_error_codes(tmp_path):
 
 
 def test_every_entry_point_sits_behind_the_barrier():
-    """Source check: each `int mi355rt_*(...)` defined in a .cpp of csrc/device opens with the guard, and the host writers with theirs."""
+    """Source check: every `mi355rt_*` function defined at file scope in ANY .cpp or .hip of csrc/device is an export of the built library and the other
+    way round, each defined once; each `int` one opens with the guard; and the host writers open with theirs."""
+    import importlib
     import re
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    isa_stats = importlib.import_module("isa_stats")
+    build = importlib.import_module("raytracer-rust_amd.build")
     dev_dir = os.path.join(ROOT, "raytracer-rust_amd/csrc/device")
-    src = {n: open(os.path.join(dev_dir, n)).read() for n in sorted(os.listdir(dev_dir)) if n.endswith((".cpp", ".h"))}
-    defs, named = [], 0
-    for name, text in src.items():
-        if not name.endswith(".cpp"):
-            continue
-        named += len(re.findall(r"\nint mi355rt_\w+\(", text))
-        if 'extern "C" {' in text:
-            defs += re.findall(r"\nint (mi355rt_\w+)\((?:[^()]|\([^()]*\))*\) \{\n(.*)\n", text[text.index('extern "C" {'):])
-    # every definition there is: 25 in rt_api.cpp, 6 in rt_multi.cpp, 7 in rt_oneshot.cpp, and mi355rt_debug_has_variant, whose one line calls nothing that throws
-    assert len(defs) == 38 and named == 39 and len({n for n, _ in defs}) == 38
-    bare = [n for n, first in defs if "return guard([&]() -> int {" not in first]
-    assert not bare, bare
+    src = {n: open(os.path.join(dev_dir, n)).read() for n in sorted(os.listdir(dev_dir)) if n.endswith((".cpp", ".hip", ".h"))}
+    # a definition at file scope: return type and name at the start of a line, the parameter list, ` {`; what follows on that line and the next line
+    definition = re.compile(r"^(?:extern \"C\" )?([A-Za-z_][\w ]*?[ \*]+)(mi355rt_\w+)\((?:[^()]|\([^()]*\))*\) \{([^\n]*)(?=\n([^\n]*))", re.M)
+    defs = [(name, m.group(1).strip(), m.group(2), m.group(3), m.group(4)) for name, text in src.items() if not name.endswith(".h")
+            for m in definition.finditer(text)]
+    names = [d[2] for d in defs]
+    assert len(names) == len(set(names)), sorted(n for n in names if names.count(n) > 1)
+    # ... against the dynamic symbol table of the built library
+    table = subprocess.check_output([os.path.join(isa_stats.LLVM, "llvm-readelf"), "--dyn-syms", "-W", build.DEVICE_SO], text=True)
+    exported = {f[7] for f in (line.split() for line in table.splitlines()) if len(f) == 8 and f[3] == "FUNC" and f[6] != "UND" and f[7].startswith("mi355rt_")}
+    assert set(names) == exported, (sorted(set(names) - exported), sorted(exported - set(names)))
+    # every int-returning one, with what follows its opening brace.  The count is the parent tree's, where the barrier test saw 38 of them in three files
+    # and four per-feature tests the other 12 in their .hip files: 38 + 3 (rt_radiance.hip) + 3 (rt_view.hip) + 2 (rt_probe.hip) + 4 (rt_noise.hip) = 50, and
+    # mi355rt_debug_has_variant, whose one line calls nothing that throws.  Now: 9 in rt_api.cpp, 13 in rt_queries.cpp, 10 (and has_variant) in rt_debug.cpp,
+    # 6 in rt_multi.cpp, 8 in rt_oneshot.cpp, 4 in rt_noise.hip, none elsewhere; 7 more exports return something else (two destroys, a version, four strings).
+    ints = [d for d in defs if d[1] == "int"]
+    per_file = {name: sum(1 for d in ints if d[0] == name) for name in src if any(d[0] == name for d in ints)}
+    assert per_file == {"rt_api.cpp": 9, "rt_queries.cpp": 13, "rt_debug.cpp": 11, "rt_multi.cpp": 6, "rt_oneshot.cpp": 8, "rt_noise.hip": 4}, per_file
+    assert len(ints) == 51 and len(defs) == 58
+    bare = [d[2] for d in ints if d[3].strip() != "" or "return guard([&]() -> int {" not in d[4]]
+    assert bare == ["mi355rt_debug_has_variant"], bare
+    # the context struct is seen by the three sources that implement its calls, and by nothing else
+    assert sorted(n for n, text in src.items() if '"rt_context.h"' in text) == ["rt_api.cpp", "rt_debug.cpp", "rt_queries.cpp"]
     # the handlers besides the barrier's own: rt_prepare.cpp's (fail_noexcept lives with the last error) and what rt_api.cpp held before the
     # calls with host buffers moved out of it -- the thread deal (now rt_host.h) and the part of mi355rt_render_multi (now rt_oneshot.cpp)
-    assert sum(src[n].count("catch") for n in ("rt_api.cpp", "rt_oneshot.cpp", "rt_host.h", "rt_prepare.cpp")) >= 5
+    assert sum(src[n].count("catch") for n in ("rt_api.cpp", "rt_queries.cpp", "rt_debug.cpp", "rt_oneshot.cpp", "rt_host.h", "rt_prepare.cpp")) >= 5
     png = open(os.path.join(ROOT, "raytracer-rust_amd/csrc/host/png_write.cpp")).read()
     assert png.count("return mi355rt_host::guard(") == 3
     # ... and EVERY `int mi355rt_*(...)` the host library defines, whichever file it lives in (ADVICE r4: bvh_build* and scene_load_json had

@@ -209,20 +209,19 @@ def test_declared_and_exported_and_the_abi_number_did_not_move(native, abi):
 
 
 def test_every_entry_point_of_rt_probe_sits_behind_the_barrier():
-    """The regular expression of tests/test_exception_barrier.py, applied to rt_probe.hip: the two entry points live beside their kernels, each
-    opening with the guard; what they call -- context_probe_rays and context_probe_radiance in rt_api.cpp, which need the context struct -- is no entry point."""
+    """The regular expression of tests/test_exception_barrier.py, applied to the two entry points: they stand in rt_queries.cpp, which sees the context
+    struct, each defined once and opening with the guard, and no .hip file defines either."""
     dev_dir = os.path.join(ROOT, "raytracer-rust_amd/csrc/device")
-    text = open(os.path.join(dev_dir, "rt_probe.hip")).read()
-    assert len(re.findall(r"\nint mi355rt_\w+\(", text)) == 2
-    defs = re.findall(r"\nint (mi355rt_\w+)\((?:[^()]|\([^()]*\))*\) \{\n(.*)\n", text[text.index('extern "C" {'):])
-    assert {n for n, _ in defs} == set(NEW) and len(defs) == 2
+    src = {n: open(os.path.join(dev_dir, n)).read() for n in sorted(os.listdir(dev_dir)) if n.endswith((".cpp", ".hip"))}
+    text = src["rt_queries.cpp"]
+    defs = [(n, first) for n, first in re.findall(r"\nint (mi355rt_\w+)\((?:[^()]|\([^()]*\))*\) \{\n(.*)\n", text[text.index('extern "C" {'):]) if n in NEW]
+    assert sorted(n for n, _ in defs) == sorted(NEW) and len(defs) == 2
     bare = [n for n, first in defs if "return guard([&]() -> int {" not in first]
     assert not bare, bare
-    api = open(os.path.join(dev_dir, "rt_api.cpp")).read()
-    assert "int mi355rt::context_probe_rays(" in api and "int mi355rt::context_probe_radiance(" in api
-    for name in ("rt_api.cpp", "rt_multi.cpp", "rt_oneshot.cpp", "rt_prepare.cpp"):              # ... and neither is defined in the files that test counts
-        assert not re.search(r"\nint (?:" + "|".join(NEW) + r")\(", open(os.path.join(dev_dir, name)).read()), name
-    prepare = open(os.path.join(dev_dir, "rt_prepare.cpp")).read()
+    for name, other in src.items():                                                             # ... defined there only, and in no .hip
+        if name != "rt_queries.cpp":
+            assert not re.search(r"\nint (?:" + "|".join(NEW) + r")\(", other), name
+    prepare = src["rt_prepare.cpp"]
     for plan in ("int plan_probe(", "int plan_probe_rays("):
         assert plan in prepare and "hip" not in prepare.split(plan)[1].split("\n}\n")[0].lower()   # the plans hold no HIP call
     assert "#include <hip" not in prepare

@@ -82,21 +82,24 @@ def test_declared_and_exported_and_the_abi_number_did_not_move(native, abi):
 
 
 def test_every_entry_point_of_rt_radiance_sits_behind_the_barrier():
-    """The regular expression of tests/test_exception_barrier.py, applied to rt_radiance.hip: the three entry points live beside their kernels, as
-    rt_noise.hip's do, each opening with the guard; what they call -- context_trace_radiance in rt_api.cpp, which needs the context struct, and
-    oneshot_trace_radiance on rt_oneshot.cpp's query scaffold -- is no entry point."""
+    """The regular expression of tests/test_exception_barrier.py, applied to the three entry points: the two of the resident scene stand in rt_queries.cpp,
+    which sees the context struct, and mi355rt_trace_radiance with the other calls with host buffers in rt_oneshot.cpp, on its query scaffold; each is
+    defined once and opens with the guard, and no .hip file defines any of them."""
     dev_dir = os.path.join(ROOT, "raytracer-rust_amd/csrc/device")
-    text = open(os.path.join(dev_dir, "rt_radiance.hip")).read()
-    assert len(re.findall(r"\nint mi355rt_\w+\(", text)) == 3
-    defs = re.findall(r"\nint (mi355rt_\w+)\((?:[^()]|\([^()]*\))*\) \{\n(.*)\n", text[text.index('extern "C" {'):])
-    assert {n for n, _ in defs} == set(NEW) and len(defs) == 3
-    bare = [n for n, first in defs if "return guard([&]() -> int {" not in first]
+    src = {n: open(os.path.join(dev_dir, n)).read() for n in sorted(os.listdir(dev_dir)) if n.endswith((".cpp", ".hip"))}
+    defs = {n: re.findall(r"\nint (mi355rt_\w+)\((?:[^()]|\([^()]*\))*\) \{\n(.*)\n", text[text.index('extern "C" {'):]) for n, text in src.items() if 'extern "C" {' in text}
+    where = {"mi355rt_radiance_scratch_bytes": "rt_queries.cpp", "mi355rt_context_trace_radiance": "rt_queries.cpp", "mi355rt_trace_radiance": "rt_oneshot.cpp"}
+    assert set(where) == set(NEW)
+    for name, home in where.items():
+        assert [n for n, d in defs.items() for f, _ in d if f == name] == [home], name
+        assert sum(len(re.findall(r"\nint " + name + r"\(", text)) for text in src.values()) == 1, name
+    bare = [f for d in defs.values() for f, first in d if f in NEW and "return guard([&]() -> int {" not in first]
     assert not bare, bare
-    api, oneshot = (open(os.path.join(dev_dir, n)).read() for n in ("rt_api.cpp", "rt_oneshot.cpp"))
-    assert "int mi355rt::context_trace_radiance(" in api and "int mi355rt::oneshot_trace_radiance(" in oneshot
-    for name in ("rt_api.cpp", "rt_multi.cpp", "rt_oneshot.cpp", "rt_prepare.cpp"):              # ... and none of the three is defined in the files that test counts
-        src = open(os.path.join(dev_dir, name)).read()
-        assert not re.search(r"\nint (?:" + "|".join(NEW) + r")\(", src), name
+    for name, text in src.items():                                                              # ... and none of the three is defined in any .hip
+        if name.endswith(".hip"):
+            assert not re.search(r"\nint (?:" + "|".join(NEW) + r")\(", text), name
+    prepare = src["rt_prepare.cpp"]
+    assert "int plan_radiance(" in prepare and "hip" not in prepare.split("int plan_radiance(")[1].split("\n}\n")[0].lower()   # the plan holds no HIP call
 
 
 def test_scratch_bytes(native, abi):
