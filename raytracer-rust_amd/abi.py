@@ -183,6 +183,19 @@ class DenoiseParams(C.Structure):                         # mi355rt_denoise_para
 DENOISE_DEFAULTS = (5, 5, 2.0, 0.05)
 
 
+class ReprojectParams(C.Structure):                       # mi355rt_reproject_params (include/mi355rt_post.h), 16 bytes
+    _fields_ = [("max_history", u32), ("flags", u32), ("normal_min", f32), ("plane_tolerance", f32)]
+
+    @classmethod
+    def make(cls, max_history=32, normal_min=0.9, plane_tolerance=0.05, flags=0):
+        """The defaults are what mi355rt_post_reproject uses for a null pointer."""
+        return cls(max_history, flags, normal_min, plane_tolerance)
+
+
+REPROJECT_DEFAULTS = (32, 0, 0.9, 0.05)
+POST_ABI_VERSION = 1
+
+
 class NoiseParams(C.Structure):                           # mi355rt_noise_params, 32 bytes
     _fields_ = [("threshold", C.c_double), ("floor", C.c_double), ("min_chunks", u32), ("_pad", u32), ("allowed_above", u64)]
 

@@ -7,6 +7,9 @@
                              set_scene and the renders; rt_queries.cpp: the calls that only read the resident scene; rt_debug.cpp: the debug hooks and
                              the knobs; rt_prepare.cpp: scene preparation and the plans, no HIP in it; rt_multi.cpp: the multi-device context;
                              rt_oneshot.cpp: the calls with host buffers, clients of the public functions)
+  libmi355rt_post.so  hipcc: image-space post stages on device buffers, a library of its own (csrc/post; include/mi355rt_post.h): post_reproject.hip: the
+                             temporal reprojection's kernel; post_plan.cpp: its defaults, refusals and launch geometry, no HIP in it; post_api.cpp: the exports.
+                             Nothing of csrc/device is linked in (rt_math.h is included for the packing); kernel_hash() does not cover it.
   libmi355rt_host.so  g++:   CPU-side producers -- scene loader, mesh readers, BVH build, PNG (csrc/host)
   rt_render           g++:   CLI that stands in for the Rust `main` (csrc/tools)
 
@@ -24,6 +27,7 @@ CSRC = os.path.join(HERE, "csrc")
 
 DEVICE_SO = os.path.join(OUT, "libmi355rt.so")
 HOST_SO = os.path.join(OUT, "libmi355rt_host.so")
+POST_SO = os.path.join(OUT, "libmi355rt_post.so")
 CLI = os.path.join(OUT, "rt_render")
 
 # -ffp-contract=off: no FMA contraction -- the reference (rustc) never fuses a*b+c, and parity with the
@@ -162,6 +166,22 @@ def build_empty_pass_off(force=False, verbose=False):
     return build_device_variant("empty_pass_off", EMPTY_PASS_OFF_DEFINES, force=force, verbose=verbose)
 
 
+POST_SRCS = [os.path.join(CSRC, "post", f) for f in ("post_reproject.hip", "post_plan.cpp", "post_api.cpp")]
+POST_DEPS = POST_SRCS + [os.path.join(CSRC, "post", "post_plan.h"), os.path.join(CSRC, "device", "rt_math.h"), os.path.join(CSRC, "device", "rt_device.h"),
+                         os.path.join(ROOT, "include", "mi355rt.h"), os.path.join(ROOT, "include", "mi355rt_post.h")]
+
+
+def build_post(force=False, verbose=False):
+    """libmi355rt_post.so: the device library's compiler and flags (gfx950, -ffp-contract=off, no xnack), its own sources."""
+    os.makedirs(OUT, exist_ok=True)
+    if force or _stale(POST_SO, POST_DEPS):
+        cmd = [hipcc_path(), *HIPCC_FLAGS, "-o", POST_SO, *POST_SRCS]
+        if verbose:
+            print(" ".join(cmd))
+        subprocess.check_call(cmd)
+    return POST_SO
+
+
 def build_host(force=False, verbose=False):
     os.makedirs(OUT, exist_ok=True)
     srcs = _host_srcs()
@@ -205,7 +225,7 @@ def build_verify(force=False, verbose=False):
 
 
 def build_all(force=False, verbose=False):
-    return build_device(force, verbose=verbose), build_host(force, verbose=verbose), build_cli(force, verbose=verbose)
+    return build_device(force, verbose=verbose), build_host(force, verbose=verbose), build_cli(force, verbose=verbose), build_post(force, verbose=verbose)
 
 
 if __name__ == "__main__":
