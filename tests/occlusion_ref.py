@@ -1,6 +1,6 @@
 """Reference for the occlusion queries (not a test): a numpy float32 restatement of mi355rt.h's definitions.
 
-  pcg4d           the generator of rt_rng.h vectorised in uint32 (the oracle exposes the scalar one as oracle.pcg4d)
+  pcg4d           oracle/rng_np.py's, re-exported: the generator of rt_rng.h on uint32 arrays (the oracle exposes the scalar one as oracle.pcg4d)
   ball_floats     c_k = (float)(w_k >> 8) * 2^-24 * 2 - 1
   ao_directions   the directions N + v of the samples of one pixel (16 tries per sample, then v = 0); not normalised: the ray is
                   {P, d} and Ray::new -- in the oracle's hook as on the device -- normalises it once
@@ -9,29 +9,12 @@
                   ray does not depend on `samples` or `radius` -- so that the cases of a test share their oracle calls."""
 import numpy as np
 
+from oracle.rng_np import pcg4d  # noqa: F401  -- re-exported: tests/test_occlusion_reference_cpu.py pins it under this name
+
 F = np.float32
 U = np.uint32
 NO_HIT = 0xFFFFFFFF
 TRIES = 16
-
-
-def pcg4d(x, y, z, w):
-    """uint32 arrays (broadcast against each other) -> the four output words, each of the broadcast shape."""
-    with np.errstate(over="ignore"):
-        x, y, z, w = (np.asarray(v).astype(U) for v in np.broadcast_arrays(x, y, z, w))
-        a, c = U(1664525), U(1013904223)
-        x, y, z, w = x * a + c, y * a + c, z * a + c, w * a + c
-
-        def mix(x, y, z, w):
-            x = x + y * w
-            y = y + z * x
-            z = z + x * y
-            w = w + y * z
-            return x, y, z, w
-
-        x, y, z, w = mix(x, y, z, w)
-        x, y, z, w = x ^ (x >> U(16)), y ^ (y >> U(16)), z ^ (z >> U(16)), w ^ (w >> U(16))
-        return mix(x, y, z, w)
 
 
 def ball_floats(words):

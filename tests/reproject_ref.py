@@ -3,6 +3,8 @@ formula by formula, one rounding per operation in the order written -- every num
 and numpy fuses nothing.  The tests compare mi355rt_post_reproject's bytes with it and check its properties without a GPU."""
 import numpy as np
 
+from device_buffers import packed_of  # noqa: F401  -- re-exported: out_packed is packed_of(out[:, :3]), and tests/test_reproject_cpu.py pins it here
+
 F = np.float32
 NO_HIT = 0xFFFFFFFF
 DEFAULTS = (32, 0, 0.9, 0.05)                 # mi355rt_reproject_params for a null pointer: max_history, flags, normal_min, plane_tolerance
@@ -98,12 +100,3 @@ def reproject(cur, prev, hits_cur, color_cur, hits_prev=None, hist_prev=None, pa
     have = ws > F(0.0)
     out[have, :3], out[have, 3] = blended[have], nlen[have]
     return out
-
-
-def packed_of(linear):
-    """src/color.rs:87-93 in numpy float32: sqrt, clamp to [0, 1] (a NaN becomes 0 by the cast's rule), * 255, truncate; 0x00RRGGBB."""
-    with np.errstate(invalid="ignore"):
-        c = np.sqrt(np.asarray(linear, F))
-        c = np.where(c < 0, F(0), np.where(c > 1, F(1), c)).astype(F) * F(255.0)
-        w = np.where(np.isnan(c), 0, c).astype(np.uint32)
-    return ((w[..., 0] << 16) | (w[..., 1] << 8) | w[..., 2]).astype(np.uint32)

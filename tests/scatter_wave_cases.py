@@ -16,6 +16,8 @@ import functools
 
 import numpy as np
 
+from oracle.rng_np import block_of, ctr_block, path_base, pcg4d  # noqa: F401  -- re-exported: the tests reach them under these names
+
 f32, u32 = np.float32, np.uint32
 EPS = f32(1e-4)
 ONES = 0xFFFFFFFF
@@ -34,31 +36,6 @@ DEPTHS = ("shallow", "deep8", "deep16", "half12")
 
 
 # ---- the generator and the unit-ball draw, on uint32 / float32 arrays ---------------------------------------------------------------
-def pcg4d(x, y, z, w):
-    """Jarzynski & Olano's pcg4d on uint32 arrays (numpy wraps mod 2^32)."""
-    with np.errstate(over="ignore"):
-        A, Cc, S = u32(1664525), u32(1013904223), u32(16)
-        x, y, z, w = [np.asarray(v, u32) * A + Cc for v in (x, y, z, w)]
-        x = x + y * w; y = y + z * x; z = z + x * y; w = w + y * z
-        x = x ^ (x >> S); y = y ^ (y >> S); z = z ^ (z >> S); w = w ^ (w >> S)
-        x = x + y * w; y = y + z * x; z = z + x * y; w = w + y * z
-    return x, y, z, w
-
-
-def path_base(k0, k1, x, s):
-    return pcg4d(x, s, k0, k1)
-
-
-def block_of(base, ray, j):
-    """Block j of the event after ray `ray` of the paths with `base` (rt_rng.h: pcg4d(base + (0, 0, ray, j)))."""
-    with np.errstate(over="ignore"):
-        return pcg4d(base[0], base[1], base[2] + np.asarray(ray, u32), base[3] + np.asarray(j, u32))
-
-
-def ctr_block(k0, k1, x, s, ray, j):
-    return block_of(path_base(k0, k1, x, s), ray, j)
-
-
 def range11(w):
     """rand's random_range(-1.0..1.0) from a u32: (value1_2 - 1) * 2 + -1 with the 23 high bits as the mantissa of a float in [1, 2)."""
     v12 = ((np.asarray(w, u32) >> u32(9)) | u32(0x3F800000)).view(f32)

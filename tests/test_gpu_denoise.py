@@ -2,7 +2,7 @@
 linear result bit for bit (NaNs folded), the packed words against the oracle's color_to_u32 of the reference's linear result.  Real inputs
 (a render and the first hits of the same context), synthetic inputs with the values a filter gets wrong at the sizes where the tiling can go
 wrong, the plumbing (aliasing, one output only, guard words, repeats, a second stream, the one-shot) and the refusals on a live context."""
-import ctypes as C
+import types
 
 import numpy as np
 import pytest
@@ -10,12 +10,12 @@ import pytest
 import denoise_cases as cases
 import denoise_ref as ref
 import fuzz_scenes
+from device_buffers import Guarded
 from parity import assert_same_bits_nan_folded
 
 pytestmark = pytest.mark.gpu
 
 F = np.float32
-PATTERN = 0xA5
 GUARD = 256                                                              # bytes behind every output and behind the scratch
 
 
@@ -25,43 +25,29 @@ def pack(oracle_mod, lin):
     return np.array([f(float(r), float(g), float(b)) for r, g, b in flat], np.uint32).reshape(lin.shape[:2])
 
 
-class Buffers:
-    """Device buffers of one call: input, hits, scratch, both outputs, each output and the scratch with GUARD bytes of PATTERN behind it."""
+def buffers(device, lin, hits):
+    """Device buffers of one call: input, hits, scratch, both outputs, each with GUARD bytes of the pattern behind it."""
+    R, W = lin.shape[:2]
+    n = R * W
+    mk = lambda size, data=None: Guarded(size, data, GUARD)
+    return types.SimpleNamespace(R=R, W=W, n=n, lin=mk(n * 12, np.array(lin, F, order="C")), hits=mk(n * 48, hits), scratch=mk(device.denoise_scratch_bytes(W, R)),
+                                 out=mk(n * 12), packed=mk(n * 4))
 
-    def __init__(self, device, lin, hits):
-        import torch
-        self.R, self.W = lin.shape[:2]
-        n = self.R * self.W
-        self.n = n
-        self.lin = torch.from_numpy(np.array(lin, F, order="C")).cuda()
-        self.hits = torch.from_numpy(np.ascontiguousarray(hits).view(np.uint8).copy()).cuda()
-        self.scratch_bytes = device.denoise_scratch_bytes(self.W, self.R)
-        self.scratch = torch.full((self.scratch_bytes + GUARD,), PATTERN, dtype=torch.uint8, device="cuda")
-        self.out = torch.full((n * 12 + GUARD,), PATTERN, dtype=torch.uint8, device="cuda")
-        self.packed = torch.full((n * 4 + GUARD,), PATTERN, dtype=torch.uint8, device="cuda")
-        torch.cuda.synchronize()
 
-    def linear(self):
-        raw = self.out.cpu().numpy()
-        assert (raw[self.n * 12:] == PATTERN).all(), "the call wrote past the linear output"
-        return raw[:self.n * 12].view(F).reshape(self.R, self.W, 3).copy()
+def linear_of(b):
+    return b.out.read(F, "denoise: the linear output").reshape(b.R, b.W, 3)
 
-    def packed_words(self):
-        raw = self.packed.cpu().numpy()
-        assert (raw[self.n * 4:] == PATTERN).all(), "the call wrote past the packed output"
-        return raw[:self.n * 4].view(np.uint32).reshape(self.R, self.W).copy()
 
-    def scratch_guard_ok(self):
-        return bool((self.scratch[self.scratch_bytes:].cpu().numpy() == PATTERN).all())
+def packed_words(b):
+    return b.packed.read(np.uint32, "denoise: the packed output").reshape(b.R, b.W)
 
 
 def run(device, ctx, lin, hits, params=None, want_linear=True, want_packed=True, stream=None):
     import torch
-    b = Buffers(device, lin, hits)
-    ctx.denoise(b.W, b.R, b.lin.data_ptr(), b.hits.data_ptr(), b.scratch.data_ptr(), b.out.data_ptr() if want_linear else None,
-                b.packed.data_ptr() if want_packed else None, params, stream)
+    b = buffers(device, lin, hits)
+    ctx.denoise(b.W, b.R, b.lin.ptr, b.hits.ptr, b.scratch.ptr, b.out.ptr if want_linear else None, b.packed.ptr if want_packed else None, params, stream)
     torch.cuda.synchronize()
-    assert b.scratch_guard_ok(), "the call wrote past the scratch"
+    b.scratch.read(np.uint8, "denoise: the scratch")
     return b
 
 
@@ -69,9 +55,9 @@ def check(oracle_mod, device, abi, ctx, lin, hits, what, **kw):
     """One call with both outputs against the reference."""
     want = ref.denoise(lin, hits, **{**ref.DEFAULTS, **kw}) if kw else ref.denoise(lin, hits, **ref.DEFAULTS)
     b = run(device, ctx, lin, hits, abi.DenoiseParams.make(**kw) if kw else None)
-    got = b.linear()
+    got = linear_of(b)
     assert_same_bits_nan_folded(got, want, what)
-    got_packed, want_packed = b.packed_words(), pack(oracle_mod, want)
+    got_packed, want_packed = packed_words(b), pack(oracle_mod, want)
     bad = np.argwhere(got_packed != want_packed)
     assert not len(bad), f"{what}: packed differs at {bad[:6].tolist()}: got {got_packed[tuple(bad[0])]:#x} want {want_packed[tuple(bad[0])]:#x} ({len(bad)} px)"
     return got, want
@@ -179,27 +165,27 @@ def test_aliasing_single_outputs_repeats_and_the_one_shot(native, oracle_mod, ab
     W, H = 131, 70
     lin, hits = cases.synthetic(abi, W, H, 1000 + W * 7 + H)
     both = run(device, ctx, lin, hits)
-    want_lin, want_packed = both.linear(), both.packed_words()
+    want_lin, want_packed = linear_of(both), packed_words(both)
     assert_same_bits_nan_folded(want_lin, ref.denoise(lin, hits, **ref.DEFAULTS), "defaults")
     # twice: identical bytes
     again = run(device, ctx, lin, hits)
-    assert again.linear().tobytes() == want_lin.tobytes() and again.packed_words().tobytes() == want_packed.tobytes()
+    assert linear_of(again).tobytes() == want_lin.tobytes() and packed_words(again).tobytes() == want_packed.tobytes()
     # one output only: the other buffer is not touched
     only_lin = run(device, ctx, lin, hits, want_packed=False)
-    assert only_lin.linear().tobytes() == want_lin.tobytes() and (only_lin.packed.cpu().numpy() == PATTERN).all()
+    assert linear_of(only_lin).tobytes() == want_lin.tobytes() and only_lin.packed.untouched()
     only_packed = run(device, ctx, lin, hits, want_linear=False)
-    assert only_packed.packed_words().tobytes() == want_packed.tobytes() and (only_packed.out.cpu().numpy() == PATTERN).all()
+    assert packed_words(only_packed).tobytes() == want_packed.tobytes() and only_packed.out.untouched()
     # out == in
     for levels in (0, 1, 5):
         p = abi.DenoiseParams.make(levels=levels)
         sep = run(device, ctx, lin, hits, p)
-        b = Buffers(device, lin, hits)
-        b.out[:b.n * 12] = b.lin.view(torch.uint8).reshape(-1)
+        b = buffers(device, lin, hits)
+        b.out.upload(np.array(lin, F, order="C"))
         torch.cuda.synchronize()
-        ctx.denoise(W, H, b.out.data_ptr(), b.hits.data_ptr(), b.scratch.data_ptr(), b.out.data_ptr(), b.packed.data_ptr(), p)
+        ctx.denoise(W, H, b.out.ptr, b.hits.ptr, b.scratch.ptr, b.out.ptr, b.packed.ptr, p)
         torch.cuda.synchronize()
-        assert b.linear().tobytes() == sep.linear().tobytes() and b.packed_words().tobytes() == sep.packed_words().tobytes(), levels
-        assert b.scratch_guard_ok()
+        assert linear_of(b).tobytes() == linear_of(sep).tobytes() and packed_words(b).tobytes() == packed_words(sep).tobytes(), levels
+        b.scratch.read(np.uint8, "denoise: the scratch")
     # the one-shot: host buffers, a context of its own
     one_lin, one_packed = device.denoise(lin, hits)
     assert one_lin.tobytes() == want_lin.tobytes() and one_packed.tobytes() == want_packed.tobytes()
@@ -222,15 +208,15 @@ def test_a_call_on_a_second_stream_beside_a_render_of_the_same_context(native, o
         c.render(want_packed.data_ptr())
         lin, hits = cases.synthetic(abi, W, H, 77)
         alone = run(device, c, lin, hits)
-        b = Buffers(device, lin, hits)
+        b = buffers(device, lin, hits)
         s_render, s_filter = torch.cuda.Stream(), torch.cuda.Stream()
         torch.cuda.synchronize()
         c.render(packed.data_ptr(), None, None, s_render.cuda_stream)
-        c.denoise(W, H, b.lin.data_ptr(), b.hits.data_ptr(), b.scratch.data_ptr(), b.out.data_ptr(), b.packed.data_ptr(), None, s_filter.cuda_stream)
+        c.denoise(W, H, b.lin.ptr, b.hits.ptr, b.scratch.ptr, b.out.ptr, b.packed.ptr, None, s_filter.cuda_stream)
         c.render(packed.data_ptr(), None, None, s_render.cuda_stream)
         torch.cuda.synchronize()
         c.check()
-        assert b.linear().tobytes() == alone.linear().tobytes() and b.packed_words().tobytes() == alone.packed_words().tobytes()
+        assert linear_of(b).tobytes() == linear_of(alone).tobytes() and packed_words(b).tobytes() == packed_words(alone).tobytes()
         assert torch.equal(packed, want_packed)
     finally:
         c.close()
@@ -242,8 +228,8 @@ def test_refusals_on_a_live_context_leave_the_outputs_untouched(native, abi, ctx
     _, device = native
     W, H = 5, 3
     lin, hits = cases.synthetic(abi, W, H, 9)
-    b = Buffers(device, lin, hits)
-    i, h, s, o, p = b.lin.data_ptr(), b.hits.data_ptr(), b.scratch.data_ptr(), b.out.data_ptr(), b.packed.data_ptr()
+    b = buffers(device, lin, hits)
+    i, h, s, o, p = b.lin.ptr, b.hits.ptr, b.scratch.ptr, b.out.ptr, b.packed.ptr
     P = abi.DenoiseParams.make
     calls = [lambda: ctx.denoise(W, H, 0, h, s, o, p), lambda: ctx.denoise(W, H, i, 0, s, o, p), lambda: ctx.denoise(W, H, i, h, 0, o, p),
              lambda: ctx.denoise(W, H, i, h, s, 0, 0), lambda: ctx.denoise(W, H, i, h + 8, s, o, p), lambda: ctx.denoise(W, H, i, h, s + 4, o, p),
@@ -257,9 +243,8 @@ def test_refusals_on_a_live_context_leave_the_outputs_untouched(native, abi, ctx
             call()
         assert e.value.rc == abi.ERR_INVALID, k
     torch.cuda.synchronize()
-    for t in (b.out, b.packed, b.scratch):
-        assert (t.cpu().numpy() == PATTERN).all()
+    assert b.out.untouched() and b.packed.untouched() and b.scratch.untouched()
     assert device.lib().mi355rt_context_check(ctx._h) == 0
     ctx.denoise(W, H, i, h, s, o, p)                                     # and the context still works
     torch.cuda.synchronize()
-    assert_same_bits_nan_folded(b.linear(), ref.denoise(lin, hits, **ref.DEFAULTS), "after the refusals")
+    assert_same_bits_nan_folded(linear_of(b), ref.denoise(lin, hits, **ref.DEFAULTS), "after the refusals")

@@ -11,12 +11,12 @@ import pytest
 import occlusion_ref as R
 import test_gpu_ray_queries as Q
 from conftest import load_for_both
+from device_buffers import Guarded
 
 pytestmark = pytest.mark.gpu
 
 F = np.float32
 U = np.uint32
-PATTERN = 0xA5
 EPS = F(1e-4)
 
 
@@ -28,17 +28,15 @@ def segments_of(abi, origins, dirs, t_max):
     return s
 
 
-def run_occluded(ctx, seg, n=None, stream=None, extra=8):
+def run_occluded(ctx, seg, n=None, stream=None):
     import torch
     n = len(seg) if n is None else n
     d_seg = torch.from_numpy(np.ascontiguousarray(seg).view(F).reshape(-1, 8).copy()).cuda()
-    d_out = torch.full(((n + extra) * 4,), PATTERN, dtype=torch.uint8, device="cuda")
+    d_out = Guarded(n * 4, guard=8 * 4)
     torch.cuda.synchronize()
-    ctx.occluded(d_seg.data_ptr(), n, d_out.data_ptr(), stream)
+    ctx.occluded(d_seg.data_ptr(), n, d_out.ptr, stream)
     torch.cuda.synchronize()
-    raw = d_out.cpu().numpy()
-    assert (raw[n * 4:] == PATTERN).all() and len(raw) == (n + extra) * 4, "the query wrote past word n - 1"
-    out = raw[:n * 4].view(U).copy()
+    out = d_out.read(U, "occluded: the words")
     assert np.isin(out, (0, 1)).all(), "a word was not written (or is neither 0 nor 1)"
     return out
 
@@ -235,21 +233,17 @@ def test_the_trap_scene(b_first, native, oracle_mod, abi):
 
 
 # ---- 3: ambient occlusion -------------------------------------------------------------------------------------------------------------------
-def run_ao(device, abi, ctx, W, H, params, options=None, stream=None, extra=8, hits=None):
+def run_ao(device, abi, ctx, W, H, params, options=None, stream=None):
     """first_hits and ambient_occlusion for the same options -> (hit records, float32 [rows * W]); guard floats behind the output stay untouched."""
     import torch
     rows = abi.rows_selected(H, options)
     n = len(rows) * W
-    d_hits = Q.hit_buffer(n) if hits is None else hits
-    d_out = torch.full(((n + extra) * 4,), PATTERN, dtype=torch.uint8, device="cuda")
+    d_hits, d_out = Q.hit_buffer(n), Guarded(n * 4, guard=8 * 4)
     torch.cuda.synchronize()
-    if hits is None:
-        ctx.first_hits(d_hits.data_ptr(), options, stream)
-    ctx.ambient_occlusion(d_hits.data_ptr(), d_out.data_ptr(), params, options, stream)
+    ctx.first_hits(d_hits.ptr, options, stream)
+    ctx.ambient_occlusion(d_hits.ptr, d_out.ptr, params, options, stream)
     torch.cuda.synchronize()
-    raw = d_out.cpu().numpy()
-    assert (raw[n * 4:] == PATTERN).all(), "the pass wrote past float n - 1"
-    return Q.read_hits(abi, d_hits, n), raw[:n * 4].view(F).copy(), rows
+    return Q.read_hits(abi, d_hits), d_out.read(F, "ambient_occlusion: the floats"), rows
 
 
 def assert_ao(got, want, what):
@@ -373,8 +367,8 @@ def test_repeats_a_call_beside_a_render_and_the_refusals(native, oracle_mod, abi
         torch.cuda.synchronize()
         ctx.render(packed.data_ptr(), None, None, s_render.cuda_stream)
         ctx.occluded(d_seg.data_ptr(), len(seg), d_words.data_ptr(), s_query.cuda_stream)
-        ctx.first_hits(d_hits.data_ptr(), opt, s_query.cuda_stream)
-        ctx.ambient_occlusion(d_hits.data_ptr(), d_ao.data_ptr(), prm, opt, s_query.cuda_stream)
+        ctx.first_hits(d_hits.ptr, opt, s_query.cuda_stream)
+        ctx.ambient_occlusion(d_hits.ptr, d_ao.data_ptr(), prm, opt, s_query.cuda_stream)
         ctx.render(packed.data_ptr(), None, None, s_render.cuda_stream)
         torch.cuda.synchronize()
         ctx.check()
@@ -385,7 +379,7 @@ def test_repeats_a_call_beside_a_render_and_the_refusals(native, oracle_mod, abi
         # refusals on a live context: nothing is launched, nothing is written
         fresh = torch.full((64,), 0x5A5A5A5A, dtype=torch.int32, device="cuda")
         torch.cuda.synchronize()
-        p, hp = fresh.data_ptr(), d_hits.data_ptr()
+        p, hp = fresh.data_ptr(), d_hits.ptr
         with pytest.raises(device.RenderError) as e:
             ctx.ambient_occlusion(hp, p, prm, abi.Options.make(flags=abi.FLAG_FIXED_AABB))
         assert e.value.rc == abi.ERR_UNSUPPORTED

@@ -9,58 +9,27 @@ import pytest
 import probe_cases as PC
 import view_cases as VC
 from conftest import load_for_both
+from device_buffers import RadianceBuffers, scene_contexts
 
 pytestmark = pytest.mark.gpu
 
 F = np.float32
-PATTERN = 0xA5
-GUARD = 64                                                              # bytes behind every buffer a call writes: they keep the pattern
 
 
 # ---- device plumbing ------------------------------------------------------------------------------------------------------------------
-class Buffers:
-    """The device buffers of n probes and up to `samples` samples per call: probes, rays, float4 sums, means, scratch; guard bytes behind each."""
-
-    def __init__(self, device, probes, samples=1, fill_nan=True):
-        import torch
-        self.n = n = len(probes)
-        self.scratch_bytes = device.radiance_scratch_bytes(n, samples)
-        mk = lambda size: torch.full((size + GUARD,), PATTERN, dtype=torch.uint8, device="cuda")
-        self.probes, self.rays, self.accum, self.linear, self.scratch = mk(n * 32), mk(n * 32), mk(n * 16), mk(n * 12), mk(self.scratch_bytes)
-        self._put(self.probes, probes)
-        if fill_nan:
-            self.accum[:n * 16].view(torch.float32).fill_(float("nan"))   # a call with sample_begin == 0 must not read the sums
-
-    def _put(self, t, records):
-        import torch
-        assert records.dtype.itemsize == 32 and len(records) == self.n
-        t[:self.n * 32].copy_(torch.from_numpy(np.ascontiguousarray(records).view(np.uint8).reshape(-1).copy()))
-
-    def upload_rays(self, rays):
-        self._put(self.rays, rays)
-
-    def read_rays(self, abi):
-        r = self.rays.cpu().numpy()
-        assert (r[self.n * 32:] == PATTERN).all(), "probe_rays wrote past ray n - 1"
-        return r[:self.n * 32].view(abi.PATH_RAY_DTYPE).copy()
-
-    def read(self):
-        """(sums float32 [n, 4], means float32 [n, 3]) after checking the guards."""
-        n = self.n
-        a, l, s = (t.cpu().numpy() for t in (self.accum, self.linear, self.scratch))
-        assert (a[n * 16:] == PATTERN).all() and (l[n * 12:] == PATTERN).all(), "probe_radiance wrote past probe n - 1"
-        assert (s[self.scratch_bytes:] == PATTERN).all(), "probe_radiance wrote past its scratch"
-        return a[:n * 16].view(F).reshape(-1, 4).copy(), l[:n * 12].view(F).reshape(-1, 3).copy()
+def buffers(device, probes, samples=1, fill_nan=True):
+    """The buffers of n probes and up to `samples` samples per call, the probe records among them."""
+    return RadianceBuffers("probe_radiance", len(probes), device.radiance_scratch_bytes(len(probes), samples), probes=probes, fill_nan=fill_nan)
 
 
 def probe_radiance(ctx, abi, buf, begin, end, depth=PC.DEPTH, seed=0, stream=None):
-    ctx.probe_radiance(abi.RadianceParams.make(begin, end, depth, seed), buf.probes.data_ptr(), buf.n, buf.accum.data_ptr(), buf.scratch.data_ptr(),
-                       buf.linear.data_ptr(), stream)
+    ctx.probe_radiance(abi.RadianceParams.make(begin, end, depth, seed), buf.probes.ptr, buf.n, buf.accum.ptr, buf.scratch.ptr,
+                       buf.linear.ptr, stream)
 
 
 def one_call(device, abi, ctx, probes, S, depth=PC.DEPTH, seed=0):
     import torch
-    buf = Buffers(device, probes, S)
+    buf = buffers(device, probes, S)
     probe_radiance(ctx, abi, buf, 0, S, depth, seed)
     torch.cuda.synchronize()
     ctx.check()
@@ -69,22 +38,15 @@ def one_call(device, abi, ctx, probes, S, depth=PC.DEPTH, seed=0):
 
 def by_query(device, abi, oracle_mod, ctx, probes, S, depth=PC.DEPTH, seed=0):
     """The probes through mi355rt_context_trace_radiance: one call per sample along the maker's rays, the sums carried.  (sums, means)."""
-    import torch
-    buf = Buffers(device, probes, 1)
-    for s in range(S):
-        buf.upload_rays(PC.probe_rays(oracle_mod, abi, probes, s, seed))
-        ctx.trace_radiance(abi.RadianceParams.make(s, s + 1, depth, seed), buf.rays.data_ptr(), buf.n, buf.accum.data_ptr(), buf.scratch.data_ptr(), buf.linear.data_ptr())
-    torch.cuda.synchronize()
-    ctx.check()
-    return buf.read()
+    return buffers(device, probes).by_query(ctx, abi, S, lambda s: PC.probe_rays(oracle_mod, abi, probes, s, seed), depth, seed)
 
 
 def device_rays(device, abi, ctx, probes, s, seed):
     import torch
-    buf = Buffers(device, probes)
-    ctx.probe_rays(buf.probes.data_ptr(), buf.n, s, buf.rays.data_ptr(), seed)
+    buf = buffers(device, probes)
+    ctx.probe_rays(buf.probes.ptr, buf.n, s, buf.rays.ptr, seed)
     torch.cuda.synchronize()
-    return buf.read_rays(abi)
+    return buf.read_rays(abi, "probe_rays")
 
 
 def sphere_scene(abi, host, centre, radius, colour, miss):
@@ -117,14 +79,7 @@ def sets(scenes, oracle_mod, abi):
 @pytest.fixture(scope="module")
 def contexts(native, abi, scenes):
     """One context per scene, with a view the calls never look at."""
-    _, device = native
-    out = {}
-    for name, sc in scenes.items():
-        out[name] = device.Context(0)
-        out[name].set_scene(sc, abi.Camera(), abi.Settings(1, 1, 1, 1))
-    yield out
-    for c in out.values():
-        c.close()
+    yield from scene_contexts(native[1], abi, scenes)
 
 
 # ---- 1: the rays ----------------------------------------------------------------------------------------------------------------------------
@@ -203,7 +158,7 @@ def test_any_chunking_gives_the_words_of_one_call(native, abi, sets, contexts):
     sums, means = whole(device, abi, contexts, sets)
     assert np.isfinite(sums).all() and (sums[:, :3] > 0).any()             # the NaN the sums were pre-filled with was not read
     for chunks in (((0, 5), (5, 16), (16, 17)), ((0, 16), (16, 17)), tuple((s, s + 1) for s in range(17))):
-        buf = Buffers(device, sets["cornell"], 16)                         # the scratch is sized for the largest chunk
+        buf = buffers(device, sets["cornell"], 16)                         # the scratch is sized for the largest chunk
         for a, b in chunks:
             probe_radiance(contexts["cornell"], abi, buf, a, b, PC.DEPTH, PC.SEEDS[1])
         torch.cuda.synchronize()
@@ -282,7 +237,7 @@ def test_beside_a_render_of_the_same_context(native, oracle_mod, abi, sets):
         torch.cuda.synchronize()
         s_render, s_probe = torch.cuda.Stream(), torch.cuda.Stream()
         packed = torch.zeros((H, W), dtype=torch.int32, device="cuda")
-        buf = Buffers(device, probes, 17)
+        buf = buffers(device, probes, 17)
         torch.cuda.synchronize()
         ctx.render(packed.data_ptr(), None, None, s_render.cuda_stream)
         probe_radiance(ctx, abi, buf, 0, 17, PC.DEPTH, 5, stream=s_probe.cuda_stream)
@@ -302,38 +257,37 @@ def test_refusals_leave_the_sums_untouched_and_one_probe_works(native, oracle_mo
     _, device = native
     ctx = contexts["cornell"]
     probes = sets["cornell"][:5]
-    buf = Buffers(device, probes, 4, fill_nan=False)
+    buf = buffers(device, probes, 4, fill_nan=False)
     prm = abi.RadianceParams.make(0, 4, PC.DEPTH)
 
     def refused(word, params=prm, probes_at=None, n=5, accum=None, scratch=None, linear=None):
         with pytest.raises(device.RenderError) as e:
-            ctx.probe_radiance(params, buf.probes.data_ptr() if probes_at is None else probes_at, n, buf.accum.data_ptr() if accum is None else accum,
-                               buf.scratch.data_ptr() if scratch is None else scratch, linear)
+            ctx.probe_radiance(params, buf.probes.ptr if probes_at is None else probes_at, n, buf.accum.ptr if accum is None else accum,
+                               buf.scratch.ptr if scratch is None else scratch, linear)
         assert e.value.rc == abi.ERR_INVALID and word in str(e.value) and "probe_radiance: " in str(e.value), (word, str(e.value))
 
     refused("params.sample_begin", params=abi.RadianceParams.make(4, 4, PC.DEPTH))
     refused("params.flags", params=abi.RadianceParams(0, 4, PC.DEPTH, 1, 0, 0))
     refused("params.reserved", params=abi.RadianceParams(0, 4, PC.DEPTH, 0, 0, 1))
-    refused("d_probes must be 16-byte aligned", probes_at=buf.probes.data_ptr() + 8)
-    refused("d_accum must be 16-byte aligned", accum=buf.accum.data_ptr() + 4)
-    refused("d_scratch must be 16-byte aligned", scratch=buf.scratch.data_ptr() + 8)
-    refused("d_out_linear must be 4-byte aligned", linear=buf.linear.data_ptr() + 2)
+    refused("d_probes must be 16-byte aligned", probes_at=buf.probes.ptr + 8)
+    refused("d_accum must be 16-byte aligned", accum=buf.accum.ptr + 4)
+    refused("d_scratch must be 16-byte aligned", scratch=buf.scratch.ptr + 8)
+    refused("d_out_linear must be 4-byte aligned", linear=buf.linear.ptr + 2)
     refused("split the call", params=abi.RadianceParams.make(0, 65536, PC.DEPTH), n=65536)
     with pytest.raises(device.RenderError) as e:
-        ctx.probe_radiance(prm, None, 5, buf.accum.data_ptr(), buf.scratch.data_ptr())
+        ctx.probe_radiance(prm, None, 5, buf.accum.ptr, buf.scratch.ptr)
     assert "d_probes is null" in str(e.value)
     with pytest.raises(device.RenderError) as e:
-        ctx.probe_rays(buf.probes.data_ptr(), 5, 0, buf.rays.data_ptr() + 8)
+        ctx.probe_rays(buf.probes.ptr, 5, 0, buf.rays.ptr + 8)
     assert "probe_rays: d_rays must be 16-byte aligned" in str(e.value)
     with pytest.raises(device.RenderError) as e:
-        ctx.probe_rays(buf.probes.data_ptr() + 4, 5, 0, buf.rays.data_ptr())
+        ctx.probe_rays(buf.probes.ptr + 4, 5, 0, buf.rays.ptr)
     assert "probe_rays: d_probes must be 16-byte aligned" in str(e.value)
     ctx.probe_radiance(prm, None, 0, None, None)                           # n == 0: MI355RT_OK, nothing is looked at
     ctx.probe_rays(None, 0, 0, None)
     torch.cuda.synchronize()
     ctx.check()
-    for t in (buf.accum, buf.linear, buf.scratch, buf.rays):
-        assert (t.cpu().numpy() == PATTERN).all()                           # nothing was enqueued
+    assert all(t.untouched() for t in (buf.accum, buf.linear, buf.scratch, buf.rays))      # nothing was enqueued
     # one probe, one sample: the query along the maker's ray, and the same words again
     one = sets["cornell"][7:8]
     sums, means = one_call(device, abi, ctx, one, 1, PC.DEPTH, 0)

@@ -11,48 +11,23 @@ import fuzz_scenes
 import radiance_cases as RC
 import scene_shapes as SS
 from conftest import load_for_both
+from device_buffers import PATTERN, RadianceBuffers, packed_of
 from parity import assert_parity, assert_same_bits_nan_folded
 
 pytestmark = pytest.mark.gpu
 
 F = np.float32
-PATTERN = 0xA5
-GUARD = 64                                                              # bytes behind every buffer the query writes: they keep the pattern
 
 
 # ---- device plumbing ------------------------------------------------------------------------------------------------------------------
-class Buffers:
-    """The device buffers of one query of n rays and up to `samples` samples per call: rays, float4 sums, means, scratch; guard bytes behind the three
-    the query writes.  fill_nan: the sums start as NaN (a call with sample_begin == 0 must not read them)."""
-
-    def __init__(self, device, n, samples, fill_nan=True):
-        import torch
-        self.n, self.samples = n, samples
-        self.scratch_bytes = device.radiance_scratch_bytes(n, samples)
-        self.rays = torch.zeros(max(n, 1) * 32, dtype=torch.uint8, device="cuda")
-        self.accum = torch.full((n * 16 + GUARD,), PATTERN, dtype=torch.uint8, device="cuda")
-        self.linear = torch.full((n * 12 + GUARD,), PATTERN, dtype=torch.uint8, device="cuda")
-        self.scratch = torch.full((self.scratch_bytes + GUARD,), PATTERN, dtype=torch.uint8, device="cuda")
-        if fill_nan and n:
-            self.accum[:n * 16].view(torch.float32).fill_(float("nan"))
-
-    def upload(self, rays):
-        import torch
-        assert rays.dtype.itemsize == 32 and len(rays) == self.n
-        self.rays.copy_(torch.from_numpy(np.ascontiguousarray(rays).view(np.uint8).reshape(-1).copy()))
-
-    def read(self, used_scratch_bytes=None):
-        """(sums float32 [n, 4], means float32 [n, 3]) after checking the guards."""
-        a, l, s = self.accum.cpu().numpy(), self.linear.cpu().numpy(), self.scratch.cpu().numpy()
-        assert (a[self.n * 16:] == PATTERN).all(), "the query wrote past sum n - 1"
-        assert (l[self.n * 12:] == PATTERN).all(), "the query wrote past mean n - 1"
-        assert (s[self.scratch_bytes if used_scratch_bytes is None else used_scratch_bytes:] == PATTERN).all(), "the query wrote past its scratch"
-        return a[:self.n * 16].view(F).reshape(-1, 4).copy(), l[:self.n * 12].view(F).reshape(-1, 3).copy()
+def buffers(device, n, samples, fill_nan=True):
+    """The buffers of one query of n rays and up to `samples` samples per call."""
+    return RadianceBuffers("trace_radiance", n, device.radiance_scratch_bytes(n, samples), fill_nan=fill_nan)
 
 
 def query(ctx, abi, buf, begin, end, depth, seed=0, stream=None, want_linear=True):
     prm = abi.RadianceParams.make(begin, end, depth, seed)
-    ctx.trace_radiance(prm, buf.rays.data_ptr(), buf.n, buf.accum.data_ptr(), buf.scratch.data_ptr(), buf.linear.data_ptr() if want_linear else None, stream)
+    ctx.trace_radiance(prm, buf.rays.ptr, buf.n, buf.accum.ptr, buf.scratch.ptr, buf.linear.ptr if want_linear else None, stream)
 
 
 def context_for(device, abi, sc):
@@ -63,16 +38,9 @@ def context_for(device, abi, sc):
 
 def render_by_query(device, abi, oracle_mod, sc, cam, W, H, S, depth, seed=0):
     """The image of `cam` through the query: one call per sample with that sample's camera rays, the sums carried.  float32 [H, W, 3]."""
-    import torch
     ctx = context_for(device, abi, sc)
     try:
-        buf = Buffers(device, W * H, 1)
-        for s in range(S):
-            buf.upload(RC.camera_rays(oracle_mod, abi, cam, W, H, s, seed))
-            query(ctx, abi, buf, s, s + 1, depth, seed)
-        torch.cuda.synchronize()
-        ctx.check()
-        sums, means = buf.read()
+        sums, means = buffers(device, W * H, 1).by_query(ctx, abi, S, lambda s: RC.camera_rays(oracle_mod, abi, cam, W, H, s, seed), depth, seed)
         assert (sums[:, 3].view(np.uint32) == 0).all()                      # the fourth word of a sum is written +0
         return means.reshape(H, W, 3)
     finally:
@@ -82,15 +50,6 @@ def render_by_query(device, abi, oracle_mod, sc, cam, W, H, S, depth, seed=0):
 def oracle_linear(oracle_mod, abi, sc, cam, W, H, S, depth, seed=0):
     _, linear, _ = oracle_mod.render(sc, cam, abi.Settings(W, H, S, depth), abi.Options.make(seed=seed), threads=4)
     return linear
-
-
-def packed_of(linear):
-    """renderer.rs:112-120 / color.rs:87-93 in numpy float32: sqrt, clamp to [0, 1] (NaN -> 0 by the cast's rule), * 255, truncate."""
-    with np.errstate(invalid="ignore"):
-        c = np.sqrt(np.asarray(linear, F))
-        c = np.where(c < 0, F(0), np.where(c > 1, F(1), c)).astype(F) * F(255.0)
-        w = np.where(np.isnan(c), 0, c).astype(np.uint32)
-    return (w[..., 0] << 16) | (w[..., 1] << 8) | w[..., 2]
 
 
 # ---- 1: exact against oracle.render ------------------------------------------------------------------------------------------------------
@@ -219,8 +178,8 @@ DEPTH = 12
 
 def one_call(device, abi, ctx, rays, S, depth=DEPTH, seed=5):
     import torch
-    buf = Buffers(device, len(rays), S)
-    buf.upload(rays)
+    buf = buffers(device, len(rays), S)
+    buf.rays.upload(rays)
     query(ctx, abi, buf, 0, S, depth, seed)
     torch.cuda.synchronize()
     return buf.read()
@@ -247,8 +206,8 @@ def test_any_chunking_gives_the_words_of_one_call(S, native, abi, cornell_ctx):
     sums, means = whole(device, abi, ctx, S)
     assert np.isfinite(sums).all() and (sums[:, :3] > 0).any()             # the NaN the sums were pre-filled with was not read
     # S calls of one sample
-    buf = Buffers(device, len(rays), 1)
-    buf.upload(rays)
+    buf = buffers(device, len(rays), 1)
+    buf.rays.upload(rays)
     for s in range(S):
         query(ctx, abi, buf, s, s + 1, DEPTH, 5)
     torch.cuda.synchronize()
@@ -257,8 +216,8 @@ def test_any_chunking_gives_the_words_of_one_call(S, native, abi, cornell_ctx):
     # [0, a), [a, S) for an uneven a; the scratch is sized for the larger chunk
     if S > 1:
         a = {15: 4, 16: 5, 17: 16, 40: 17}[S]
-        buf = Buffers(device, len(rays), max(a, S - a))
-        buf.upload(rays)
+        buf = buffers(device, len(rays), max(a, S - a))
+        buf.rays.upload(rays)
         query(ctx, abi, buf, 0, a, DEPTH, 5)
         query(ctx, abi, buf, a, S, DEPTH, 5)
         torch.cuda.synchronize()
@@ -289,13 +248,13 @@ def test_one_ray_and_no_ray(native, abi, cornell_ctx):
     sums, means = whole(device, abi, ctx, 17)
     got_sums, got_means = one_call(device, abi, ctx, rays[5:6], 17)
     assert got_sums.tobytes() == sums[5:6].tobytes() and got_means.tobytes() == means[5:6].tobytes()
-    buf = Buffers(device, 1, 17)
-    buf.upload(rays[5:6])
+    buf = buffers(device, 1, 17)
+    buf.rays.upload(rays[5:6])
     query(ctx, abi, buf, 0, 17, DEPTH, 5, want_linear=False)                # without the optional means
     torch.cuda.synchronize()
     s1, l1 = buf.read()
     assert s1.tobytes() == sums[5:6].tobytes() and (l1.view(np.uint8) == PATTERN).all()
-    buf = Buffers(device, 0, 1)                                             # n_rays == 0: MI355RT_OK, nothing written
+    buf = buffers(device, 0, 1)                                             # n_rays == 0: MI355RT_OK, nothing written
     ctx.trace_radiance(abi.RadianceParams.make(0, 1, 4), None, 0, None, None, None, None)
     torch.cuda.synchronize()
     buf.read()
@@ -330,8 +289,8 @@ def test_beside_a_render_of_the_same_context(native, oracle_mod, abi):
         torch.cuda.synchronize()
         s_render, s_query = torch.cuda.Stream(), torch.cuda.Stream()
         packed = torch.zeros((H, W), dtype=torch.int32, device="cuda")
-        buf = Buffers(device, len(rays), 17)
-        buf.upload(rays)
+        buf = buffers(device, len(rays), 17)
+        buf.rays.upload(rays)
         torch.cuda.synchronize()
         ctx.render(packed.data_ptr(), None, None, s_render.cuda_stream)
         query(ctx, abi, buf, 0, 17, DEPTH, 5, stream=s_query.cuda_stream)

@@ -14,12 +14,12 @@ import pytest
 
 import fuzz_scenes
 import kat_f32 as K
+from device_buffers import Guarded
 from parity import assert_same_bits_nan_folded
 
 pytestmark = pytest.mark.gpu
 
 F = np.float32
-PATTERN = 0xA5
 
 
 # ---- scenes, built once -------------------------------------------------------------------------------------------------------------
@@ -123,15 +123,13 @@ def to_device_rays(abi, origins, dirs):
     return torch.from_numpy(r).cuda()
 
 
-def hit_buffer(n, extra=8):
-    import torch
-    return torch.full(((n + extra) * 48,), PATTERN, dtype=torch.uint8, device="cuda")
+def hit_buffer(n):
+    """n hit records with eight records of guard bytes behind them."""
+    return Guarded(n * 48, guard=8 * 48)
 
 
-def read_hits(abi, buf, n, extra=8):
-    raw = buf.cpu().numpy()
-    assert (raw[n * 48:] == PATTERN).all() and len(raw) == (n + extra) * 48, "the query wrote past record n - 1"
-    return raw[:n * 48].view(abi.HIT_DTYPE).copy()
+def read_hits(abi, buf):
+    return buf.read(abi.HIT_DTYPE, "the query's hit records")
 
 
 def context_for(device, abi, sc, W=64, H=48, spp=1, depth=1):
@@ -145,18 +143,18 @@ def trace(device, abi, ctx, origins, dirs, stream=None):
     n = len(origins)
     rays, hits = to_device_rays(abi, origins, dirs), hit_buffer(n)
     torch.cuda.synchronize()
-    ctx.trace_rays(rays.data_ptr(), n, hits.data_ptr(), stream)
+    ctx.trace_rays(rays.data_ptr(), n, hits.ptr, stream)
     torch.cuda.synchronize()
-    return read_hits(abi, hits, n)
+    return read_hits(abi, hits)
 
 
 def first_hits(device, abi, ctx, n, options=None):
     import torch
     hits = hit_buffer(n)
     torch.cuda.synchronize()
-    ctx.first_hits(hits.data_ptr(), options)
+    ctx.first_hits(hits.ptr, options)
     torch.cuda.synchronize()
-    return read_hits(abi, hits, n)
+    return read_hits(abi, hits)
 
 
 # ---- 1: every kind, arbitrary rays ------------------------------------------------------------------------------------------------------
@@ -314,37 +312,37 @@ def test_one_shot_repeats_and_a_query_beside_a_render(native, oracle_mod, abi):
         d_rays, d_hits, d_px = to_device_rays(abi, o, d), hit_buffer(len(o)), hit_buffer(W * H)
         torch.cuda.synchronize()
         ctx.render(packed.data_ptr(), None, None, s_render.cuda_stream)
-        ctx.trace_rays(d_rays.data_ptr(), len(o), d_hits.data_ptr(), s_query.cuda_stream)
-        ctx.first_hits(d_px.data_ptr(), None, s_query.cuda_stream)
+        ctx.trace_rays(d_rays.data_ptr(), len(o), d_hits.ptr, s_query.cuda_stream)
+        ctx.first_hits(d_px.ptr, None, s_query.cuda_stream)
         ctx.render(packed.data_ptr(), None, None, s_render.cuda_stream)
         torch.cuda.synchronize()
         ctx.check()
-        assert read_hits(abi, d_hits, len(o)).tobytes() == alone.tobytes()
-        assert read_hits(abi, d_px, W * H).tobytes() == first_hits(device, abi, ctx, W * H).tobytes()
+        assert read_hits(abi, d_hits).tobytes() == alone.tobytes()
+        assert read_hits(abi, d_px).tobytes() == first_hits(device, abi, ctx, W * H).tobytes()
         assert torch.equal(packed, want_packed)
         # refusals: nothing is launched, nothing is written
         L = device.lib()
         fresh = hit_buffer(4)
         torch.cuda.synchronize()
         with pytest.raises(device.RenderError) as e:
-            ctx.first_hits(fresh.data_ptr(), abi.Options.make(flags=abi.FLAG_FIXED_AABB))
+            ctx.first_hits(fresh.ptr, abi.Options.make(flags=abi.FLAG_FIXED_AABB))
         assert e.value.rc == abi.ERR_UNSUPPORTED
-        for call in (lambda: ctx.first_hits(fresh.data_ptr() + 4), lambda: ctx.first_hits(0), lambda: ctx.first_hits(fresh.data_ptr(), abi.Options.make(flags=2)),
-                     lambda: ctx.first_hits(fresh.data_ptr(), abi.Options.make(n_parts=2, part=2)),
-                     lambda: ctx.first_hits(fresh.data_ptr(), abi.Options(3, 0, 0, 0, 0, 1, 1, 0, 0, 0)),
-                     lambda: ctx.trace_rays(d_rays.data_ptr() + 8, 2, fresh.data_ptr()), lambda: ctx.trace_rays(d_rays.data_ptr(), 2, fresh.data_ptr() + 4),
-                     lambda: ctx.trace_rays(0, 2, fresh.data_ptr()), lambda: ctx.trace_rays(d_rays.data_ptr(), 2, 0)):
+        for call in (lambda: ctx.first_hits(fresh.ptr + 4), lambda: ctx.first_hits(0), lambda: ctx.first_hits(fresh.ptr, abi.Options.make(flags=2)),
+                     lambda: ctx.first_hits(fresh.ptr, abi.Options.make(n_parts=2, part=2)),
+                     lambda: ctx.first_hits(fresh.ptr, abi.Options(3, 0, 0, 0, 0, 1, 1, 0, 0, 0)),
+                     lambda: ctx.trace_rays(d_rays.data_ptr() + 8, 2, fresh.ptr), lambda: ctx.trace_rays(d_rays.data_ptr(), 2, fresh.ptr + 4),
+                     lambda: ctx.trace_rays(0, 2, fresh.ptr), lambda: ctx.trace_rays(d_rays.data_ptr(), 2, 0)):
             with pytest.raises(device.RenderError) as e:
                 call()
             assert e.value.rc == abi.ERR_INVALID
         ctx.trace_rays(0, 0, 0)                                                        # n_rays == 0: a no-op
         torch.cuda.synchronize()
-        assert (fresh.cpu().numpy() == PATTERN).all()
+        assert fresh.untouched()
         assert L.mi355rt_context_check(ctx._h) == 0
         empty = device.Context(0)                                                      # a context without a scene
         try:
             with pytest.raises(device.RenderError) as e:
-                empty.trace_rays(d_rays.data_ptr(), 2, fresh.data_ptr())
+                empty.trace_rays(d_rays.data_ptr(), 2, fresh.ptr)
             assert e.value.rc == abi.ERR_INVALID
         finally:
             empty.close()

@@ -10,13 +10,12 @@ import denoise_ref
 import reproject_cases as RC
 import reproject_ref as RR
 from conftest import load_for_both, pkg
+from device_buffers import Guarded
 from parity import assert_same_bits_nan_folded
 
 pytestmark = pytest.mark.gpu
 
 F = np.float32
-PATTERN = 0xA5
-GUARD = 64                                                              # bytes behind every buffer: they keep the pattern
 
 
 @pytest.fixture(scope="module")
@@ -26,31 +25,6 @@ def post():
 
 
 # ---- device plumbing ------------------------------------------------------------------------------------------------------------------
-class Guarded:
-    """A device buffer of `size` bytes with GUARD bytes of PATTERN behind it; the payload starts as PATTERN too."""
-
-    def __init__(self, size, data=None):
-        import torch
-        self.size = size
-        self.t = torch.full((size + GUARD,), PATTERN, dtype=torch.uint8, device="cuda")
-        if data is not None:
-            raw = np.ascontiguousarray(data).view(np.uint8).reshape(-1)
-            assert raw.size == size
-            self.t[:size].copy_(torch.from_numpy(raw.copy()))
-
-    @property
-    def ptr(self):
-        return self.t.data_ptr()
-
-    def read(self, dtype, what):
-        raw = self.t.cpu().numpy()
-        assert (raw[self.size:] == PATTERN).all(), f"{what}: written past its end"
-        return raw[:self.size].view(dtype).copy()
-
-    def untouched(self):
-        return bool((self.t.cpu().numpy() == PATTERN).all())
-
-
 def run(post, case, linear=True, packed=True, alias=False, prev=True, stream=None, sync=True):
     """One call on the case's records.  (hist float32 [n, 4], linear float32 [n, 3] or None, packed uint32 [n] or None), the guards checked: of the
     outputs AND of the inputs (the call writes nothing but its outputs)."""

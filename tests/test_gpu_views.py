@@ -11,81 +11,34 @@ import pytest
 import scene_shapes as SS
 import view_cases as VC
 from conftest import SCENES, load_for_both, pkg
+from device_buffers import Guarded, RadianceBuffers, packed_of, scene_contexts
 from parity import assert_same_bits_nan_folded
 
 pytestmark = pytest.mark.gpu
 
 F = np.float32
-PATTERN = 0xA5
-GUARD = 64                                                              # bytes behind every buffer a call writes: they keep the pattern
+
 
 # ---- device plumbing ------------------------------------------------------------------------------------------------------------------
-class Buffers:
-    """The device buffers of one view and up to `samples` samples per call: rays, float4 sums, means, packed words, scratch; guard bytes behind each."""
-
-    def __init__(self, device, view, samples=1, fill_nan=True):
-        import torch
-        self.view, self.n = view, view.width * view.height
-        n = self.n
-        self.scratch_bytes = device.view_scratch_bytes(view, samples)
-        mk = lambda size: torch.full((size + GUARD,), PATTERN, dtype=torch.uint8, device="cuda")
-        self.rays, self.accum, self.linear, self.packed, self.scratch = mk(n * 32), mk(n * 16), mk(n * 12), mk(n * 4), mk(self.scratch_bytes)
-        if fill_nan:
-            self.accum[:n * 16].view(torch.float32).fill_(float("nan"))   # a call with sample_begin == 0 must not read the sums
-
-    def upload_rays(self, rays):
-        import torch
-        assert rays.dtype.itemsize == 32 and len(rays) == self.n
-        self.rays[:self.n * 32].copy_(torch.from_numpy(np.ascontiguousarray(rays).view(np.uint8).reshape(-1).copy()))
-
-    def read_rays(self, abi):
-        r = self.rays.cpu().numpy()
-        assert (r[self.n * 32:] == PATTERN).all(), "view_rays wrote past ray n - 1"
-        return r[:self.n * 32].view(abi.PATH_RAY_DTYPE).copy()
-
-    def read(self):
-        """(sums float32 [n, 4], means float32 [n, 3], packed uint32 [n]) after checking the guards."""
-        n = self.n
-        a, l, p, s = (t.cpu().numpy() for t in (self.accum, self.linear, self.packed, self.scratch))
-        assert (a[n * 16:] == PATTERN).all() and (l[n * 12:] == PATTERN).all() and (p[n * 4:] == PATTERN).all(), "render_view wrote past pixel n - 1"
-        assert (s[self.scratch_bytes:] == PATTERN).all(), "render_view wrote past its scratch"
-        return a[:n * 16].view(F).reshape(-1, 4).copy(), l[:n * 12].view(F).reshape(-1, 3).copy(), p[:n * 4].view(np.uint32).copy()
+def buffers(device, view, samples=1, fill_nan=True):
+    """The buffers of one view and up to `samples` samples per call, the packed words among them."""
+    buf = RadianceBuffers("render_view", view.width * view.height, device.view_scratch_bytes(view, samples), packed=True, fill_nan=fill_nan)
+    buf.view = view
+    return buf
 
 
 def render_view(ctx, abi, buf, begin, end, depth=VC.DEPTH, seed=0, stream=None, linear=True, packed=True):
-    ctx.render_view(buf.view, abi.RadianceParams.make(begin, end, depth, seed), buf.accum.data_ptr(), buf.scratch.data_ptr(),
-                    buf.linear.data_ptr() if linear else None, buf.packed.data_ptr() if packed else None, stream)
+    ctx.render_view(buf.view, abi.RadianceParams.make(begin, end, depth, seed), buf.accum.ptr, buf.scratch.ptr,
+                    buf.linear.ptr if linear else None, buf.packed.ptr if packed else None, stream)
 
 
 def one_call(device, abi, ctx, view, S, depth=VC.DEPTH, seed=0):
     import torch
-    buf = Buffers(device, view, S)
+    buf = buffers(device, view, S)
     render_view(ctx, abi, buf, 0, S, depth, seed)
     torch.cuda.synchronize()
     ctx.check()
     return buf.read()
-
-
-def by_query(device, abi, ctx, view, S, rays_of, depth=VC.DEPTH, seed=0):
-    """The view through mi355rt_context_trace_radiance: one call per sample along rays_of(buf, s), the sums carried.  (sums, means)."""
-    import torch
-    buf = Buffers(device, view, 1)
-    for s in range(S):
-        rays_of(buf, s)
-        ctx.trace_radiance(abi.RadianceParams.make(s, s + 1, depth, seed), buf.rays.data_ptr(), buf.n, buf.accum.data_ptr(), buf.scratch.data_ptr(), buf.linear.data_ptr())
-    torch.cuda.synchronize()
-    ctx.check()
-    sums, means, _ = buf.read()
-    return sums, means
-
-
-def packed_of(linear):
-    """renderer.rs:112-120 / color.rs:87-93 in numpy float32: sqrt, clamp to [0, 1] (NaN -> 0 by the cast's rule), * 255, truncate."""
-    with np.errstate(invalid="ignore"):
-        c = np.sqrt(np.asarray(linear, F))
-        c = np.where(c < 0, F(0), np.where(c > 1, F(1), c)).astype(F) * F(255.0)
-        w = np.where(np.isnan(c), 0, c).astype(np.uint32)
-    return (w[..., 0] << 16) | (w[..., 1] << 8) | w[..., 2]
 
 
 @pytest.fixture(scope="module")
@@ -99,14 +52,7 @@ def scenes(native, oracle_mod, abi):
 @pytest.fixture(scope="module")
 def contexts(native, abi, scenes):
     """One context per scene, with a view the calls never look at: a view needs no set_scene of its own."""
-    _, device = native
-    out = {}
-    for name, sc in scenes.items():
-        out[name] = device.Context(0)
-        out[name].set_scene(sc, abi.Camera(), abi.Settings(1, 1, 1, 1))
-    yield out
-    for c in out.values():
-        c.close()
+    yield from scene_contexts(native[1], abi, scenes)
 
 
 CAM_CASES = [(n, c) for n in VC.SCENES for c in VC.CAMERAS]
@@ -115,10 +61,10 @@ ALL_SAMPLES = range(max(VC.SAMPLES))
 
 def device_rays(device, abi, ctx, view, s, seed):
     import torch
-    buf = Buffers(device, view)
-    ctx.view_rays(view, s, buf.rays.data_ptr(), seed)
+    buf = buffers(device, view)
+    ctx.view_rays(view, s, buf.rays.ptr, seed)
     torch.cuda.synchronize()
-    return buf.read_rays(abi)
+    return buf.read_rays(abi, "view_rays")
 
 
 # ---- 1: pinhole rays ------------------------------------------------------------------------------------------------------------------------
@@ -196,7 +142,7 @@ def test_a_thin_lens_view_is_the_radiance_query_along_the_numpy_rays(name, cname
     lens = VC.lens_of(cam)
     view = VC.make_view(abi, cam, W, H, abi.VIEW_THIN_LENS)
     sums, means, packed = one_call(device, abi, contexts[name], view, S, VC.DEPTH, seed)
-    want_sums, want_means = by_query(device, abi, contexts[name], view, S, lambda buf, s: buf.upload_rays(VC.thin_lens_rays(oracle_mod, abi, cam, W, H, s, *lens, seed)), VC.DEPTH, seed)
+    want_sums, want_means = buffers(device, view).by_query(contexts[name], abi, S, lambda s: VC.thin_lens_rays(oracle_mod, abi, cam, W, H, s, *lens, seed), VC.DEPTH, seed)
     assert sums.tobytes() == want_sums.tobytes() and means.tobytes() == want_means.tobytes()
     assert packed.tobytes() == packed_of(means).astype(np.uint32).tobytes()
     assert np.isfinite(means).all() and len(np.unique(means, axis=0)) > 1
@@ -228,7 +174,7 @@ def test_any_chunking_gives_the_words_of_one_call(model, native, abi, scenes, co
     _, device = native
     sums, means, packed = whole(device, abi, contexts, scenes, model)
     assert np.isfinite(sums).all() and (sums[:, :3] > 0).any()             # the NaN the sums were pre-filled with was not read
-    buf = Buffers(device, model_view(abi, scenes, model), 11)              # the scratch is sized for the largest chunk
+    buf = buffers(device, model_view(abi, scenes, model), 11)              # the scratch is sized for the largest chunk
     for a, b in ((0, 5), (5, 16), (16, 17)):
         render_view(contexts["cornell"], abi, buf, a, b, VC.DEPTH, VC.SEEDS[1])
     torch.cuda.synchronize()
@@ -263,13 +209,13 @@ def test_centre_rays_fed_to_trace_rays_are_first_hits(name, native, abi, scenes)
             want = torch.zeros(W * H * 48, dtype=torch.uint8, device="cuda")
             ctx.first_hits(want.data_ptr())
             view = VC.make_view(abi, sc.camera, W, H, abi.VIEW_PINHOLE, centre=True)
-            buf = Buffers(device, view)
-            ctx.view_rays(view, 0, buf.rays.data_ptr())
-            got = torch.full((W * H * 48,), PATTERN, dtype=torch.uint8, device="cuda")
-            ctx.trace_rays(buf.rays.data_ptr(), W * H, got.data_ptr())
+            buf = buffers(device, view)
+            ctx.view_rays(view, 0, buf.rays.ptr)
+            got = Guarded(W * H * 48)
+            ctx.trace_rays(buf.rays.ptr, W * H, got.ptr)
             torch.cuda.synchronize()
             ctx.check()
-            g, w = got.cpu().numpy().view(abi.HIT_DTYPE), want.cpu().numpy().view(abi.HIT_DTYPE)
+            g, w = got.read(abi.HIT_DTYPE, "trace_rays: hits"), want.cpu().numpy().view(abi.HIT_DTYPE)
             assert g.tobytes() == w.tobytes(), (W, H)
             assert (w["primitive"] != abi.NO_HIT).any()
     finally:
@@ -293,7 +239,7 @@ def test_beside_a_render_of_the_same_context(native, oracle_mod, abi, scenes):
         torch.cuda.synchronize()
         s_render, s_view = torch.cuda.Stream(), torch.cuda.Stream()
         packed = torch.zeros((H, W), dtype=torch.int32, device="cuda")
-        buf = Buffers(device, view, 17)
+        buf = buffers(device, view, 17)
         torch.cuda.synchronize()
         ctx.render(packed.data_ptr(), None, None, s_render.cuda_stream)
         render_view(ctx, abi, buf, 0, 17, VC.DEPTH, 5, stream=s_view.cuda_stream)
@@ -315,12 +261,12 @@ def test_refusals_leave_the_sums_untouched_and_one_pixel_works(native, oracle_mo
     ctx, sc = contexts["cornell"], scenes["cornell"]
     cam = VC.camera("inside", sc)
     ok = VC.make_view(abi, cam, 5, 3, abi.VIEW_PINHOLE)
-    buf = Buffers(device, ok, 4, fill_nan=False)
+    buf = buffers(device, ok, 4, fill_nan=False)
     prm = abi.RadianceParams.make(0, 4, VC.DEPTH)
 
     def refused(word, view=ok, params=prm, accum=None, scratch=None, linear=None, packed=None):
         with pytest.raises(device.RenderError) as e:
-            ctx.render_view(view, params, buf.accum.data_ptr() if accum is None else accum, buf.scratch.data_ptr() if scratch is None else scratch, linear, packed)
+            ctx.render_view(view, params, buf.accum.ptr if accum is None else accum, buf.scratch.ptr if scratch is None else scratch, linear, packed)
         assert e.value.rc == abi.ERR_INVALID and word in str(e.value), (word, str(e.value))
 
     bad = VC.make_view(abi, cam, 5, 3, abi.VIEW_PINHOLE); bad.model = 2
@@ -334,20 +280,19 @@ def test_refusals_leave_the_sums_untouched_and_one_pixel_works(native, oracle_mo
     refused("view.width", view=VC.make_view(abi, cam, 0, 3, abi.VIEW_PINHOLE))
     refused("split the call", view=VC.make_view(abi, cam, 65536, 65536, abi.VIEW_PINHOLE))
     refused("params.sample_begin", params=abi.RadianceParams.make(4, 4, VC.DEPTH))
-    refused("d_accum must be 16-byte aligned", accum=buf.accum.data_ptr() + 4)
-    refused("d_scratch must be 16-byte aligned", scratch=buf.scratch.data_ptr() + 8)
-    refused("d_out_linear must be 4-byte aligned", linear=buf.linear.data_ptr() + 2)
-    refused("d_out_packed must be 4-byte aligned", packed=buf.packed.data_ptr() + 1)
+    refused("d_accum must be 16-byte aligned", accum=buf.accum.ptr + 4)
+    refused("d_scratch must be 16-byte aligned", scratch=buf.scratch.ptr + 8)
+    refused("d_out_linear must be 4-byte aligned", linear=buf.linear.ptr + 2)
+    refused("d_out_packed must be 4-byte aligned", packed=buf.packed.ptr + 1)
     with pytest.raises(device.RenderError) as e:
-        ctx.view_rays(ok, 0, buf.rays.data_ptr() + 8)
+        ctx.view_rays(ok, 0, buf.rays.ptr + 8)
     assert "d_rays must be 16-byte aligned" in str(e.value)
     with pytest.raises(device.RenderError) as e:
-        ctx.render_view(None, prm, buf.accum.data_ptr(), buf.scratch.data_ptr())
+        ctx.render_view(None, prm, buf.accum.ptr, buf.scratch.ptr)
     assert "view is null" in str(e.value)
     torch.cuda.synchronize()
     ctx.check()
-    for t in (buf.accum, buf.linear, buf.packed, buf.scratch, buf.rays):
-        assert (t.cpu().numpy() == PATTERN).all()                           # nothing was enqueued
+    assert all(t.untouched() for t in (buf.accum, buf.linear, buf.packed, buf.scratch, buf.rays))      # nothing was enqueued
     # one pixel, one sample: the oracle's 1 x 1 image
     one = VC.make_view(abi, cam, 1, 1, abi.VIEW_PINHOLE)
     sums, means, packed = one_call(device, abi, ctx, one, 1, VC.DEPTH, 0)

@@ -117,6 +117,22 @@ def test_pcg4d_three_restatements_vectors_and_bijection(oracle_mod):
     assert oracle_mod.ctr_block(1, 2, 3, 4, 5, 6, gen=1).tolist() == oracle_mod.philox_rounds(1, 2, 3, 4, 5, 6, 7).tolist() != oracle_mod.philox(1, 2, 3, 4, 5, 6).tolist()
 
 
+def test_the_shared_numpy_pcg4d_is_the_oracles(oracle_mod):
+    """oracle/rng_np.py, the copy the tests' references and the stage benches import: the inputs of tests/test_occlusion_reference_cpu.py, and one
+    broadcast of scalars against a column and a row."""
+    from oracle import rng_np
+    rng = np.random.default_rng(8)
+    args = rng.integers(0, 2 ** 32, (300, 4), dtype=np.uint64).astype(np.uint32)
+    args[:8] = [[0, 0, 0, 0], [0xFFFFFFFF] * 4, [1, 0, 0, 0], [0, 1, 0, 0], [0, 0, 1, 0], [0, 0, 0, 1], [799, 599, 255 * 16 + 15, 7], [0x80000000, 1, 2, 3]]
+    got = np.stack(rng_np.pcg4d(*args.T), axis=1)
+    assert got.dtype == np.uint32
+    for a, g in zip(args, got):
+        assert g.tolist() == oracle_mod.pcg4d(*(int(v) for v in a)).tolist(), a
+    w = rng_np.pcg4d(5, np.uint32(7), np.arange(3, dtype=np.uint32)[:, None], np.array([9, 0xFFFFFFFF], np.uint32)[None, :])
+    assert all(v.shape == (3, 2) and v.dtype == np.uint32 for v in w)
+    assert [int(v[2, 1]) for v in w] == oracle_mod.pcg4d(5, 7, 2, 0xFFFFFFFF).tolist()
+
+
 def test_ctr_stream_first_sample_of_a_row_is_keyed_by_row(oracle_mod, abi):
     """Two rows never share a key and a seed offset of k equals shifting the row by k."""
     a = oracle_mod.ctr_block(5, 0, 1, 2, 0, 0).tolist()

@@ -15,7 +15,6 @@ cornell-box at 800 x 600, max depth 30, chunks of 64 samples:
 Every step is one rt_render process under its own `timeout -k 10`; the steps of a phase are chained with `&&`, so nothing is started after a
 step that failed, hung or was killed, and the tool stops there.  Without a GPU the first step fails; nothing is measured on the CPU."""
 import argparse
-import importlib
 import os
 import re
 import shlex
@@ -24,8 +23,8 @@ import subprocess
 import sys
 import tempfile
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import stage_bench
+from stage_bench import ROOT
 
 SCENE = os.path.join(ROOT, "data/scenes/tungsten/cornell-box/scene.json")
 W, H, DEPTH, ALLOW = 800, 600, 30, 0.05
@@ -70,7 +69,7 @@ def main(argv=None):
     STOP = CHUNK * KSTOP
     args.out = args.out or os.path.join(ROOT, "profiles", "converge_device.txt" if args.noise_device else "converge.txt")
     import numpy as np
-    build = importlib.import_module("raytracer-rust_amd.build")
+    build, = stage_bench.packages("build")
     exe = build.CLI
     if not os.path.exists(exe):
         sys.exit(f"converge_bench: {exe} is missing: build first")
@@ -109,7 +108,7 @@ def main(argv=None):
             rows_d.append((float(n.group(9)), float(n.group(10)), float(h.group(1)), int(n.group(4)), float(n.group(6)), float(n.group(7))))
     med = lambda rows, i: statistics.median(r[i] for r in rows)
     flags = (f" --chunk {CHUNK}" if CHUNK != 64 else "") + (f" --stop-chunks {KSTOP}" if KSTOP != 4 else "") + (" --noise-device" if args.noise_device else "")
-    lines = [f"# python tools/converge_bench.py --repeats {args.repeats}{flags}   kernel_hash {build.kernel_hash()}",
+    lines = [stage_bench.header("converge_bench", f"--repeats {args.repeats}{flags}", device_name=False),
              f"# cornell-box {W}x{H}, max depth {DEPTH}, chunks of {CHUNK} samples; target {target!r} with --noise-allow {ALLOW} ({allowed} pixels), --min-chunks {KSTOP}: stops at {STOP} samples",
              "# wall_ms: context, scene upload, buffers, every chunk, the copy back (no file written inside it); kernel_ms: path tracing + resolve kernels, device events",
              f"# converging: kernel_ms covers the samples the device traced (rendered), the speculative chunk included; fixed: rt_render --chunk {CHUNK} --spp {STOP} (mi355rt_render_progressive)",

@@ -16,16 +16,14 @@ warm-up batch; the median is reported.  Every (scene, size) step runs in a proce
 fails ends the tool.  The file records build.kernel_hash() and the registers, code bytes and LDS of the k_denoise* kernels (tools/isa_stats.py).
 Without a GPU the tool fails; it measures nothing on the CPU."""
 import argparse
-import importlib
 import json
 import os
 import statistics
 import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+import stage_bench
+from stage_bench import ROOT
 
 SCENES = {"cornell-box": ("data/scenes/tungsten/cornell-box/scene.json", False), "teapot": ("data/scenes/tungsten/teapot/scene.json", True)}
 SIZES = [(800, 600), (1920, 1080)]
@@ -36,9 +34,7 @@ BATCH = 50
 def step(name, W, H, seconds):
     """One (scene, size): runs in a child process, prints one JSON line."""
     import torch
-    abi = importlib.import_module("raytracer-rust_amd.abi")
-    host = importlib.import_module("raytracer-rust_amd.host")
-    device = importlib.import_module("raytracer-rust_amd.device")
+    abi, host, device = stage_bench.packages("abi", "host", "device")
     path, skip = SCENES[name]
     sc = host.LoadedScene(os.path.join(ROOT, path), W, H, SPP, 0, skip_unknown_primitives=skip)           # max_depth 0: the scene file's own
     ctx = device.Context(0)
@@ -57,12 +53,7 @@ def step(name, W, H, seconds):
         ctx.first_hits(hits.data_ptr(), None, s)
         torch.cuda.synchronize()
 
-        def timed(call):
-            evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(BATCH)]
-            for a, b in evs:
-                a.record(stream); call(); b.record(stream)
-            torch.cuda.synchronize()
-            return [a.elapsed_time(b) for a, b in evs]
+        timed = lambda call: stage_bench.timed_launches(stream, call, BATCH)
 
         def denoise(levels):
             p = abi.DenoiseParams.make(levels=levels)
@@ -116,19 +107,11 @@ def main(argv=None):
     args = ap.parse_args(argv)
     import torch  # noqa: F401  -- before the HIP library (tests/conftest.py: one HIP runtime in the process)
     if args.step:
-        if not torch.cuda.is_available():
-            sys.exit("denoise_bench: no GPU visible -- nothing is measured on the CPU")
+        stage_bench.require_gpu("denoise_bench")
         return step(args.step[0], int(args.step[1]), int(args.step[2]), args.seconds)
-    build = importlib.import_module("raytracer-rust_amd.build")
-    isa_stats = importlib.import_module("isa_stats")
-    lines = [f"# python tools/denoise_bench.py --seconds {args.seconds:g}   kernel_hash {build.kernel_hash()}",
-             "# k_denoise* kernels of the measured library (tools/isa_stats.py):",
-             f"# {'kernel':24s} {'code B':>7s} {'vgpr':>5s} {'sgpr':>5s} {'vspill':>6s} {'sspill':>6s} {'private B':>9s} {'LDS B':>6s} {'scratch_ insts':>14s}"]
-    for k, st in sorted(isa_stats.kernel_stats(build.DEVICE_SO).items(), key=lambda kv: isa_stats.short(kv[0])):
-        if "k_denoise" in k:
-            lines.append(f"# {isa_stats.short(k):24s} {st.get('code_bytes', 0):7d} {st.get('vgpr_count', 0):5d} {st.get('sgpr_count', 0):5d} "
-                         f"{st.get('vgpr_spill_count', 0):6d} {st.get('sgpr_spill_count', 0):6d} {st.get('private_segment_fixed_size', 0):9d} "
-                         f"{st.get('group_segment_fixed_size', 0):6d} {st.get('scratch_insts', 0):14d}")
+    build, = stage_bench.packages("build")
+    lines = [stage_bench.header("denoise_bench", f"--seconds {args.seconds:g}", device_name=False), "# k_denoise* kernels of the measured library (tools/isa_stats.py):"]
+    lines += stage_bench.kernel_table(build.DEVICE_SO, lambda k: "k_denoise" in k, 24, insts=False)[0]
     lines += ["", f"## mi355rt_context_denoise with the defaults (levels 5) on a {SPP}-spp frame, beside mi355rt_context_first_hits and a {SPP}-spp mi355rt_context_render of the same frame",
               f"##   ms = median per call, device events around each call (render: path tracing + resolve kernel by mi355rt_context_set_timing); batches of {BATCH} back to back, alternating",
               f"{'scene':12s} {'size':>10s} {'variant':>7s} {'denoise ms':>10s} {'(min)':>8s} {'calls':>6s} {'first_hits ms':>13s} {'render 4spp ms':>14s} {'launches':>8s} {'denoise / render':>16s}"]
@@ -154,10 +137,7 @@ def main(argv=None):
             print(lines[-1], flush=True)
             print(per_kernel[-1], flush=True)
             print(ab[-1], flush=True)
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        f.write("\n".join(lines + per_kernel + ab) + "\n")
-    print("wrote", args.out)
+    stage_bench.write_report(lines + per_kernel + ab, args.out, echo=False)
 
 
 if __name__ == "__main__":

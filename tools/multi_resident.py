@@ -30,8 +30,8 @@ import time
 
 import torch  # noqa: F401  -- before the HIP library (tests/conftest.py: one HIP runtime in the process)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import stage_bench
+from stage_bench import ROOT
 
 
 def main(argv=None):
@@ -44,9 +44,7 @@ def main(argv=None):
     ap.add_argument("--chunk", type=int, default=0, help="samples per progressive chunk: time the chunked frame instead (0: off)")
     args = ap.parse_args(argv)
     devices = [int(d) for d in args.devices.split(",") if d.strip()]
-    abi = importlib.import_module("raytracer-rust_amd.abi")
-    host = importlib.import_module("raytracer-rust_amd.host")
-    device = importlib.import_module("raytracer-rust_amd.device")
+    abi, host, device = stage_bench.packages("abi", "host", "device")
     path, W, H, spp, depth, skip_unknown = bench.WORKLOADS[args.workload]
     sc = host.LoadedScene(os.path.join(ROOT, path), W, H, spp, depth, skip_unknown_primitives=skip_unknown)
     opt = abi.Options.make(strip_rows=args.strip_rows)

@@ -12,43 +12,33 @@ the rays nor that reduction is charged to the baseline.
       cornell   shadow-style segments from the first-hit point of every pixel of an 800 x 600 view that hits something to a point just below the light.
 (b) mi355rt_context_ambient_occlusion at 800 x 600 x 16 samples, radius +inf, on cornell-box, teapot and semesterbild -- both forms of
     dealing (pixel, sample) pairs to lanes (diagnostic knob "ao_form": 0 = a pixel's samples across the lanes of a wave, 1 = a pixel per lane)
-    -- against trace_rays over the same sample rays (made here with the definition of mi355rt.h in torch integer arithmetic; only the rays
+    -- against trace_rays over the same sample rays (made here with the definition of mi355rt.h: the generator's words by oracle/rng_np.py, the rest in torch; only the rays
     of pixels that hit something, which are the rays the pass traces).  The pass's floats are compared with the reduction of the baseline's records.
 Every figure: ms per launch by device events around the launch, launches back to back in batches, batches alternating between the
 contenders, until each has at least --seconds of timed kernel work after a warm-up batch; medians.  The file records build.kernel_hash()
 and the registers of the kernels (tools/isa_stats.py).  Without a GPU the tool fails; it measures nothing on the CPU."""
 import argparse
 import ctypes as C
-import importlib
 import os
 import statistics
-import sys
 
 import numpy as np
 import torch  # noqa: F401  -- before the HIP library (tests/conftest.py: one HIP runtime in the process)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+import stage_bench
+from oracle.rng_np import pcg4d
+from stage_bench import ROOT
 
 SCENES = [("cornell-box", "data/scenes/tungsten/cornell-box/scene.json", False), ("teapot", "data/scenes/tungsten/teapot/scene.json", True),
           ("semesterbild", "data/scenes/semesterbild.json", False)]
 W, H, SAMPLES = 800, 600, 16
 BATCH = 10
-M32 = 0xFFFFFFFF
 
 
 def alternate(contenders, seconds):
     """contenders: {name: launch()} -> {name: [ms per launch]}; batches of BATCH launches alternate until every contender has `seconds` of timed work."""
     stream = torch.cuda.current_stream()
-
-    def batch(launch):
-        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(BATCH)]
-        for a, b in evs:
-            a.record(stream); launch(); b.record(stream)
-        torch.cuda.synchronize()
-        return [a.elapsed_time(b) for a, b in evs]
-
+    batch = lambda launch: stage_bench.timed_launches(stream, launch, BATCH)
     for launch in contenders.values():
         batch(launch)                                                    # warm-up: code objects, row tables
     ms = {k: [] for k in contenders}
@@ -58,33 +48,16 @@ def alternate(contenders, seconds):
     return ms
 
 
-def pcg4d(x, y, z, w):
-    """rt_rng.h's pcg4d on int64 tensors holding uint32 values (a 64-bit product wraps, its low 32 bits are the 32-bit product's)."""
-    lcg = lambda v: (v * 1664525 + 1013904223) & M32
-    x, y, z, w = lcg(x), lcg(y), lcg(z), lcg(w)
-
-    def mix(x, y, z, w):
-        x = (x + y * w) & M32
-        y = (y + z * x) & M32
-        z = (z + x * y) & M32
-        w = (w + y * z) & M32
-        return x, y, z, w
-
-    x, y, z, w = mix(x, y, z, w)
-    x, y, z, w = x ^ (x >> 16), y ^ (y >> 16), z ^ (z >> 16), w ^ (w >> 16)
-    return mix(x, y, z, w)
-
-
 def ao_rays(hits_f, hit_pixels, seed):
     """The sample rays of mi355rt.h's definition for the pixels `hit_pixels` (indices into the 800 x 600 image): float32 [n, SAMPLES, 8] on the device."""
-    x = (hit_pixels % W)[:, None].expand(-1, SAMPLES).contiguous()
-    y = (hit_pixels // W)[:, None].expand(-1, SAMPLES).contiguous()
-    s = torch.arange(SAMPLES, device="cuda", dtype=torch.int64)[None, :].expand(len(hit_pixels), -1)
+    px = hit_pixels.cpu().numpy()
+    x, y = (px % W).astype(np.uint32)[:, None], (px // W).astype(np.uint32)[:, None]
+    s = np.arange(SAMPLES, dtype=np.uint32)[None, :]
     v = torch.zeros((len(hit_pixels), SAMPLES, 3), dtype=torch.float32, device="cuda")
     found = torch.zeros((len(hit_pixels), SAMPLES), dtype=torch.bool, device="cuda")
     for j in range(16):
-        w0, w1, w2, _ = pcg4d(x, y, s * 16 + j, torch.full_like(x, seed))
-        c = torch.stack([(w >> 8).to(torch.float32) * (2.0 ** -24) * 2.0 - 1.0 for w in (w0, w1, w2)], dim=-1)
+        words = pcg4d(x, y, s * np.uint32(16) + np.uint32(j), np.uint32(seed))[:3]                 # on the host; the float mapping on the device
+        c = torch.stack([torch.from_numpy((w >> np.uint32(8)).astype(np.float32)).cuda() * (2.0 ** -24) * 2.0 - 1.0 for w in words], dim=-1)
         l2 = (c[..., 0] * c[..., 0] + c[..., 1] * c[..., 1]) + c[..., 2] * c[..., 2]
         take = (l2 < 1.0) & ~found
         v[take] = c[take]
@@ -188,21 +161,10 @@ def main(argv=None):
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "occlusion.txt"))
     ap.add_argument("--seconds", type=float, default=0.5, help="timed kernel work per figure, at least")
     args = ap.parse_args(argv)
-    if not torch.cuda.is_available():
-        sys.exit("occlusion_bench: no GPU visible -- nothing is measured on the CPU")
-    abi = importlib.import_module("raytracer-rust_amd.abi")
-    build = importlib.import_module("raytracer-rust_amd.build")
-    host = importlib.import_module("raytracer-rust_amd.host")
-    device = importlib.import_module("raytracer-rust_amd.device")
-    isa_stats = importlib.import_module("isa_stats")
-    lines = [f"# python tools/occlusion_bench.py --seconds {args.seconds:g}   kernel_hash {build.kernel_hash()}   {torch.cuda.get_device_name(0)}",
-             "# occlusion kernels of the measured library and the baseline's (tools/isa_stats.py):",
-             f"# {'kernel':22s} {'code B':>7s} {'insts':>6s} {'vgpr':>5s} {'sgpr':>5s} {'vspill':>6s} {'sspill':>6s} {'private B':>9s} {'LDS B':>6s} {'scratch_ insts':>14s}"]
-    for k, st in sorted(isa_stats.kernel_stats(build.DEVICE_SO).items(), key=lambda kv: isa_stats.short(kv[0])):
-        if isa_stats.short(k).startswith(("k_occluded", "k_ao_", "k_query_rays")):
-            lines.append(f"# {isa_stats.short(k):22s} {st.get('code_bytes', 0):7d} {st.get('insts', 0):6d} {st.get('vgpr_count', 0):5d} {st.get('sgpr_count', 0):5d} "
-                         f"{st.get('vgpr_spill_count', 0):6d} {st.get('sgpr_spill_count', 0):6d} {st.get('private_segment_fixed_size', 0):9d} "
-                         f"{st.get('group_segment_fixed_size', 0):6d} {st.get('scratch_insts', 0):14d}")
+    stage_bench.require_gpu("occlusion_bench")
+    abi, build, host, device = stage_bench.packages("abi", "build", "host", "device")
+    lines = [stage_bench.header("occlusion_bench", f"--seconds {args.seconds:g}"), "# occlusion kernels of the measured library and the baseline's (tools/isa_stats.py):"]
+    lines += stage_bench.kernel_table(build.DEVICE_SO, lambda k: k.startswith(("k_occluded", "k_ao_", "k_query_rays")), 22)[0]
     scenes = {name: load(host, name, path, skip) for name, path, skip in SCENES}
     lines += ["", "## (a) mi355rt_context_occluded against mi355rt_context_trace_rays on the same buffer: median ms per launch, device events, alternating batches of %d" % BATCH,
               f"{'segments':44s} {'n':>8s} {'occluded':>8s} {'occluded ms':>11s} {'launches':>8s} {'Msegments/s':>11s} {'trace_rays ms':>13s} {'launches':>8s} {'trace_rays / occluded':>21s} {'same answers':>12s}"]
@@ -226,10 +188,7 @@ def main(argv=None):
         lines.append(f"{r['scene']:14s} {r['hit_pixels']:10d} {r['rays']:9d} {r['mean']:8.4f} {r['spread_ms']:10.4f} {r['rays'] / r['spread_ms'] / 1e3:8.1f} {r['lane_ms']:17.4f} "
                      f"{r['trace_ms']:13.4f} {r['trace_ms'] / r['spread_ms']:19.2f} {r['lane_ms'] / r['spread_ms']:13.2f} {L['spread']:4d}/{L['lane']:4d}/{L['trace_rays']:4d} {str(r['same']):>11s}")
         print(lines[-1], flush=True)
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        f.write("\n".join(lines) + "\n")
-    print("wrote", args.out)
+    stage_bench.write_report(lines, args.out, echo=False)
 
 
 if __name__ == "__main__":

@@ -22,35 +22,21 @@ one probe_radiance call for the same 16.
 The file records build.kernel_hash() and the registers, spills, code size and instruction counts of the k_probe* kernels beside k_radiance*.
 Without a GPU the tool fails."""
 import argparse
-import importlib
 import os
-import statistics
-import sys
 import time
 
 import numpy as np
 import torch  # noqa: F401  -- before the HIP library (tests/conftest.py: one HIP runtime in the process)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+import stage_bench
+from oracle.rng_np import pcg4d
+from stage_bench import ROOT
 
 W, H, SAMPLES, DEPTH = 800, 600, 16, 30
 BATCH = 8
 TRIES = 64
 F = np.float32
 U = np.uint32
-LCG_A, LCG_C = U(1664525), U(1013904223)
-
-
-def pcg4d(x, y, z, w):
-    """rt_rng.h pcg4d on uint32 arrays (wrapping arithmetic)."""
-    with np.errstate(over="ignore"):
-        x, y, z, w = (a * LCG_A + LCG_C for a in (x, y, z, w))
-        x = x + y * w; y = y + z * x; z = z + x * y; w = w + y * z
-        x, y, z, w = (a ^ (a >> U(16)) for a in (x, y, z, w))
-        x = x + y * w; y = y + z * x; z = z + x * y; w = w + y * z
-    return x, y, z, w
 
 
 def normalized_rows(a):
@@ -90,13 +76,8 @@ def main(argv=None):
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "probe_bench.txt"))
     ap.add_argument("--seconds", type=float, default=1.0, help="timed kernel work per line, at least")
     args = ap.parse_args(argv)
-    if not torch.cuda.is_available():
-        sys.exit("probe_bench: no GPU visible -- nothing is measured on the CPU")
-    abi = importlib.import_module("raytracer-rust_amd.abi")
-    build = importlib.import_module("raytracer-rust_amd.build")
-    host = importlib.import_module("raytracer-rust_amd.host")
-    device = importlib.import_module("raytracer-rust_amd.device")
-    isa_stats = importlib.import_module("isa_stats")
+    stage_bench.require_gpu("probe_bench")
+    abi, build, host, device = stage_bench.packages("abi", "build", "host", "device")
 
     sc = host.LoadedScene(os.path.join(ROOT, "data/scenes/tungsten/cornell-box/scene.json"), W, H, SAMPLES, DEPTH)
     ctx = device.Context(0)
@@ -123,15 +104,6 @@ def main(argv=None):
         prm = abi.RadianceParams.make(0, SAMPLES, DEPTH, 0)
         one = [abi.RadianceParams.make(si, si + 1, DEPTH, 0) for si in range(SAMPLES)]
 
-        def timed(call):
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record(stream)
-            for _ in range(BATCH):
-                call()
-            b.record(stream)
-            torch.cuda.synchronize()
-            return a.elapsed_time(b) / BATCH
-
         def per_sample():
             for si in range(SAMPLES):
                 ctx.trace_radiance(one[si], d_rays.data_ptr() + si * n * 32, n, d_accum.data_ptr(), d_scratch.data_ptr(), d_linear.data_ptr(), s)
@@ -143,15 +115,14 @@ def main(argv=None):
                  Q16: per_sample}
         order = [P, Q0, Q1, Q16]
         means, sums = {}, {}
-        for name in order:                                                  # warm-up, and what each line computes
-            timed(calls[name])
+
+        def warmed(name):                                                   # what each line computes
             means[name] = float((d_linear_pm if name == Q1 else d_linear).cpu().numpy().mean())
             sums[name] = d_accum.cpu().numpy().tobytes()
-        assert sums[P] == sums[Q16], "probe_radiance and the query along probe_rays' rays, sample by sample, differ"
-        ms = {name: [] for name in order}
-        while min(sum(v) * BATCH for v in ms.values()) < args.seconds * 1e3:
-            for name in order:
-                ms[name].append(timed(calls[name]))
+            if name == Q16:
+                assert sums[P] == sums[Q16], "probe_radiance and the query along probe_rays' rays, sample by sample, differ"
+
+        ms = stage_bench.interleaved_rounds(calls, args.seconds, BATCH, warmed=warmed)
         ctx.check()
 
         # the host-made route, wall time: rays in numpy, upload, one call per sample index
@@ -179,18 +150,10 @@ def main(argv=None):
     finally:
         ctx.close()
 
-    med = {k: statistics.median(v) for k, v in ms.items()}
-    spread = {k: (max(v) - min(v)) / med[k] for k, v in ms.items()}
-    lines = [f"# python tools/probe_bench.py --seconds {args.seconds:g}   kernel_hash {build.kernel_hash()}   {torch.cuda.get_device_name(0)}",
-             "# k_probe* and k_radiance* kernels of the measured library (tools/isa_stats.py):",
-             f"# {'kernel':28s} {'code B':>7s} {'insts':>6s} {'vgpr':>5s} {'sgpr':>5s} {'vspill':>6s} {'sspill':>6s} {'private B':>9s} {'LDS B':>6s} {'scratch_ insts':>14s}"]
-    insts = {}
-    for k, st in sorted(isa_stats.kernel_stats(build.DEVICE_SO).items(), key=lambda kv: isa_stats.short(kv[0])):
-        if "k_probe" in k or "k_radiance" in k:
-            insts[isa_stats.short(k)] = st.get("insts", 0)
-            lines.append(f"# {isa_stats.short(k):28s} {st.get('code_bytes', 0):7d} {st.get('insts', 0):6d} {st.get('vgpr_count', 0):5d} {st.get('sgpr_count', 0):5d} "
-                         f"{st.get('vgpr_spill_count', 0):6d} {st.get('sgpr_spill_count', 0):6d} {st.get('private_segment_fixed_size', 0):9d} "
-                         f"{st.get('group_segment_fixed_size', 0):6d} {st.get('scratch_insts', 0):14d}")
+    med, spread = stage_bench.summary(ms)
+    table, stats = stage_bench.kernel_table(build.DEVICE_SO, lambda k: "k_probe" in k or "k_radiance" in k, 28)
+    insts = {k: st.get("insts", 0) for k, st in stats.items()}
+    lines = [stage_bench.header("probe_bench", f"--seconds {args.seconds:g}"), "# k_probe* and k_radiance* kernels of the measured library (tools/isa_stats.py):"] + table
     lines += [f"# static instructions: k_probe_paths {insts['k_probe_paths']} against k_radiance_paths {insts['k_radiance_paths']} (+{insts['k_probe_paths'] - insts['k_radiance_paths']}), "
               f"k_probe_paths_mesh {insts['k_probe_paths_mesh']} against k_radiance_paths_mesh {insts['k_radiance_paths_mesh']} (+{insts['k_probe_paths_mesh'] - insts['k_radiance_paths_mesh']})",
               "", f"## cornell-box, {n} probes at the first hits of the {W} x {H} centre rays ({W * H - n} misses dropped), samples [0, {SAMPLES}) per call, max_depth {DEPTH}: "
@@ -208,11 +171,7 @@ def main(argv=None):
               "", f"## the host-made route to the same sums, wall time on the host for {SAMPLES} sample indices (one run; the same sums, word for word):",
               f"##     rays in numpy {make_s * 1e3:.1f} ms + upload of {SAMPLES} x {n * 32 / 1e6:.2f} MB {upload_s * 1e3:.1f} ms + {SAMPLES} calls = {host_route_s * 1e3:.1f} ms in all;",
               f"##     one probe_radiance call for the same {SAMPLES} samples, enqueue to synchronize: {probe_wall_s * 1e3:.3f} ms: {host_route_s / probe_wall_s:.0f} x"]
-    print("\n".join(lines), flush=True)
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        f.write("\n".join(lines) + "\n")
-    print("wrote", args.out)
+    stage_bench.write_report(lines, args.out)
 
 
 if __name__ == "__main__":

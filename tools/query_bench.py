@@ -18,18 +18,15 @@ The file records build.kernel_hash() and the registers, spills and scratch of th
 tool fails; it measures nothing on the CPU."""
 import argparse
 import ctypes as C
-import importlib
 import os
 import statistics
-import sys
 import time
 
 import numpy as np
 import torch  # noqa: F401  -- before the HIP library (tests/conftest.py: one HIP runtime in the process)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+import stage_bench
+from stage_bench import ROOT
 
 SCENES = [("cornell-box", "data/scenes/tungsten/cornell-box/scene.json", False), ("teapot", "data/scenes/tungsten/teapot/scene.json", True),
           ("semesterbild", "data/scenes/semesterbild.json", False)]
@@ -48,12 +45,7 @@ def first_hit_pass(abi, host, device, name, path, skip_unknown, seconds):
         stream = torch.cuda.current_stream()
         s = stream.cuda_stream
 
-        def query_batch():
-            evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(BATCH)]
-            for a, b in evs:
-                a.record(stream); ctx.first_hits(hits.data_ptr(), None, s); b.record(stream)
-            torch.cuda.synchronize()
-            return [a.elapsed_time(b) for a, b in evs]
+        query_batch = lambda: stage_bench.timed_launches(stream, lambda: ctx.first_hits(hits.data_ptr(), None, s), BATCH)
 
         def render_batch():
             for _ in range(BATCH):
@@ -106,12 +98,7 @@ def incoherent(abi, host, device, seconds):
         stream = torch.cuda.current_stream()
         torch.cuda.synchronize()
 
-        def batch(k):
-            evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(k)]
-            for a, b in evs:
-                a.record(stream); ctx.trace_rays(d_rays.data_ptr(), n, d_hits.data_ptr(), stream.cuda_stream); b.record(stream)
-            torch.cuda.synchronize()
-            return [a.elapsed_time(b) for a, b in evs]
+        batch = lambda k: stage_bench.timed_launches(stream, lambda: ctx.trace_rays(d_rays.data_ptr(), n, d_hits.data_ptr(), stream.cuda_stream), k)
 
         batch(3)
         q_ms = []
@@ -141,21 +128,10 @@ def main(argv=None):
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "ray_queries.txt"))
     ap.add_argument("--seconds", type=float, default=0.5, help="timed kernel work per figure, at least")
     args = ap.parse_args(argv)
-    if not torch.cuda.is_available():
-        sys.exit("query_bench: no GPU visible -- nothing is measured on the CPU")
-    abi = importlib.import_module("raytracer-rust_amd.abi")
-    build = importlib.import_module("raytracer-rust_amd.build")
-    host = importlib.import_module("raytracer-rust_amd.host")
-    device = importlib.import_module("raytracer-rust_amd.device")
-    isa_stats = importlib.import_module("isa_stats")
-    lines = [f"# python tools/query_bench.py --seconds {args.seconds:g}   kernel_hash {build.kernel_hash()}   {torch.cuda.get_device_name(0)}",
-             "# k_query_* kernels of the measured library (tools/isa_stats.py):",
-             f"# {'kernel':22s} {'code B':>7s} {'insts':>6s} {'vgpr':>5s} {'sgpr':>5s} {'vspill':>6s} {'sspill':>6s} {'private B':>9s} {'LDS B':>6s} {'scratch_ insts':>14s}"]
-    for k, st in sorted(isa_stats.kernel_stats(build.DEVICE_SO).items(), key=lambda kv: isa_stats.short(kv[0])):
-        if "k_query" in k:
-            lines.append(f"# {isa_stats.short(k):22s} {st.get('code_bytes', 0):7d} {st.get('insts', 0):6d} {st.get('vgpr_count', 0):5d} {st.get('sgpr_count', 0):5d} "
-                         f"{st.get('vgpr_spill_count', 0):6d} {st.get('sgpr_spill_count', 0):6d} {st.get('private_segment_fixed_size', 0):9d} "
-                         f"{st.get('group_segment_fixed_size', 0):6d} {st.get('scratch_insts', 0):14d}")
+    stage_bench.require_gpu("query_bench")
+    abi, build, host, device = stage_bench.packages("abi", "build", "host", "device")
+    lines = [stage_bench.header("query_bench", f"--seconds {args.seconds:g}"), "# k_query_* kernels of the measured library (tools/isa_stats.py):"]
+    lines += stage_bench.kernel_table(build.DEVICE_SO, lambda k: "k_query" in k, 22)[0]
     lines += ["", f"## (a) first-hit pass, {W} x {H} = {W * H} camera rays: mi355rt_context_first_hits against mi355rt_context_render at 1 spp, max_depth 1 (render + resolve kernel)",
               "##     ms = median per launch, device events around the kernels; launches back to back in alternating batches of %d" % BATCH,
               f"{'scene':14s} {'render variant':>14s} {'misses':>7s} {'first_hits ms':>13s} {'(min)':>8s} {'launches':>8s} {'Mrays/s':>9s} {'back-to-back ms':>15s} "
@@ -173,10 +149,7 @@ def main(argv=None):
               f"{b['scene']:14s} {b['rays']:8d} {b['misses']:7d} {b['query_ms']:13.4f} {b['query_launches']:8d} {b['rays_per_s'] / 1e6:9.1f} {b['hook_ms']:12.3f} {b['hook_calls']:6d} "
               f"{b['hook_rays_per_s'] / 1e6:9.1f} {b['ratio']:22.1f} {str(b['same_as_hook']):>12s}"]
     print(lines[-1], flush=True)
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        f.write("\n".join(lines) + "\n")
-    print("wrote", args.out)
+    stage_bench.write_report(lines, args.out, echo=False)
 
 
 if __name__ == "__main__":

@@ -15,17 +15,14 @@ same number of paths through the same scene from the same camera.
 The file records build.kernel_hash() and the registers, spills and code size of the k_radiance* kernels (tools/isa_stats.py).  Without a GPU the
 tool fails; it measures nothing on the CPU."""
 import argparse
-import importlib
 import os
 import statistics
-import sys
 
 import numpy as np
 import torch  # noqa: F401  -- before the HIP library (tests/conftest.py: one HIP runtime in the process)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+import stage_bench
+from stage_bench import ROOT
 
 W, H, SAMPLES, DEPTH = 800, 600, 16, 30
 KS = (1, 2, 4, 8, 16)
@@ -55,13 +52,8 @@ def main(argv=None):
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "radiance_bench.txt"))
     ap.add_argument("--seconds", type=float, default=1.0, help="timed kernel work per K, at least")
     args = ap.parse_args(argv)
-    if not torch.cuda.is_available():
-        sys.exit("radiance_bench: no GPU visible -- nothing is measured on the CPU")
-    abi = importlib.import_module("raytracer-rust_amd.abi")
-    build = importlib.import_module("raytracer-rust_amd.build")
-    host = importlib.import_module("raytracer-rust_amd.host")
-    device = importlib.import_module("raytracer-rust_amd.device")
-    isa_stats = importlib.import_module("isa_stats")
+    stage_bench.require_gpu("radiance_bench")
+    abi, build, host, device = stage_bench.packages("abi", "build", "host", "device")
 
     sc = host.LoadedScene(os.path.join(ROOT, "data/scenes/tungsten/cornell-box/scene.json"), W, H, SAMPLES, DEPTH)
     n = W * H
@@ -79,35 +71,21 @@ def main(argv=None):
 
         def query_batch(k):
             ctx.set_knob("radiance_items", k)
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record(stream)
-            for _ in range(BATCH):
-                ctx.trace_radiance(prm, d_rays.data_ptr(), n, d_accum.data_ptr(), d_scratch.data_ptr(), d_linear.data_ptr(), s)
-            b.record(stream)
-            torch.cuda.synchronize()
-            return a.elapsed_time(b) / BATCH
+            return stage_bench.timed_batch(stream, lambda: ctx.trace_radiance(prm, d_rays.data_ptr(), n, d_accum.data_ptr(), d_scratch.data_ptr(), d_linear.data_ptr(), s), BATCH)
 
         def render_batch():
-            for _ in range(BATCH):
-                ctx.render(d_packed.data_ptr(), None, None, s)
-            torch.cuda.synchronize()
-            r, v, _ = ctx.read_timing()                                    # (summed over the bands of every render)
-            return r / BATCH, v / BATCH
+            r, v = stage_bench.render_kernel_batch(ctx, d_packed, s, BATCH)
+            r_ms.append(r); v_ms.append(v)
 
         ctx.set_timing(True)
-        words = {}
-        for k in KS:                                                       # warm-up, and: K does not change a word
-            query_batch(k)
+        words, r_ms, v_ms = {}, [], []
+        stage_bench.render_kernel_batch(ctx, d_packed, s, BATCH)           # the yardstick's warm-up
+
+        def warmed(k):                                                     # K does not change a word
             words[k] = d_accum.cpu().numpy().tobytes()
-        assert all(words[k] == words[KS[0]] for k in KS), "the sums depend on K"
-        render_batch()
-        ms = {k: [] for k in KS}
-        r_ms, v_ms = [], []
-        while min(sum(v) * BATCH for v in ms.values()) < args.seconds * 1e3:
-            for k in KS:
-                ms[k].append(query_batch(k))
-            r, v = render_batch()
-            r_ms.append(r); v_ms.append(v)
+            assert words[k] == words[KS[0]], "the sums depend on K"
+
+        ms = stage_bench.interleaved_rounds({k: k for k in KS}, args.seconds, BATCH, query_batch, render_batch, warmed)
         ctx.set_knob("radiance_items", 0)
         ctx.check()
         mean = float(d_linear.cpu().numpy().mean())
@@ -116,17 +94,10 @@ def main(argv=None):
         ctx.close()
 
     rk, vk = statistics.median(r_ms), statistics.median(v_ms)
-    med = {k: statistics.median(v) for k, v in ms.items()}
-    spread = {k: (max(v) - min(v)) / med[k] for k, v in ms.items()}
+    med, spread = stage_bench.summary(ms)
     best = min(KS, key=lambda k: med[k])
-    lines = [f"# python tools/radiance_bench.py --seconds {args.seconds:g}   kernel_hash {build.kernel_hash()}   {torch.cuda.get_device_name(0)}",
-             "# k_radiance* kernels of the measured library (tools/isa_stats.py):",
-             f"# {'kernel':22s} {'code B':>7s} {'insts':>6s} {'vgpr':>5s} {'sgpr':>5s} {'vspill':>6s} {'sspill':>6s} {'private B':>9s} {'LDS B':>6s} {'scratch_ insts':>14s}"]
-    for k, st in sorted(isa_stats.kernel_stats(build.DEVICE_SO).items(), key=lambda kv: isa_stats.short(kv[0])):
-        if "k_radiance" in k:
-            lines.append(f"# {isa_stats.short(k):22s} {st.get('code_bytes', 0):7d} {st.get('insts', 0):6d} {st.get('vgpr_count', 0):5d} {st.get('sgpr_count', 0):5d} "
-                         f"{st.get('vgpr_spill_count', 0):6d} {st.get('sgpr_spill_count', 0):6d} {st.get('private_segment_fixed_size', 0):9d} "
-                         f"{st.get('group_segment_fixed_size', 0):6d} {st.get('scratch_insts', 0):14d}")
+    lines = [stage_bench.header("radiance_bench", f"--seconds {args.seconds:g}"), "# k_radiance* kernels of the measured library (tools/isa_stats.py):"]
+    lines += stage_bench.kernel_table(build.DEVICE_SO, lambda k: "k_radiance" in k, 22)[0]
     lines += ["", f"## cornell-box, {W} x {H} = {n} camera rays (pixel centres), samples [0, {SAMPLES}) per call, max_depth {DEPTH}: {n * SAMPLES} paths per call "
                   f"(k_radiance_paths + k_radiance_sum); image mean {mean:.6f}",
               f"##     ms = median over the rounds of (device events around {BATCH} calls back to back) / {BATCH}; spread = (max - min) / median of the rounds; rounds interleave every K and the yardstick",
@@ -139,11 +110,7 @@ def main(argv=None):
               f"{rk:18.4f} {vk:17.4f} {rk + vk:8.4f} {len(r_ms):6d} {n * SAMPLES / ((rk + vk) * 1e-3) / 1e6:10.1f}",
               "", f"## fastest K: {best} ({med[best]:.4f} ms; K = 1: {med[1]:.4f} ms, {100 * (med[1] - med[best]) / med[1]:+.2f} % against a spread of "
                   f"{100 * max(spread[1], spread[best]):.2f} %); the query takes {med[best] / (rk + vk):.2f} x the render's kernels for the same number of paths"]
-    print("\n".join(lines), flush=True)
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        f.write("\n".join(lines) + "\n")
-    print("wrote", args.out)
+    stage_bench.write_report(lines, args.out)
 
 
 if __name__ == "__main__":

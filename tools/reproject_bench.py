@@ -17,17 +17,13 @@ Cornell-box at 800 x 600 along a small orbit: the scene's camera swung about the
     reprojected one, the denoised raw one and the denoised reprojected one.
 The file records the registers, spills and code size of k_post_reproject.  Without a GPU the tool fails."""
 import argparse
-import importlib
 import os
-import statistics
-import sys
 
 import numpy as np
 import torch  # noqa: F401  -- before the HIP libraries (tests/conftest.py: one HIP runtime in the process)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+import stage_bench
+from stage_bench import ROOT
 
 W, H, SPP, DEPTH = 800, 600, 2, 30
 REF_SPP, REF_CHUNK, REF_SEED = 1024, 64, 1 << 20
@@ -64,14 +60,8 @@ def main(argv=None):
     ap.add_argument("--frames", type=int, default=8)
     ap.add_argument("--step-deg", type=float, default=0.5)
     args = ap.parse_args(argv)
-    if not torch.cuda.is_available():
-        sys.exit("reproject_bench: no GPU visible -- nothing is measured on the CPU")
-    abi = importlib.import_module("raytracer-rust_amd.abi")
-    build = importlib.import_module("raytracer-rust_amd.build")
-    host = importlib.import_module("raytracer-rust_amd.host")
-    device = importlib.import_module("raytracer-rust_amd.device")
-    post = importlib.import_module("raytracer-rust_amd.post")
-    isa_stats = importlib.import_module("isa_stats")
+    stage_bench.require_gpu("reproject_bench")
+    abi, build, host, device, post = stage_bench.packages("abi", "build", "host", "device", "post")
 
     sc = host.LoadedScene(os.path.join(ROOT, "data/scenes/tungsten/cornell-box/scene.json"), W, H, SPP, DEPTH)
     n = W * H
@@ -127,36 +117,16 @@ def main(argv=None):
                  "reproject": lambda: reproject(k, me), "denoise, defaults (5 levels)": lambda: denoise(d_rep, d_dn_rep, me),
                  "denoise, levels = 1 (yardstick)": lambda: denoise(d_rep, d_dn_rep, me, one_level)}
 
-        def timed(call):
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record(stream)
-            for _ in range(BATCH):
-                call()
-            b.record(stream)
-            torch.cuda.synchronize()
-            return a.elapsed_time(b) / BATCH
-
         hist_before = d_hist[me].clone()
-        for call in calls.values():
-            timed(call)
-        ms = {name: [] for name in calls}
-        while min(sum(v) * BATCH for v in ms.values()) < args.seconds * 1e3:
-            for name, call in calls.items():
-                ms[name].append(timed(call))
+        ms = stage_bench.interleaved_rounds(calls, args.seconds, BATCH)
         ctx.check()
         assert torch.equal(hist_before.view(torch.int32), d_hist[me].view(torch.int32)), "the timed calls did not reproduce the chain's history"
     finally:
         ctx.close()
 
-    med = {name: statistics.median(v) for name, v in ms.items()}
-    spread = {name: (max(v) - min(v)) / med[name] for name, v in ms.items()}
-    lines = [f"# python tools/reproject_bench.py --seconds {args.seconds:g} --frames {args.frames} --step-deg {args.step_deg:g}   kernel_hash {build.kernel_hash()}   {torch.cuda.get_device_name(0)}",
-             "# k_post_reproject of the measured library (tools/isa_stats.py):",
-             f"# {'kernel':28s} {'code B':>7s} {'insts':>6s} {'vgpr':>5s} {'sgpr':>5s} {'vspill':>6s} {'sspill':>6s} {'private B':>9s} {'LDS B':>6s} {'scratch_ insts':>14s}"]
-    for name, st in sorted(isa_stats.kernel_stats(build.POST_SO).items(), key=lambda kv: isa_stats.short(kv[0])):
-        lines.append(f"# {isa_stats.short(name):28s} {st.get('code_bytes', 0):7d} {st.get('insts', 0):6d} {st.get('vgpr_count', 0):5d} {st.get('sgpr_count', 0):5d} "
-                     f"{st.get('vgpr_spill_count', 0):6d} {st.get('sgpr_spill_count', 0):6d} {st.get('private_segment_fixed_size', 0):9d} "
-                     f"{st.get('group_segment_fixed_size', 0):6d} {st.get('scratch_insts', 0):14d}")
+    med, spread = stage_bench.summary(ms)
+    lines = [stage_bench.header("reproject_bench", f"--seconds {args.seconds:g} --frames {args.frames} --step-deg {args.step_deg:g}"),
+             "# k_post_reproject of the measured library (tools/isa_stats.py):"] + stage_bench.kernel_table(build.POST_SO, None, 28)[0]
     y = "denoise, levels = 1 (yardstick)"
     lines += ["", f"## (a) cornell-box, {W} x {H}, frame {k} of the orbit ({args.step_deg:g} degrees a frame): ms per call",
               f"##     ms = median over the rounds of (device events around {BATCH} calls back to back) / {BATCH}; spread = (max - min) / median of the rounds; rounds interleave every line",
@@ -170,11 +140,7 @@ def main(argv=None):
               f"{'frame':>5s} {'raw':>9s} {'reprojected':>11s} {'denoised raw':>12s} {'denoised reprojected':>20s} {'mean length':>11s} {'restarted':>9s}"]
     for i, q in enumerate(quality):
         lines.append(f"{i:5d} {q[0]:9.5f} {q[1]:11.5f} {q[2]:12.5f} {q[3]:20.5f} {q[4]:11.2f} {q[5] * 100:8.2f}%")
-    print("\n".join(lines), flush=True)
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        f.write("\n".join(lines) + "\n")
-    print("wrote", args.out)
+    stage_bench.write_report(lines, args.out)
 
 
 if __name__ == "__main__":

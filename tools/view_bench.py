@@ -16,34 +16,21 @@ checked word for word against mi355rt_context_view_rays), their upload, and one 
 the wall time of one render_view call for the same 16.
 The file records build.kernel_hash() and the registers, spills and code size of the k_view* kernels.  Without a GPU the tool fails."""
 import argparse
-import importlib
 import os
 import statistics
-import sys
 import time
 
 import numpy as np
 import torch  # noqa: F401  -- before the HIP library (tests/conftest.py: one HIP runtime in the process)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+import stage_bench
+from oracle.rng_np import pcg4d
+from stage_bench import ROOT
 
 W, H, SAMPLES, DEPTH = 800, 600, 16, 30
 BATCH = 8
 F = np.float32
 U = np.uint32
-LCG_A, LCG_C = U(1664525), U(1013904223)
-
-
-def pcg4d(x, y, z, w):
-    """rt_rng.h pcg4d on uint32 arrays (wrapping arithmetic)."""
-    with np.errstate(over="ignore"):
-        x, y, z, w = (a * LCG_A + LCG_C for a in (x, y, z, w))
-        x = x + y * w; y = y + z * x; z = z + x * y; w = w + y * z
-        x, y, z, w = (a ^ (a >> U(16)) for a in (x, y, z, w))
-        x = x + y * w; y = y + z * x; z = z + x * y; w = w + y * z
-    return x, y, z, w
 
 
 def host_rays(abi, cam, s, seed=0):
@@ -72,13 +59,8 @@ def main(argv=None):
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "view_bench.txt"))
     ap.add_argument("--seconds", type=float, default=1.0, help="timed kernel work per line, at least")
     args = ap.parse_args(argv)
-    if not torch.cuda.is_available():
-        sys.exit("view_bench: no GPU visible -- nothing is measured on the CPU")
-    abi = importlib.import_module("raytracer-rust_amd.abi")
-    build = importlib.import_module("raytracer-rust_amd.build")
-    host = importlib.import_module("raytracer-rust_amd.host")
-    device = importlib.import_module("raytracer-rust_amd.device")
-    isa_stats = importlib.import_module("isa_stats")
+    stage_bench.require_gpu("view_bench")
+    abi, build, host, device = stage_bench.packages("abi", "build", "host", "device")
 
     sc = host.LoadedScene(os.path.join(ROOT, "data/scenes/tungsten/cornell-box/scene.json"), W, H, SAMPLES, DEPTH)
     cam = sc.camera
@@ -100,46 +82,28 @@ def main(argv=None):
         s = stream.cuda_stream
         prm = abi.RadianceParams.make(0, SAMPLES, DEPTH, 0)
 
-        def timed(call):
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record(stream)
-            for _ in range(BATCH):
-                call()
-            b.record(stream)
-            torch.cuda.synchronize()
-            return a.elapsed_time(b) / BATCH
-
         calls = {name: (lambda v=v: ctx.render_view(v, prm, d_accum.data_ptr(), d_scratch.data_ptr(), d_linear.data_ptr(), d_packed.data_ptr(), s)) for name, v in views.items()}
         calls["query, resident rays"] = lambda: ctx.trace_radiance(prm, d_rays.data_ptr(), n, d_accum.data_ptr(), d_scratch.data_ptr(), d_linear.data_ptr(), s)
         order = ["view pinhole", "view pinhole centre", "query, resident rays", "view thin lens"]
-
-        def render_batch():
-            for _ in range(BATCH):
-                ctx.render(d_render.data_ptr(), None, None, s)
-            torch.cuda.synchronize()
-            r, v, _ = ctx.read_timing()
-            return r / BATCH, v / BATCH
-
+        calls = {name: calls[name] for name in order}
         ctx.set_timing(True)
-        means = {}
-        for name in order:                                                  # warm-up, and what each line computes
-            timed(calls[name])
+        means, kept, r_ms, v_ms = {}, {}, [], []
+        stage_bench.render_kernel_batch(ctx, d_render, s, BATCH)             # the render's warm-up, and its image
+
+        def warmed(name):                                                   # what each line computes
             means[name] = float(d_linear.cpu().numpy().mean())
             if name == "view pinhole":
-                view_packed = d_packed.cpu().numpy().copy()
+                assert d_render.cpu().numpy().tobytes() == d_packed.cpu().numpy().tobytes(), "the pinhole view is not the render's image"
             if name == "view pinhole centre":
-                centre_sums = d_accum.cpu().numpy().tobytes()
+                kept["centre_sums"] = d_accum.cpu().numpy().tobytes()
             if name == "query, resident rays":
-                assert d_accum.cpu().numpy().tobytes() == centre_sums, "the centre view and the query along centre rays differ"
-        render_batch()
-        assert d_render.cpu().numpy().tobytes() == view_packed.tobytes(), "the pinhole view is not the render's image"
-        ms = {name: [] for name in order}
-        r_ms, v_ms = [], []
-        while min(sum(v) * BATCH for v in ms.values()) < args.seconds * 1e3:
-            for name in order:
-                ms[name].append(timed(calls[name]))
-            r, v = render_batch()
+                assert d_accum.cpu().numpy().tobytes() == kept["centre_sums"], "the centre view and the query along centre rays differ"
+
+        def render_batch():
+            r, v = stage_bench.render_kernel_batch(ctx, d_render, s, BATCH)
             r_ms.append(r); v_ms.append(v)
+
+        ms = stage_bench.interleaved_rounds(calls, args.seconds, BATCH, after_round=render_batch, warmed=warmed)
         ctx.check()
 
         # the host-made route to the jittered image, wall time: rays in numpy, upload, one call per sample index
@@ -172,17 +136,10 @@ def main(argv=None):
         ctx.close()
 
     rk, vk = statistics.median(r_ms), statistics.median(v_ms)
-    med = {k: statistics.median(v) for k, v in ms.items()}
-    spread = {k: (max(v) - min(v)) / med[k] for k, v in ms.items()}
+    med, spread = stage_bench.summary(ms)
     q = "query, resident rays"
-    lines = [f"# python tools/view_bench.py --seconds {args.seconds:g}   kernel_hash {build.kernel_hash()}   {torch.cuda.get_device_name(0)}",
-             "# k_view* kernels of the measured library (tools/isa_stats.py):",
-             f"# {'kernel':28s} {'code B':>7s} {'insts':>6s} {'vgpr':>5s} {'sgpr':>5s} {'vspill':>6s} {'sspill':>6s} {'private B':>9s} {'LDS B':>6s} {'scratch_ insts':>14s}"]
-    for k, st in sorted(isa_stats.kernel_stats(build.DEVICE_SO).items(), key=lambda kv: isa_stats.short(kv[0])):
-        if "k_view" in k or "k_radiance" in k:
-            lines.append(f"# {isa_stats.short(k):28s} {st.get('code_bytes', 0):7d} {st.get('insts', 0):6d} {st.get('vgpr_count', 0):5d} {st.get('sgpr_count', 0):5d} "
-                         f"{st.get('vgpr_spill_count', 0):6d} {st.get('sgpr_spill_count', 0):6d} {st.get('private_segment_fixed_size', 0):9d} "
-                         f"{st.get('group_segment_fixed_size', 0):6d} {st.get('scratch_insts', 0):14d}")
+    lines = [stage_bench.header("view_bench", f"--seconds {args.seconds:g}"), "# k_view* kernels of the measured library (tools/isa_stats.py):"]
+    lines += stage_bench.kernel_table(build.DEVICE_SO, lambda k: "k_view" in k or "k_radiance" in k, 28)[0]
     lines += ["", f"## cornell-box, {W} x {H}, samples [0, {SAMPLES}) per call, max_depth {DEPTH}: {n * SAMPLES} paths per call (paths kernel + sum kernel), K = 8 (the default)",
               f"##     ms = median over the rounds of (device events around {BATCH} calls back to back) / {BATCH}; spread = (max - min) / median of the rounds; rounds interleave every line and the render",
               f"{'':>22s} {'ms per call':>11s} {'(min)':>8s} {'(max)':>8s} {'spread':>7s} {'rounds':>6s} {'Msamples/s':>10s} {'/ query':>8s} {'/ render kernels':>16s} {'image mean':>10s}"]
@@ -199,11 +156,7 @@ def main(argv=None):
               "", f"## the host-made route to the jittered image, wall time on the host for {SAMPLES} sample indices (one run; the same linear image, word for word):",
               f"##     rays in numpy {make_s * 1e3:.1f} ms + upload of {SAMPLES} x {n * 32 / 1e6:.2f} MB {upload_s * 1e3:.1f} ms + {SAMPLES} calls = {host_route_s * 1e3:.1f} ms in all;",
               f"##     one render_view call for the same {SAMPLES} samples, enqueue to synchronize: {view_wall_s * 1e3:.3f} ms: {host_route_s / view_wall_s:.0f} x"]
-    print("\n".join(lines), flush=True)
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        f.write("\n".join(lines) + "\n")
-    print("wrote", args.out)
+    stage_bench.write_report(lines, args.out)
 
 
 if __name__ == "__main__":
