@@ -65,7 +65,8 @@
  *   given without prev; d_hist_out == d_hist_prev; a negative hip_device.  After the argument checks: MI355RT_ERR_NO_DEVICE when no HIP
  *   device is visible or hip_device is out of range (there is no CPU path).
  *
- * NOT BUILT: reprojecting misses by direction (a sky), moment buffers and variance-guided filtering, motion of objects, a multi-GPU form.
+ * NOT BUILT: reprojecting misses by direction (a sky), motion of objects, a multi-GPU form.  (Moment buffers and variance-guided filtering are
+ * built beside this library, on the same steps 1 to 3: mi355rt_svgf.h.)
  */
 #ifndef MI355RT_POST_H
 #define MI355RT_POST_H

@@ -196,6 +196,31 @@ REPROJECT_DEFAULTS = (32, 0, 0.9, 0.05)
 POST_ABI_VERSION = 1
 
 
+class SvgfAccumulateParams(C.Structure):                  # mi355rt_svgf_accumulate_params (include/mi355rt_svgf.h), 32 bytes
+    _fields_ = [("max_history", u32), ("flags", u32), ("normal_min", f32), ("plane_tolerance", f32),
+                ("min_temporal", u32), ("normal_squarings", u32), ("sigma_plane", f32), ("reserved", u32)]
+
+    @classmethod
+    def make(cls, max_history=32, normal_min=0.9, plane_tolerance=0.05, min_temporal=4, normal_squarings=5, sigma_plane=0.05, flags=0, reserved=0):
+        """The defaults are what mi355rt_svgf_accumulate uses for a null pointer."""
+        return cls(max_history, flags, normal_min, plane_tolerance, min_temporal, normal_squarings, sigma_plane, reserved)
+
+
+class SvgfFilterParams(C.Structure):                      # mi355rt_svgf_filter_params, 24 bytes
+    _fields_ = [("levels", u32), ("normal_squarings", u32), ("sigma_luminance", f32), ("sigma_plane", f32), ("flags", u32), ("reserved", u32)]
+
+    @classmethod
+    def make(cls, levels=5, normal_squarings=5, sigma_luminance=1.0, sigma_plane=0.05, flags=0, reserved=0):
+        """The defaults are what mi355rt_svgf_filter uses for a null pointer."""
+        return cls(levels, normal_squarings, sigma_luminance, sigma_plane, flags, reserved)
+
+
+SVGF_ACCUMULATE_DEFAULTS = (32, 0, 0.9, 0.05, 4, 5, 0.05, 0)
+SVGF_FILTER_DEFAULTS = (5, 5, 1.0, 0.05, 0, 0)
+SVGF_GATHERS_ONLY = 1
+SVGF_ABI_VERSION = 1
+
+
 class NoiseParams(C.Structure):                           # mi355rt_noise_params, 32 bytes
     _fields_ = [("threshold", C.c_double), ("floor", C.c_double), ("min_chunks", u32), ("_pad", u32), ("allowed_above", u64)]
 

@@ -10,6 +10,9 @@
   libmi355rt_post.so  hipcc: image-space post stages on device buffers, a library of its own (csrc/post; include/mi355rt_post.h): post_reproject.hip: the
                              temporal reprojection's kernel; post_plan.cpp: its defaults, refusals and launch geometry, no HIP in it; post_api.cpp: the exports.
                              Nothing of csrc/device is linked in (rt_math.h is included for the packing); kernel_hash() does not cover it.
+  libmi355rt_svgf.so  hipcc: the variance-guided temporal filter on device buffers, a library of its own (csrc/svgf; include/mi355rt_svgf.h): svgf_kernels.hip: the
+                             kernels of accumulate and filter; svgf_plan.cpp: defaults, refusals and launch geometry, no HIP in it; svgf_api.cpp: the exports.
+                             Nothing of csrc/device or csrc/post is linked in (rt_math.h is included for the packing); kernel_hash() does not cover it.
   libmi355rt_host.so  g++:   CPU-side producers -- scene loader, mesh readers, BVH build, PNG (csrc/host)
   rt_render           g++:   CLI that stands in for the Rust `main` (csrc/tools)
 
@@ -28,6 +31,7 @@ CSRC = os.path.join(HERE, "csrc")
 DEVICE_SO = os.path.join(OUT, "libmi355rt.so")
 HOST_SO = os.path.join(OUT, "libmi355rt_host.so")
 POST_SO = os.path.join(OUT, "libmi355rt_post.so")
+SVGF_SO = os.path.join(OUT, "libmi355rt_svgf.so")
 CLI = os.path.join(OUT, "rt_render")
 
 # -ffp-contract=off: no FMA contraction -- the reference (rustc) never fuses a*b+c, and parity with the
@@ -182,6 +186,22 @@ def build_post(force=False, verbose=False):
     return POST_SO
 
 
+SVGF_SRCS = [os.path.join(CSRC, "svgf", f) for f in ("svgf_kernels.hip", "svgf_plan.cpp", "svgf_api.cpp")]
+SVGF_DEPS = SVGF_SRCS + [os.path.join(CSRC, "svgf", "svgf_plan.h"), os.path.join(CSRC, "device", "rt_math.h"), os.path.join(CSRC, "device", "rt_device.h"),
+                         os.path.join(ROOT, "include", "mi355rt.h"), os.path.join(ROOT, "include", "mi355rt_svgf.h")]
+
+
+def build_svgf(force=False, verbose=False):
+    """libmi355rt_svgf.so: the device library's compiler and flags (gfx950, -ffp-contract=off, no xnack), its own sources."""
+    os.makedirs(OUT, exist_ok=True)
+    if force or _stale(SVGF_SO, SVGF_DEPS):
+        cmd = [hipcc_path(), *HIPCC_FLAGS, "-o", SVGF_SO, *SVGF_SRCS]
+        if verbose:
+            print(" ".join(cmd))
+        subprocess.check_call(cmd)
+    return SVGF_SO
+
+
 def build_host(force=False, verbose=False):
     os.makedirs(OUT, exist_ok=True)
     srcs = _host_srcs()
@@ -225,7 +245,7 @@ def build_verify(force=False, verbose=False):
 
 
 def build_all(force=False, verbose=False):
-    return build_device(force, verbose=verbose), build_host(force, verbose=verbose), build_cli(force, verbose=verbose), build_post(force, verbose=verbose)
+    return build_device(force, verbose=verbose), build_host(force, verbose=verbose), build_cli(force, verbose=verbose), build_post(force, verbose=verbose), build_svgf(force, verbose=verbose)
 
 
 if __name__ == "__main__":
