@@ -13,6 +13,7 @@
   libmi355rt_svgf.so  hipcc: the variance-guided temporal filter on device buffers, a library of its own (csrc/svgf; include/mi355rt_svgf.h): svgf_kernels.hip: the
                              kernels of accumulate and filter; svgf_plan.cpp: defaults, refusals and launch geometry, no HIP in it; svgf_api.cpp: the exports.
                              Nothing of csrc/device or csrc/post is linked in (rt_math.h is included for the packing); kernel_hash() does not cover it.
+                             (libmi355rt_svgf_grid3.so: the tests' variant with grids of at most 3 workgroups, build_svgf_grid3; not part of build_all.)
   libmi355rt_host.so  g++:   CPU-side producers -- scene loader, mesh readers, BVH build, PNG (csrc/host)
   rt_render           g++:   CLI that stands in for the Rust `main` (csrc/tools)
 
@@ -200,6 +201,28 @@ def build_svgf(force=False, verbose=False):
             print(" ".join(cmd))
         subprocess.check_call(cmd)
     return SVGF_SO
+
+
+def build_svgf_variant(name, defines=(), force=False, verbose=False):
+    """libmi355rt_svgf_<name>.so: the same sources and flags with `defines`, a library of its own; never loaded by the product path and not part of
+    build_all.  svgf.open_library(path) binds it."""
+    os.makedirs(OUT, exist_ok=True)
+    so = os.path.join(OUT, f"libmi355rt_svgf_{name}.so")
+    if force or _stale(so, SVGF_DEPS):
+        cmd = [hipcc_path(), *HIPCC_FLAGS, *[f"-D{d}" for d in defines], "-o", so, *SVGF_SRCS]
+        if verbose:
+            print(" ".join(cmd))
+        subprocess.check_call(cmd)
+    return so
+
+
+# The library whose grids have at most 3 workgroups (svgf_plan.h: MAX_BLOCKS), so that a frame of 9 tiles walks every kernel's tile loop three times and
+# one of 45 tiles fifteen times -- the trips a frame below 2^28 pixels never takes in the product library (tests/test_gpu_svgf_rough.py).
+SVGF_GRID3_DEFINES = ["MI355RT_SVGF_MAX_BLOCKS=3"]
+
+
+def build_svgf_grid3(force=False, verbose=False):
+    return build_svgf_variant("grid3", SVGF_GRID3_DEFINES, force=force, verbose=verbose)
 
 
 def build_host(force=False, verbose=False):

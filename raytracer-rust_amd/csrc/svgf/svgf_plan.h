@@ -12,7 +12,11 @@
 namespace mi355rt_svgf {
 
 constexpr uint32_t TILE_W = 32, TILE_H = 8, BLOCK_THREADS = TILE_W * TILE_H;   // one pixel per lane: a wave is two rows of 32 pixels
-constexpr uint32_t MAX_BLOCKS = 1u << 20;                // a workgroup takes tiles blockIdx.x, blockIdx.x + gridDim.x, ...
+#ifndef MI355RT_SVGF_MAX_BLOCKS                          // (the tests' variant library builds with 3, so that a small frame walks every tile loop more than once; the product never defines it)
+#define MI355RT_SVGF_MAX_BLOCKS (1u << 20)
+#endif
+constexpr uint32_t MAX_BLOCKS = MI355RT_SVGF_MAX_BLOCKS;  // a workgroup takes tiles blockIdx.x, blockIdx.x + gridDim.x, ...
+static_assert(MAX_BLOCKS >= 1u, "a grid has at least one workgroup");
 constexpr uint32_t SCRATCH_PER_PIXEL = 64;               // guides 32, image A 16, image B 16
 constexpr uint32_t SPATIAL_MARK = 0xBF800000u;           // -1.0f: what k_svgf_accumulate leaves in variance_out for a pixel k_svgf_spatial has to estimate (no variance is negative)
 

@@ -116,6 +116,75 @@ def reference(case, prev=True):
     return SR.accumulate(case["cur"], case["prev"], case["hits_cur"], case["color_cur"], case["hits_prev"], case["hist_prev"], case["moments_prev"], case["params"])
 
 
+# ---- rough guides: what the plane cannot give the geometry weight ------------------------------------------------------------------------------
+# The cases above are a plane with one normal and records with the opposite one: nd is +-1 and d is 0, so G(p, q) is 0 or 1 and normal_squarings,
+# sigma_plane, t_p and the absolute value never matter.  The two makers below give G thousands of values strictly inside (0, 1)
+# (tests/test_svgf_rough_cpu.py measures it).
+ROUGH_SEED = 11                                         # of rough(): every size of ROUGH_SIZES meets test_svgf_rough_cpu's conditions with it
+BUMPY_SEED = 5
+ROUGH_SIZES = [(1, 37), (37, 1), (33, 9), (70, 17), (131, 70)]     # a column, a row, one past the 32 x 8 tile each way, 9 ragged tiles, 45 ragged tiles
+BUMPY_SIZES = [((33, 9), (33, 9)), ((70, 17), (70, 17)), ((33, 9), (20, 7))]
+_rough = {}
+
+
+def rough(abi, W, H, seed=ROUGH_SEED):
+    """(hist float32 [n, 4], variance float32 [n], hits HIT_DTYPE [n], colour float32 [n, 3]), read-only and computed once: denoise_cases.synthetic's
+    colour and records unchanged -- tilted and NaN normals, t = 0 / NaN / inf, coincident positions, runs of misses; negative, denormal and non-finite
+    colours -- the history that colour with length 1, and a seeded variance: uniform in [0, 0.05), exactly 0 in the left quarter of the columns, and, at
+    a few pixels each chosen as synthetic chooses its own, 1e30, a denormal, negative values, NaN, +inf (e is inf: a = 0) and -inf -- what
+    accumulate never writes and the filter's header leaves to the caller."""
+    import denoise_cases
+    key = (W, H, seed)
+    if key not in _rough:
+        lin, hits = denoise_cases.synthetic(abi, W, H, seed)
+        n = W * H
+        colour = lin.reshape(n, 3)
+        hist = np.ones((n, 4), F)
+        hist[:, :3] = colour
+        rng = np.random.default_rng(7919 + seed)
+        var = (rng.random(n, dtype=F) * F(0.05)).astype(F)
+        var.reshape(H, W)[:, : W // 4] = F(0.0)
+
+        def pick(k):
+            return rng.choice(n, size=min(k, n), replace=False)
+        if n >= 4:
+            few = max(n // 60, 1)
+            i = pick(few); var[i] = F(1e30)
+            i = pick(few); var[i] = F(1e-40)
+            i = pick(max(n // 40, 1)); var[i] = -var[i] - F(0.01)
+            i = pick(few); var[i] = F(np.nan)
+            i = pick(few); var[i] = F(np.inf)
+            i = pick(few); var[i] = F(-np.inf)
+        else:
+            var[0] = F(-0.25)
+        for a in (hist, var):
+            a.setflags(write=False)
+        _rough[key] = (hist, var, hits, colour)
+    return _rough[key]
+
+
+def bumpy(abi, cur_size, prev_size, max_history=32, min_temporal=4, seed=BUMPY_SEED, flat=None):
+    """build(...) with every record that is neither crafted (`placed`, `added`, the two misses) nor a miss perturbed, in both frames: each component of
+    the normal + N(0, 0.15), renormalised in float64 and rounded once; position.z + N(0, 0.01).  The crafted records keep their decision boundaries;
+    around them the taps' nd and d, and the spatial estimate's G, take values strictly inside their ranges.  flat: build(...)'s dict of the same arguments
+    where the caller has it already (it is copied, not changed)."""
+    case = build(abi, cur_size, prev_size, max_history, min_temporal) if flat is None else {k: v.copy() if isinstance(v, np.ndarray) else v for k, v in flat.items()}
+    rng = np.random.default_rng(seed)
+    n_cur = cur_size[0] * cur_size[1]
+    kept_cur = {j for _, j, _, _ in case["placed"]} | {j for _, j, _ in case["added"]} | ({n_cur - 2, n_cur - 1} if n_cur >= 64 else set())
+    kept_prev = {q for _, _, q, _ in case["placed"] if q is not None} | {q for _, _, qs in case["added"] for q in qs}
+    for hits, kept in ((case["hits_cur"], kept_cur), (case["hits_prev"], kept_prev)):
+        rough_ones = hits["primitive"] != NO_HIT
+        rough_ones[sorted(kept)] = False
+        k = int(rough_ones.sum())
+        nrm = hits["normal"][rough_ones].astype(np.float64) + rng.normal(0.0, 0.15, (k, 3))
+        nrm /= np.linalg.norm(nrm, axis=1, keepdims=True)
+        pos = hits["position"][rough_ones].astype(np.float64)
+        pos[:, 2] += rng.normal(0.0, 0.01, k)
+        hits["normal"][rough_ones], hits["position"][rough_ones] = nrm.astype(F), pos.astype(F)
+    return case
+
+
 # ---- the quality case: tests/test_reproject_cpu.py's setting, entirely on the CPU -----------------------------------------------------------
 def orbit_frames(oracle_mod, abi, host):
     """cornell at 64 x 48, 8 frames of 1 spp along the 0.5-degree orbit from the oracle (seed = frame number), and the oracle's 256 spp of every
