@@ -64,7 +64,8 @@ REFS_SRCS = [os.path.join(CSRC, "refs", "rt_stages.hip"), os.path.join(CSRC, "re
 # in the kernels' translation unit (unit_ball_cooperative is defined there), so the reference build compiles REFS_KERNELS in the place of
 # rt_kernels.hip: that file, included unchanged, and the probe's header behind it.  No file that kernel_hash() covers is touched.
 REFS_KERNELS = os.path.join(CSRC, "refs", "rt_kernels_refs.hip")
-REFS_HEADERS = [os.path.join(CSRC, "refs", "rt_scatter_wave_probe.h")]
+REFS_HEADERS = [os.path.join(CSRC, "refs", "rt_scatter_wave_probe.h"),
+                os.path.join(CSRC, "refs", "rt_range_wave_probe.h")]      # mi355rt_debug_range_wave, likewise (tests/test_gpu_range_wave.py)
 
 
 def _host_srcs():
@@ -151,10 +152,21 @@ def build_device_variant(name, defines=(), force=False, verbose=False, flags=())
     return so
 
 
+# k_render_ctr_simple_qc with the guarded short arithmetic it had before its range arithmetic (rt_math.h, "Range arithmetic"): every step's define at 0,
+# which builds every kernel of the library as it was (profiles/isa_diff_range_arithmetic_vs_parent.txt).  The tests render with both libraries and
+# compare bit for bit (tests/test_gpu_range_arithmetic.py); never loaded by the product path.
+RANGE_OFF_DEFINES = ["MI355RT_QC_RENORM_CLOSED=0", "MI355RT_QC_NORM_RANGED=0", "MI355RT_QC_QUAD_NOFIX=0", "MI355RT_QC_CUBE_NOFIX=0"]
+
+
+def build_range_off(force=False, verbose=False):
+    return build_device_variant("range_off", RANGE_OFF_DEFINES, force=force, verbose=verbose)
+
+
 # k_render_ctr_simple_qc as it was before it carried its path state in place (rt_kernels.hip, MI355RT_QC_*): every step's define at 0.  The tests render
 # with both libraries and compare bit for bit (tests/test_gpu_state_in_place.py); never loaded by the product path.
 # (MI355RT_QC_EMPTY_PASS=0: the camera pass without its empty-pass shortcut, the fourth bit of FORM.)
-QC_FORM0_DEFINES = ["MI355RT_QC_HIT_IN_PLACE=0", "MI355RT_QC_STATE_IN_PLACE=0", "MI355RT_QC_TERM_SELECT=0", "MI355RT_QC_EMPTY_PASS=0"]
+# (... and without the range arithmetic that came after it, RANGE_OFF_DEFINES: the listing tests/test_state_in_place_isa.py knows as the form before.)
+QC_FORM0_DEFINES = ["MI355RT_QC_HIT_IN_PLACE=0", "MI355RT_QC_STATE_IN_PLACE=0", "MI355RT_QC_TERM_SELECT=0", "MI355RT_QC_EMPTY_PASS=0"] + RANGE_OFF_DEFINES
 
 
 def build_qc_form0(force=False, verbose=False):
@@ -168,7 +180,8 @@ EMPTY_PASS_OFF_DEFINES = ["MI355RT_QC_EMPTY_PASS=0", "MI355RT_RESOLVE_SKIP=0"]
 
 
 def build_empty_pass_off(force=False, verbose=False):
-    return build_device_variant("empty_pass_off", EMPTY_PASS_OFF_DEFINES, force=force, verbose=verbose)
+    # (with the later range arithmetic off as well, RANGE_OFF_DEFINES: "the library before the two steps" is the one the parent of that change built)
+    return build_device_variant("empty_pass_off", EMPTY_PASS_OFF_DEFINES + RANGE_OFF_DEFINES, force=force, verbose=verbose)
 
 
 POST_SRCS = [os.path.join(CSRC, "post", f) for f in ("post_reproject.hip", "post_plan.cpp", "post_api.cpp")]
@@ -258,6 +271,20 @@ def build_verify(force=False, verbose=False):
     range conversion) with the compiler's correctly rounded forms -- the product's headers, the product's flags, a standalone program
     that a gpu test runs (tests/test_gpu_short_arithmetic.py)."""
     src = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools", "verify", "short_arithmetic.hip")
+    exe = src[:-4]
+    if force or _stale(exe, [src] + DEVICE_HEADERS):
+        cmd = [hipcc_path(), *[f for f in HIPCC_FLAGS if f not in ("-fPIC", "-shared")], "-Wno-unused-value", "-Wno-unused-result", "-o", exe, src]
+        if verbose:
+            print(" ".join(cmd))
+        subprocess.check_call(cmd)
+    return exe
+
+
+def build_verify_range(force=False, verbose=False):
+    """tools/verify/range_arithmetic: the enumerations behind rt_math.h's range arithmetic (the closed-form second normalisation, the ranged first one,
+    the reciprocal and the division without a fix-up) on the shipped functions -- the product's headers, the product's flags, a standalone program
+    that a gpu test runs (tests/test_gpu_range_arithmetic.py)."""
+    src = os.path.join(ROOT, "tools", "verify", "range_arithmetic.hip")
     exe = src[:-4]
     if force or _stale(exe, [src] + DEVICE_HEADERS):
         cmd = [hipcc_path(), *[f for f in HIPCC_FLAGS if f not in ("-fPIC", "-shared")], "-Wno-unused-value", "-Wno-unused-result", "-o", exe, src]

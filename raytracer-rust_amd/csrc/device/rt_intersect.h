@@ -94,13 +94,21 @@ DI bool hit_plane(cprim_t pr, uint32_t i, f3 ro, f3 rd, float t_min, Cand& c) {
 // rounded sum at most 3 * 2^85 * (1 + 2^-21) < 2^87; with |d| <= 2^99 the computed |num| is at most 2^99 + 2^87 rounded, below 2^100: div_bounded()'s
 // proven range.  The small end and the divisor are as above.  So t = div_bounded() straight down, and a wide wave (an origin beyond 2^60, infinite or
 // NaN) overwrites it with the compiler's division.
-template <bool FASTD = false, bool BOUNDED = false>
+// RANGE_QUAD_NOFIX (k_render_ctr_simple_qc): div_bounded_nofix(), the same quotient without v_div_fixup_f32.  In a wave that is not wide, lane by lane:
+//   |denom| >= EPS and 2^-100 <= |num| < 2^100: div_bounded()'s proven range, |t| in [2^-125, 2^114): a normal number, on which the fix-up returns q.
+//   |denom| >= EPS and 0 < |num| < 2^-100 (a denormal included): |r| <= 2^14, so |q0|, the residual's term and |q| stay below 2^-85 -- t <= t_min either way.
+//   |denom| >= EPS and num == 0: q is a zero of either sign, t <= t_min either way.  (|num| >= 2^100, infinite or NaN: a wide wave.)
+//   |denom| < EPS -- zero and denormals included -- is rejected by the first comparison, whatever t is.
+//   denom NaN (a NaN direction): t is NaN with and without the fix-up, both comparisons on t are false, and the parallelogram test fails on NaN.
+// So `candidate` and every accepted t are the same bits; tools/verify/range_arithmetic.hip compares both over the significands and a table of specials.
+template <bool FASTD = false, bool BOUNDED = false, uint32_t RANGE = 0u>
 DI bool hit_quad(cprim_t pr, uint32_t i, f3 ro, f3 rd, float t_min, Cand& c, bool wide = false) {
     const rec16_t q = load_rec16(pr);                                                               // the whole record: ONE scalar load
     f3 n = mk(q[0], q[1], q[2]);
     float denom = dot(n, rd);
     const float num = q[3] - dot(n, ro);
     float t;
+    if constexpr (FASTD && BOUNDED && (RANGE & RANGE_QUAD_NOFIX) != 0u) { t = div_bounded_nofix(num, denom); keep_computed(t); if (__builtin_expect(wide, 0)) t = num / denom; } else
     if constexpr (FASTD && BOUNDED) { t = div_bounded(num, denom); keep_computed(t); if (__builtin_expect(wide, 0)) t = num / denom; } else
     if (FASTD && __builtin_expect(__ballot(fabsf(num) >= 0x1p100f) == 0ull, 1)) t = div_bounded(num, denom); else
     t = num / denom;
@@ -170,15 +178,17 @@ DI uint32_t cube_axis(f3 po) {                                                  
 // normalized() twice (ray_direction), so it is a unit vector up to rounding, a vector shorter than 1e-4 passed through, or NaN; every component of the
 // object-space direction is then below 3 * 2^100 * (1 + 2^-21) < 2^126 or NaN -- or, where an entry of the record itself is NaN or infinite (the host lets those
 // through: a cube of zero scale on one axis), NaN or infinite, on which the short reciprocal is exact as well -- and recip3 only has to look for denormals.
-// RECIP_FIRST: recip3's FIRST.
-template <bool FASTR = false, bool BOUNDED = false, bool RECIP_FIRST = false, class C>
+// RECIP_FIRST: recip3's FIRST.  RANGE_CUBE_NOFIX (k_render_ctr_simple_qc): recip3_nofix() -- zeros and infinities join the denormals that send a wave away.
+template <bool FASTR = false, bool BOUNDED = false, bool RECIP_FIRST = false, uint32_t RANGE = 0u, class C>
 DI bool hit_cube(cprim_t pr, uint32_t i, f3 ro_w, f3 rd_w, float t_min, C& c) {
     const rec16_t m = load_rec16(pr);                                                               // w2o (3 x 4) and zd: ONE scalar load
     f3 ro = mk(((m[0] * ro_w.x + m[3] * ro_w.y) + m[6] * ro_w.z) + m[9], ((m[1] * ro_w.x + m[4] * ro_w.y) + m[7] * ro_w.z) + m[10],
                ((m[2] * ro_w.x + m[5] * ro_w.y) + m[8] * ro_w.z) + m[11]);                             // xform_w2o_point
     f3 rd = mk(((m[0] * rd_w.x + m[3] * rd_w.y) + m[6] * rd_w.z) + m[12], ((m[1] * rd_w.x + m[4] * rd_w.y) + m[7] * rd_w.z) + m[13],
                ((m[2] * rd_w.x + m[5] * rd_w.y) + m[8] * rd_w.z) + m[14]);                             // xform_w2o_dir
-    float ix, iy, iz; recip3<FASTR, BOUNDED, RECIP_FIRST>(rd.x, rd.y, rd.z, ix, iy, iz);                  // (FASTR: the kernels of mesh-free lists, like normalized<FASTN>)
+    float ix, iy, iz;
+    if constexpr (FASTR && BOUNDED && (RANGE & RANGE_CUBE_NOFIX) != 0u) recip3_nofix<RECIP_FIRST>(rd.x, rd.y, rd.z, ix, iy, iz); else
+    recip3<FASTR, BOUNDED, RECIP_FIRST>(rd.x, rd.y, rd.z, ix, iy, iz);                  // (FASTR: the kernels of mesh-free lists, like normalized<FASTN>)
     float t1x = (-0.5f - ro.x) * ix, t2x = (0.5f - ro.x) * ix;
     float t1y = (-0.5f - ro.y) * iy, t2y = (0.5f - ro.y) * iy;
     float t1z = (-0.5f - ro.z) * iz, t2z = (0.5f - ro.z) * iz;
@@ -425,7 +435,7 @@ DI uint32_t prim_material_kind(const RenderParams& P, uint32_t idx) { return __f
 // no table (the host), so a shift by i >= 32 is never executed.
 // BOUNDED: see hit_quad / hit_cube.  The one test of the walk: does any active lane's origin leave [0, 2^60)?  (`!(... < ...)`: a NaN or infinite origin counts.)
 DI bool walk_origin_wide(f3 ro) { return __ballot(!(fmaxf(fmaxf(fabsf(ro.x), fabsf(ro.y)), fabsf(ro.z)) < 0x1p60f)) != 0ull; }
-template <bool HAS_MESH, uint32_t KINDS = PRIMS_ALL, bool BOUNDED = false, bool RECIP_FIRST = false, class C>
+template <bool HAS_MESH, uint32_t KINDS = PRIMS_ALL, bool BOUNDED = false, bool RECIP_FIRST = false, uint32_t RANGE = 0u, class C>
 DI void walk_list(cprim_t prims, uint32_t n_prims, const DevNode* __restrict__ nodes, const DevTri* __restrict__ tris, f3 ro, f3 rd, C& c, uint32_t pmask = ~0u) {
 #define MI_KIND(k) (((KINDS >> (k)) & 1u) != 0u)
     // Same order as the list, but the dispatch on the kind (wave-uniform: a scalar branch) is taken once per RUN of equal kinds
@@ -440,8 +450,8 @@ DI void walk_list(cprim_t prims, uint32_t n_prims, const DevNode* __restrict__ n
     uint32_t i = 0;
     while (i < n_prims) {
 #define MI_RUN(KIND, ...) if (i < n_prims && prims[i].kind == (KIND)) { const uint32_t end = min(prims[i].run_end, n_prims); do { if ((pmask >> i) & 1u) { __VA_ARGS__; } } while (++i < end); }
-        if (MI_KIND(MI355RT_PRIM_QUAD)) { MI_RUN(MI355RT_PRIM_QUAD,   hit_quad<!HAS_MESH, BOUNDED>(prims + i, i, ro, rd, EPS, c, wide)) }
-        if (MI_KIND(MI355RT_PRIM_CUBE)) { MI_RUN(MI355RT_PRIM_CUBE,   hit_cube<!HAS_MESH, BOUNDED, RECIP_FIRST>(prims + i, i, ro, rd, EPS, c)) }
+        if (MI_KIND(MI355RT_PRIM_QUAD)) { MI_RUN(MI355RT_PRIM_QUAD,   hit_quad<!HAS_MESH, BOUNDED, RANGE>(prims + i, i, ro, rd, EPS, c, wide)) }
+        if (MI_KIND(MI355RT_PRIM_CUBE)) { MI_RUN(MI355RT_PRIM_CUBE,   hit_cube<!HAS_MESH, BOUNDED, RECIP_FIRST, RANGE>(prims + i, i, ro, rd, EPS, c)) }
         if (MI_KIND(MI355RT_PRIM_SPHERE)) { MI_RUN(MI355RT_PRIM_SPHERE, hit_sphere(prims + i, i, ro, rd, EPS, c)) }
         if (MI_KIND(MI355RT_PRIM_PLANE)) { MI_RUN(MI355RT_PRIM_PLANE,  hit_plane(prims + i, i, ro, rd, EPS, c)) }
         if (HAS_MESH) { MI_RUN(MI355RT_PRIM_MESH, hit_mesh(prims + i, i, nodes, tris, ro, rd, EPS, c)) }
@@ -454,11 +464,11 @@ DI void walk_list(cprim_t prims, uint32_t n_prims, const DevNode* __restrict__ n
 // CARRY_PO: the candidate keeps the cube's object-space hit point (CandP).  On for both mesh-free kernels: the Lambert-only one
 // (cornell -1.8 % at 72 VGPRs) and the general one, which needs 80 VGPRs = 6 waves per SIMD for it (veach-mis: +1.9 % at 72 with
 // spills, -2.6 % at 80; see MI355RT_OCC_LOCKSTEP).
-template <bool HAS_MESH, bool CARRY_PO = false, uint32_t KINDS = PRIMS_ALL, bool BOUNDED = false, bool RECIP_FIRST = false>
+template <bool HAS_MESH, bool CARRY_PO = false, uint32_t KINDS = PRIMS_ALL, bool BOUNDED = false, bool RECIP_FIRST = false, uint32_t RANGE = 0u>
 DI bool hit_scene(cprim_t prims, uint32_t n_prims, const DevNode* __restrict__ nodes, const DevTri* __restrict__ tris,
                   f3 ro, f3 rd, Hit& best, uint32_t pmask = ~0u) {
     typename std::conditional<CARRY_PO && !HAS_MESH, CandP, Cand>::type c; cand_reset(c);
-    walk_list<HAS_MESH, KINDS, BOUNDED, RECIP_FIRST>(prims, n_prims, nodes, tris, ro, rd, c, pmask);
+    walk_list<HAS_MESH, KINDS, BOUNDED, RECIP_FIRST, RANGE>(prims, n_prims, nodes, tris, ro, rd, c, pmask);
     if (c.idx == CAND_NONE) return false;
     finish_hit<HAS_MESH, !HAS_MESH, !HAS_MESH, KINDS>((const DevPrim*)prims, tris, c, ro, rd, best);          // (the lockstep kernels' entry: q0 rides along when there is no mesh)
     return true;

@@ -283,7 +283,7 @@ struct HitStock {
     // `here` is 0: a wave-uniform index that the caller makes from the pass's first sample index (below 2^31, rt_device.h), so that the camera record is read (scalar loads) where the pass
     // uses it.  Read as P.cam it is a launch constant, and with the stepped generator the compiler kept its first 32 bytes in eight scalar registers
     // across the whole loop and spilled the loop's own masks for them (13 spilled SGPRs, 23 v_readlane; like this 3 and 9, the plain form 6 and 10).
-    template <class RNG>
+    template <class RNG, uint32_t RANGE = 0u>
     DI void camera(const RenderParams& P, uint32_t sidx, uint32_t slot, f3& ro, f3& rd, uint32_t here) const {
         RNG rng; uint32_t px, py;
         start_path(P, sidx, rng, px, py);
@@ -293,7 +293,7 @@ struct HitStock {
         const float v = div_by_rn(vn, P.height_f, P.inv_height_rn);                         // renderer.rs:97
         const DevCamera& cam = (&P.cam)[here];
         ro = mk(cam.position[0], cam.position[1], cam.position[2]);
-        rd = ray_direction<true>(camera_raw(cam, u, v));                                     // renderer.rs:99
+        rd = ray_direction<true, RANGE>(camera_raw(cam, u, v));                                  // renderer.rs:99
         e[4u * slot + 3u] = make_float4(__uint_as_float(rng.w[0]), __uint_as_float(rng.w[1]), __uint_as_float(rng.w[2]), __uint_as_float(rng.w[3]));
     }
     // After the walk (lanes with cam == true walked sample first + lane from `tail` + lane): finish the paths that end at their camera ray, exactly as
@@ -435,7 +435,7 @@ DI f3 unit_ball_cooperative(bool diffuse, const RNG& rng, uint32_t lane, const u
 // the lookup of miss_colour() sits in the loop whether or not a scene has a sky -- its polynomial constants in vector registers across the whole
 // iteration, and `sky == nullptr ? &P.miss : texel` as a pointer select with a per-lane load from the kernel-argument segment behind every miss.
 // FORM: see FORM_HIT_IN_PLACE (HitStock; k_render_ctr_simple_qc only).  `h` is written only there: by the lanes that are dealt a ring entry.
-template <uint32_t MATS, bool DEFAULTS = true, bool WIDE = !DEFAULTS, bool DROP_PRIO = false, bool Q0_IN_HIT = false, bool FASTN = false, int TRY1 = 0, bool REKEY = false, bool NOSKY = false, uint32_t FORM = 0u, class WC, class PS, class STOCK = NoStock>
+template <uint32_t MATS, bool DEFAULTS = true, bool WIDE = !DEFAULTS, bool DROP_PRIO = false, bool Q0_IN_HIT = false, bool FASTN = false, int TRY1 = 0, bool REKEY = false, bool NOSKY = false, uint32_t FORM = 0u, uint32_t RANGE = 0u, class WC, class PS, class STOCK = NoStock>
 DI bool shade_and_regenerate(const RenderParams& P, WC& wc, uint32_t lane, bool& live, bool can_take, bool hit, Hit& h,
                              PS& ps, uint32_t& n_paths, uint32_t& n_rays, Prof& prof, const STOCK& stock = STOCK()) {
     typedef typename PS::Rng Rng;                                                            // RngCtrT<STEP>: the kernel's form of the draw address
@@ -445,6 +445,7 @@ DI bool shade_and_regenerate(const RenderParams& P, WC& wc, uint32_t lane, bool&
     static_assert(!(STOCKED || PREHIT) || (!DEFAULTS && !REKEY), "the stock serves the lockstep form");
     static_assert(!PREHIT || (MATS & ~MATS_LAMBERT) == 0u, "an entry holds no incoming direction: the Lambert bounce does not read it");
     static_assert(FORM == 0u || (PREHIT && Q0_IN_HIT && NOSKY && TRY1 == 1), "the in-place forms belong to k_render_ctr_simple_qc");
+    static_assert(RANGE == 0u || (PREHIT && NOSKY && FASTN), "range arithmetic belongs to k_render_ctr_simple_qc");
     struct Rad { float x, y, z; };                                                        // 12 bytes per path: global_store_dwordx3
     Rad* __restrict__ radiance = reinterpret_cast<Rad*>(P.radiance);
     float4 q0;                                                                            // first 16 bytes of the hit material; read by lanes that loaded it
@@ -521,7 +522,10 @@ DI bool shade_and_regenerate(const RenderParams& P, WC& wc, uint32_t lane, bool&
             const f3 L = ps.thr * mk(0.f, 0.f, 0.f);
             radiance[ps.sidx] = Rad{L.x, L.y, L.z}; live = false;
         }
-        ps.rd = ray_direction<FASTN>(diffuse_finish<FASTN>(PREHIT && !HIT_IN_PLACE ? hs : h, ball));
+        // (RANGE: every lane runs the two normalisations, idle ones included, and the range forms ballot all of them.  An idle lane holds the leftovers of
+        //  its last path -- a unit normal and try 0 of a draw in [-1, 1)^3: ordinary vectors -- so it sends the wave to the guarded path only as an active
+        //  lane would, for a sum below 1e-4 or a NaN.  Lanes idle only while the wave drains; the A/B is of the whole frame, drain included.)
+        ps.rd = ray_direction<FASTN, RANGE>(diffuse_finish<FASTN, RANGE>(PREHIT && !HIT_IN_PLACE ? hs : h, ball));
         if (live) ++n_rays;
     } else
     if constexpr (DEFAULTS) {
@@ -589,7 +593,7 @@ DI bool shade_and_regenerate(const RenderParams& P, WC& wc, uint32_t lane, bool&
         prof.classes(live && !fresh, live && fresh, __float_as_uint(q0.x));
         const f3 ball = unit_ball_cooperative<WIDE, TRY1>(scattered && ball_use != BALL_NONE, ps.rng, lane, blk1);   // whole wave, uniform control flow
         if (live && !fresh) {
-            if (scattered) scattered = ball_finish<FASTN>(ball_use, PREHIT && !HIT_IN_PLACE ? hs : h, ball, fuzz, raw);     // (a fuzzed metal reflection may still be absorbed)
+            if (scattered) scattered = ball_finish<FASTN, RANGE>(ball_use, PREHIT && !HIT_IN_PLACE ? hs : h, ball, fuzz, raw);     // (a fuzzed metal reflection may still be absorbed)
             if (scattered) {
                 n_thr = ps.thr * atten; n_ro = scatter_origin(PREHIT && !HIT_IN_PLACE ? hs : h, side); n_ri = ps.ray_index + 1u;
                 if (n_ri == P.max_depth) {                                                   // next level has depth == 0 (renderer.rs:20-22)
@@ -602,7 +606,7 @@ DI bool shade_and_regenerate(const RenderParams& P, WC& wc, uint32_t lane, bool&
             }
         }
         ps.ro = n_ro; ps.thr = n_thr; ps.ray_index = n_ri;
-        ps.rd = ray_direction<FASTN>(raw);                                                   // fresh and scattered lanes together
+        ps.rd = ray_direction<FASTN, RANGE>(raw);                                                 // fresh and scattered lanes together
         if (live) ++n_rays;
     }
     prof.mark(3);
@@ -670,6 +674,8 @@ DI void render_ctr_lockstep(const RenderParams& P) {
     static_assert(!PARK_IN_RING || MI355RT_PREHIT_LOW == 1, "rays are parked in the ring's slots: a refill must find the ring empty");
     // An empty refill pass skips camera() and the walk (FORM_EMPTY_PASS, above HitStock).  Only without the sky lookup: there a miss is the constant P.miss.
     constexpr bool EMPTY_PASS = NOSKY && PREHIT && (FORM & FORM_EMPTY_PASS) != 0u;
+    // Range arithmetic (rt_math.h): the kernel the cornell A/B measured it on.  k_render_sky_simple_qc keeps the guarded forms until a workload of its own says otherwise.
+    constexpr uint32_t RANGE = (NOSKY && PREHIT && BOUNDED) ? MI355RT_QC_RANGE : 0u;
     // The mesh-free kernels are compiled for lists that hold something and for paths that may take a step: the host sends an empty list or max_depth == 0 to
     // k_render_ctr_mesh, the plain loop (rt_api.cpp render_samples).  Both are launch constants, and the compiler had turned `n_prims != 0` and `max_depth == 0`
     // into lane masks tested in every iteration (the masks spilled: four v_readlane, two mask operations, two branches): cornell -1.9 %.
@@ -728,10 +734,10 @@ DI void render_ctr_lockstep(const RenderParams& P) {
                 wave_lds_handoff();                        // (camera() writes into slots whose entries other lanes were dealt)
                 if constexpr (PARK_IN_RING) { stock.e[4u * lane] = make_float4(ps.ro.x, ps.ro.y, ps.ro.z, ps.rd.x); *reinterpret_cast<float2*>(stock.e + 4u * lane + 1u) = make_float2(ps.rd.y, ps.rd.z); }
                 else { stock.park_a[lane] = make_float4(ps.ro.x, ps.ro.y, ps.ro.z, ps.rd.x); stock.park_b[lane] = make_float2(ps.rd.y, ps.rd.z); }
-                if (lane < n_cam && walk_cam) stock.template camera<RngCtrT<STEP>>(P, wc.next + lane, (wc.ring_head + wc.ring_count + lane) & 63u, ps.ro, ps.rd, /* here = 0: sample indices stay below 2^31 (band_samples) */ wc.next >> 31);
+                if (lane < n_cam && walk_cam) stock.template camera<RngCtrT<STEP>, RANGE>(P, wc.next + lane, (wc.ring_head + wc.ring_count + lane) & 63u, ps.ro, ps.rd, /* here = 0: sample indices stay below 2^31 (band_samples) */ wc.next >> 31);
             }
         }
-        if (n_cam != 0u ? lane < n_cam && walk_cam : live) hit = hit_scene<HAS_MESH, true, KINDS, BOUNDED, RECIP_FIRST>(prims, P.n_prims, P.nodes, P.tris, ps.ro, ps.rd, h, pmask);     // renderer.rs:24
+        if (n_cam != 0u ? lane < n_cam && walk_cam : live) hit = hit_scene<HAS_MESH, true, KINDS, BOUNDED, RECIP_FIRST, RANGE>(prims, P.n_prims, P.nodes, P.tris, ps.ro, ps.rd, h, pmask);     // renderer.rs:24
         prof.mark(1);
         if constexpr (PREHIT) {
             if (n_cam != 0u) {                             // finish or stock the camera paths, take the parked rays back, and walk them next
@@ -754,7 +760,7 @@ DI void render_ctr_lockstep(const RenderParams& P) {
                 continue;
             }
         }
-        if (!shade_and_regenerate<MATS, false, true, true, !HAS_MESH, /* FASTN */ true, /* TRY1 */ SIMPLE ? 1 : 0, /* REKEY */ false, NOSKY, FORM>(P, wc, lane, live, true, hit, h, ps, n_paths, n_rays, prof, stock)) break;
+        if (!shade_and_regenerate<MATS, false, true, true, !HAS_MESH, /* FASTN */ true, /* TRY1 */ SIMPLE ? 1 : 0, /* REKEY */ false, NOSKY, FORM, RANGE>(P, wc, lane, live, true, hit, h, ps, n_paths, n_rays, prof, stock)) break;
         prof.mark(4);
 #ifdef MI355RT_STAMPS
         if (wc.exhausted()) {                              // all work dealt: from here on the wave only drains its own paths

@@ -199,24 +199,35 @@ DI bool scatter_pre(const DevMat* __restrict__ mats, const DevTexture* __restric
     if (diffuse) ball_use = BALL_DIFFUSE;
     return true;
 }
-template <bool FASTN = false>
+template <bool FASTN = false, uint32_t RANGE = 0u>
 DI f3 diffuse_finish(const Hit& h, f3 p) {                                          // material.rs:54-62
-    f3 dir = h.n + normalized<FASTN>(p);
+    f3 dir = h.n + normalized_ranged<FASTN, RANGE>(p);                                 // (RANGE: rt_math.h; the accepted point has len2 < 1)
     return near_zero(dir) ? h.n : dir;
 }
 // What the accepted unit-ball point turns into: the Lambert-style direction, or the metal's fuzzed reflection, which may be absorbed
 // (material.rs:97-104: `reflected + fuzz * p`, None unless it leaves on the normal's side).  Returns false when absorbed.
-template <bool FASTN = false>
+template <bool FASTN = false, uint32_t RANGE = 0u>
 DI bool ball_finish(uint32_t ball_use, const Hit& h, f3 p, float fuzz, f3& raw) {
-    if (ball_use == BALL_DIFFUSE) raw = diffuse_finish<FASTN>(h, p);
+    if (ball_use == BALL_DIFFUSE) raw = diffuse_finish<FASTN, RANGE>(h, p);
     else if (ball_use == BALL_METAL) { raw = raw + p * fuzz; return dot(raw, h.n) > 0.0f; }
     return true;
 }
 // What every scatter() and Camera::get_ray end with: `.normalized()` of the direction, then Ray::new normalises again
 // (ray.rs:12-17) -- and the origin offset along the normal.  The callers run it ONCE for all lanes of the wave, whatever
 // branch produced the raw direction (it was the tail of every material branch and of the camera ray: ~66 instructions each).
-template <bool FASTN = false>
-DI f3 ray_direction(f3 raw) { return normalized<FASTN>(normalized<FASTN>(raw)); }
+// RANGE (k_render_ctr_simple_qc; rt_math.h "Range arithmetic"): the first normalisation by normalized_ranged(), the second as the closed form of
+// its input's len2 -- the scale first, and a wave with a lane outside |len2 - 1| <= 2^-13 overwrites it with normalized<true>()'s (normalize_scale), out of line.
+template <bool FASTN = false, uint32_t RANGE = 0u>
+DI f3 ray_direction(f3 raw) {
+    const f3 once = normalized_ranged<FASTN, RANGE>(raw);
+    if constexpr (FASTN && (RANGE & RANGE_RENORM_CLOSED) != 0u) {
+        const float x = len2(once), t = renorm_t(x);
+        float r = renorm_scale(t);
+        keep_computed(r);
+        if (__builtin_expect(__ballot(!renorm_in_range(t)) != 0ull, 0)) r = normalize_scale(x);
+        return once * r;
+    } else return normalized<FASTN>(once);
+}
 DI f3 scatter_origin(const Hit& h, float side) { return h.p + h.n * side; }
 // Sequential composition (reference-stream replay kernel): random_in_unit_sphere as the plain loop, vec3.rs:54-61.
 template <class Rng>

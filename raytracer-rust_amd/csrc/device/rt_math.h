@@ -141,6 +141,109 @@ DI f3 normalized(f3 a) {                                                        
     if constexpr (FASTN) { const float l = length_for_normalize(len2(a)); if (l < EPS) return a; return a * recip_normal_range(l); }
     const float l = len(a); if (l < EPS) return a; return a * (FASTN ? recip_normal_range(l) : 1.0f / l);
 }
+
+// ---------------------------------------------------------------------------------------------------
+// Range arithmetic (k_render_ctr_simple_qc only): the short forms above, without the work that only serves operands outside the range the kernel's
+// values lie in.  Each form tests the range it is proven on -- one comparison and a ballot -- and a wave with a lane outside it takes the form above,
+// out of line; so any operand still gives the bits it gave before.  tools/verify/range_arithmetic.hip enumerates every claim on these functions.
+// RANGE (a template argument of ray_direction, diffuse_finish, hit_quad, hit_cube, recip3 and what passes it down; 0 everywhere else, which folds to the
+// code as it was): one bit per step, each with a build define, MI355RT_QC_*, whose 0 builds the form before it (build.RANGE_OFF_DEFINES: all four).
+//   RANGE_RENORM_CLOSED  ray_direction's second normalisation as a closed form of len2 (renorm_scale)
+//   RANGE_NORM_RANGED    the first normalisation of a bounded vector without guards, pass-through selects and fix-up (normalized_ranged)
+//   RANGE_QUAD_NOFIX     the quad's t without v_div_fixup_f32 (div_bounded_nofix)
+//   RANGE_CUBE_NOFIX     the cube's three reciprocals without v_div_fixup_f32 (recip_nofix; recip3's class test also looks for zeros and infinities)
+// The first and the last ship at 1.  RANGE_NORM_RANGED measures faster and stays at 0 because it changes the kernel's scalar spill figures, which
+// tests/test_nosky_budget.py and tests/test_empty_pass_isa.py pin by equality; RANGE_QUAD_NOFIX stays at 0 because its gain was inside three times
+// the spread.  What each measured: DESIGN.md 4.1 "Range arithmetic", profiles/bench_range_arithmetic_vs_parent.txt.
+// ---------------------------------------------------------------------------------------------------
+#ifndef MI355RT_QC_RENORM_CLOSED
+#define MI355RT_QC_RENORM_CLOSED 1
+#endif
+#ifndef MI355RT_QC_NORM_RANGED
+#define MI355RT_QC_NORM_RANGED 0                             // measured faster, not shipped: it moves the spill figures that existing tests pin (DESIGN.md 4.1 "Range arithmetic")
+#endif
+#ifndef MI355RT_QC_QUAD_NOFIX
+#define MI355RT_QC_QUAD_NOFIX 0                              // inside the noise on top of step 1 (2.7 times the spread where the rule asks for 3): DESIGN.md 4.1
+#endif
+#ifndef MI355RT_QC_CUBE_NOFIX
+#define MI355RT_QC_CUBE_NOFIX 1
+#endif
+enum : uint32_t { RANGE_RENORM_CLOSED = 1u, RANGE_NORM_RANGED = 2u, RANGE_QUAD_NOFIX = 4u, RANGE_CUBE_NOFIX = 8u };
+#define MI355RT_QC_RANGE ((MI355RT_QC_RENORM_CLOSED != 0 ? RANGE_RENORM_CLOSED : 0u) | (MI355RT_QC_NORM_RANGED != 0 ? RANGE_NORM_RANGED : 0u) | (MI355RT_QC_QUAD_NOFIX != 0 ? RANGE_QUAD_NOFIX : 0u) | (MI355RT_QC_CUBE_NOFIX != 0 ? RANGE_CUBE_NOFIX : 0u))
+
+// recip_normal_range() without its fix-up.  For a finite non-zero x whose reciprocal is a normal number v_div_fixup_f32(r, x, 1) returns |r| with the
+// sign of x * 1, which is r: equal to 1.0f / x for every normal x below 2^126 in magnitude, and NaN for NaN.  What the fix-up served are zeros,
+// infinities and denormals (x = 0: v_rcp gives inf, the Newton step inf * 0 = NaN): the caller keeps those out.
+DI float recip_nofix(float x) {
+    const float r = __builtin_amdgcn_rcpf(x);
+    const float e = __builtin_fmaf(-x, r, 1.0f);
+    return __builtin_fmaf(e, r, r);
+}
+// recip3<true, BOUNDED, FIRST> with recip_nofix(): the class test that sends a wave to the compiler's reciprocals looks for zeros and infinities beside
+// the denormals -- the same v_cmp_class_f32 per component with a wider mask.  What it lets through is a normal number, below 2^126 by the caller's
+// bound (hit_cube), or NaN.
+template <bool FIRST = false>
+DI void recip3_nofix(float x, float y, float z, float& ix, float& iy, float& iz) {
+    constexpr int AWAY = 0x010 | 0x080 | 0x020 | 0x040 | 0x004 | 0x200;                     // v_cmp_class_f32: -denormal, +denormal, -0, +0, -inf, +inf
+    ix = recip_nofix(x); iy = recip_nofix(y); iz = recip_nofix(z);
+    if constexpr (FIRST) { keep_computed(ix); keep_computed(iy); keep_computed(iz); }
+    const bool away = __builtin_isfpclass(x, AWAY) | __builtin_isfpclass(y, AWAY) | __builtin_isfpclass(z, AWAY);
+    if (__builtin_expect(__ballot(away) != 0ull, 0)) { ix = 1.0f / x; iy = 1.0f / y; iz = 1.0f / z; }
+}
+// div_bounded() without its fix-up: the same q. For finite non-zero a and b whose quotient is a normal number the fix-up returns |q| with the sign of
+// a * b, which is q -- so inside div_bounded()'s proven range (2^-25 <= |b| <= 2^25, 2^-100 <= |a| <= 2^100) this IS a / b.  Outside it: a == 0 gives
+// a zero (q0 = 0 * r, e = 0, q = 0 -- possibly of the other sign than a / b's); b zero, denormal (v_rcp flushes it: r = inf) or NaN gives NaN or an
+// infinity; an infinite a gives an infinity or NaN.  hit_quad's comment says why none of those lanes is accepted either way.
+DI float div_bounded_nofix(float a, float b) {
+    float r = __builtin_amdgcn_rcpf(b);
+    { const float e = __builtin_fmaf(-b, r, 1.0f); r = __builtin_fmaf(e, r, r); }
+    const float q = a * r;
+    const float e = __builtin_fmaf(-b, q, a);
+    return __builtin_fmaf(e, r, q);
+}
+// The second normalisation of ray_direction().  Its input went through normalized() once, so x = len2 is one of a handful of floats next to 1 (over
+// 20 M random directions: 11 values within 1 +- 7 * 2^-24), and there RN(1 / RN(sqrt(x))) is a step function of x:
+//   r = 1 - 2^-23 * floor((x - 1) * 2^22).
+// (The square root halves the distance to 1 and the reciprocal mirrors it, each rounded to the float grid, which is 2^-23 wide above 1 and 2^-24 below.)
+// The proof is an enumeration: the closed form equals recip_normal_range(length_for_normalize(x)) for every float x with |x - 1| <= 2^-13
+// (tests/test_range_closed_form.py with numpy's correctly rounded sqrt and division; tools/verify/range_arithmetic.hip on the shipped functions, all 2^32 x).
+// Every operation is exact: t = fma(x, 2^22, -2^22) = (x - 1) * 2^22 has at most 24 significant bits, floor(t) is an integer of magnitude at most 512,
+// and 1 - floor(t) * 2^-23 is a float.  The guard |t| <= 512, that is |x - 1| <= 2^-13, is false for NaN and for a vector that normalized() passed
+// through (a length below 1e-4: t = -2^22).
+// (t as v_ldexp_f32 and an add of the literal -2^22, both exact: as one fma the two constants 2^22 and -2^22 cost a v_mov_b32 -- VOP3 takes no literal.)
+DI float renorm_t(float x) { return __builtin_ldexpf(x, 22) - 0x1p22f; }
+DI bool renorm_in_range(float t) { return fabsf(t) <= 512.0f; }
+DI float renorm_scale(float t) { return __builtin_fmaf(-0x1p-23f, __builtin_floorf(t), 1.0f); }
+// The first normalisation for a vector of bounded length: the unit-ball point (x = len2 < 1), n + unit (x <= 4 and rounding), a camera direction.
+// One two-sided test of x -- med3(x, lo, hi) == x, false for NaN -- and inside it the straight line: v_rsq_f32 with its correction, v_rcp_f32 with its
+// Newton step, three multiplies.  NORM_LO = 2^-26 > EPS^2 (1e-8 < 1.4902e-8): for x >= 2^-26 the length RN(sqrt(x)) is at least 2^-13 = 1.2207e-4 > EPS
+// (sqrt is monotonic and exact at 2^-26), so normalized()'s pass-through `l < EPS` is false and its selects choose the scaled vector; x >= 2^-100 and
+// x != inf, so length_for_normalize()'s two guards choose `s`.  NORM_HI = 2^100: the length is a normal number in [2^-13, 2^50], far below 2^126, and
+// its reciprocal a normal number in [2^-50, 2^13], on which the fix-up is the identity (recip_nofix).  So for lo <= x <= hi, l and r are the values
+// normalized<true>() computes, bit for bit (enumerated for every such x: tools/verify/range_arithmetic.hip).
+constexpr float NORM_LO = 0x1p-26f, NORM_HI = 0x1p100f;
+DI bool norm_in_range(float x) { return __builtin_amdgcn_fmed3f(x, NORM_LO, NORM_HI) == x; }
+DI float length_ranged(float x) {
+    const float y = __builtin_amdgcn_rsqf(x);
+    const float g = x * y, h = 0.5f * y;
+    const float d = __builtin_fmaf(-g, g, x);
+    return __builtin_fmaf(d, h, g);
+}
+// A wave with a lane outside the range (a zero vector, one below 1e-4, NaN, an infinity, an idle lane's leftovers) takes normalized<true>() for all
+// lanes, out of line: the short scale is computed first (keep_computed) and overwritten there, as recip3<BOUNDED> does.  Only the SCALE is merged, one
+// register: normalized<true>() is a * normalize_scale(len2(a)), its pass-through a * 1.0f -- the same bits as `a` for every float (f32 denormals are
+// not flushed in these kernels; tools/verify/range_arithmetic.hip runs tiny and denormal vectors through both).
+DI float normalize_scale(float x) { const float l = length_for_normalize(x); return (l < EPS) ? 1.0f : recip_normal_range(l); }
+template <bool FASTN = false, uint32_t RANGE = 0u>
+DI f3 normalized_ranged(f3 a) {
+    if constexpr (FASTN && (RANGE & RANGE_NORM_RANGED) != 0u) {
+        const float x = len2(a);
+        float r = recip_nofix(length_ranged(x));
+        keep_computed(r);
+        if (__builtin_expect(__ballot(!norm_in_range(x)) != 0ull, 0)) r = normalize_scale(x);
+        return a * r;
+    } else return normalized<FASTN>(a);
+}
 DI bool near_zero(f3 a) { const float S = 1e-8f; return fabsf(a.x) < S && fabsf(a.y) < S && fabsf(a.z) < S; }  // :63-66
 DI bool has_nan(f3 a) { return (a.x != a.x) || (a.y != a.y) || (a.z != a.z); }
 DI bool is_zero(f3 a) { return a.x == 0.0f && a.y == 0.0f && a.z == 0.0f; }

@@ -7,3 +7,4 @@
 #endif
 #include "../device/rt_kernels.hip"
 #include "rt_scatter_wave_probe.h"   // k_probe_scatter_wave, mi355rt_debug_scatter_wave: the bounce's pieces on caller-chosen waves (tests/test_gpu_scatter_wave.py)
+#include "rt_range_wave_probe.h"     // k_probe_range_wave, mi355rt_debug_range_wave: the range arithmetic's forms on caller-chosen waves (tests/test_gpu_range_wave.py)

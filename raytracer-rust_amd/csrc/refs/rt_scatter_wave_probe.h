@@ -25,7 +25,8 @@ static_assert(sizeof(WaveProbeIn) == 64 && sizeof(WaveProbeOut) == 64, "wave pro
 constexpr uint32_t WAVE_PROBE_LIVE = 0x100u;
 
 // IN_PLACE: the bounce of FORM_STATE_IN_PLACE (k_render_ctr_simple_qc) -- the ball for the live lanes, diffuse_finish and ray_direction by all lanes.
-template <uint32_t MATS, bool WIDE, bool FASTN, int TRY1, bool TERMINAL_DONE, bool STEP, bool IN_PLACE>
+// RANGE: that kernel's range arithmetic (rt_math.h), as render_ctr_lockstep passes it.
+template <uint32_t MATS, bool WIDE, bool FASTN, int TRY1, bool TERMINAL_DONE, bool STEP, bool IN_PLACE, uint32_t RANGE>
 __global__ void __launch_bounds__(BLOCK_THREADS) k_probe_scatter_wave(const DevMat* __restrict__ mats, const WaveProbeIn* __restrict__ in, WaveProbeOut* __restrict__ out) {
     typedef RngCtrT<STEP> Rng;
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;                        // (the entry pads the records to whole workgroups)
@@ -52,16 +53,16 @@ __global__ void __launch_bounds__(BLOCK_THREADS) k_probe_scatter_wave(const DevM
         org = scatter_origin(h, EPS);
         rng.begin_scatter();
         ball = unit_ball_cooperative<WIDE, TRY1>(live, rng, lane, blk1);              // whole wave, uniform control flow
-        dir = ray_direction<FASTN>(diffuse_finish<FASTN>(h, ball));
+        dir = ray_direction<FASTN, RANGE>(diffuse_finish<FASTN, RANGE>(h, ball));
         scattered = live; used_ball = live;
     } else {
         uint32_t ball_use = BALL_NONE; float side = EPS, fuzz = 0.f; f3 raw = mk(0.f, 0.f, 1.f);
         if (live) scattered = scatter_pre<MATS, WIDE, FASTN, TERMINAL_DONE>(mats, nullptr, q0, h, rd_in, rng, side, raw, atten, emitted, ball_use, fuzz);
         used_ball = scattered && ball_use != BALL_NONE;
         ball = unit_ball_cooperative<WIDE, TRY1>(used_ball, rng, lane, blk1);         // whole wave, uniform control flow
-        if (live && scattered) scattered = ball_finish<FASTN>(ball_use, h, ball, fuzz, raw);   // (a fuzzed metal reflection may still be absorbed)
+        if (live && scattered) scattered = ball_finish<FASTN, RANGE>(ball_use, h, ball, fuzz, raw);   // (a fuzzed metal reflection may still be absorbed)
         org = scatter_origin(h, side);
-        dir = ray_direction<FASTN>(raw);
+        dir = ray_direction<FASTN, RANGE>(raw);
     }
     WaveProbeOut o{};
     if (live) {
@@ -76,14 +77,14 @@ __global__ void __launch_bounds__(BLOCK_THREADS) k_probe_scatter_wave(const DevM
 // The forms the library launches: the template arguments at the call sites of shade_and_regenerate (render_ctr_lockstep, render_ctr_wavefront,
 // render_ctr_state_machine) and the STEP each kernel is instantiated with.  Two kernels that resolve to the same arguments share one instantiation.
 struct WaveForm { const char* name; uint32_t mats, wide, fastn, try1, terminal_done, step, in_place; const void* kernel; };
-template <uint32_t MATS, bool WIDE, bool FASTN, int TRY1, bool TERMINAL_DONE, bool STEP, bool IN_PLACE = false>
+template <uint32_t MATS, bool WIDE, bool FASTN, int TRY1, bool TERMINAL_DONE, bool STEP, bool IN_PLACE = false, uint32_t RANGE = 0u>
 static WaveForm wave_form(const char* name) {
     return WaveForm{name, MATS, WIDE, FASTN, (uint32_t)TRY1, TERMINAL_DONE, RngCtrT<STEP>::STEPPED, IN_PLACE,
-                    reinterpret_cast<const void*>(&k_probe_scatter_wave<MATS, WIDE, FASTN, TRY1, TERMINAL_DONE, STEP, IN_PLACE>)};
+                    reinterpret_cast<const void*>(&k_probe_scatter_wave<MATS, WIDE, FASTN, TRY1, TERMINAL_DONE, STEP, IN_PLACE, RANGE>)};
 }
 static const WaveForm WAVE_FORMS[] = {
     wave_form<MATS_LAMBERT, true, true, 1, true, step_form(STEP_SIMPLE_QC)>("k_render_sky_simple_qc"),
-    wave_form<MATS_LAMBERT, true, true, 1, true, step_form(STEP_SIMPLE_QC), (MI355RT_QC_FORM & FORM_STATE_IN_PLACE) != 0u>("k_render_ctr_simple_qc"),
+    wave_form<MATS_LAMBERT, true, true, 1, true, step_form(STEP_SIMPLE_QC), (MI355RT_QC_FORM & FORM_STATE_IN_PLACE) != 0u, MI355RT_QC_RANGE>("k_render_ctr_simple_qc"),
     wave_form<MATS_LAMBERT, true, true, 1, true, step_form(STEP_SIMPLE)>("k_render_ctr_simple"),
     wave_form<MATS_NO_SPECULAR, true, true, 0, true, step_form(STEP_NOSPEC)>("k_render_ctr_nospec"),
     wave_form<MATS_NO_SPECULAR, true, true, 0, true, step_form(STEP_WF_MESHFREE)>("k_render_ctr_wf_meshfree"),

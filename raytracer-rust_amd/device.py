@@ -54,6 +54,8 @@ def refs():
     L.mi355rt_debug_rng_block.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_int]
     L.mi355rt_debug_scatter_wave.restype = C.c_int
     L.mi355rt_debug_scatter_wave.argtypes = [C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_int]
+    L.mi355rt_debug_range_wave.restype = C.c_int
+    L.mi355rt_debug_range_wave.argtypes = [C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32), C.c_int]
     L.mi355rt_debug_scatter_wave_form.restype = C.c_int
     L.mi355rt_debug_scatter_wave_form.argtypes = [C.c_uint32, C.c_void_p, C.POINTER(C.c_char_p)]
     return L
@@ -150,6 +152,23 @@ def debug_scatter_wave(form, materials, records, hip_device=0):
     _check(L.mi355rt_debug_scatter_wave(int(form), materials, len(materials), rec.ctypes.data, rec.shape[0], out.ctypes.data, hip_device),
            "mi355rt_debug_scatter_wave", L)
     return out
+
+
+def debug_range_wave(selector, quad_d, cube_d, records, hip_device=0):
+    """Diagnostic (reference build): k_render_ctr_simple_qc's range arithmetic on caller-chosen waves (csrc/refs/rt_range_wave_probe.h).  selector 0:
+    the guarded forms, 1: the RANGE bits the library ships, 2: all four steps.  quad_d: float32 [16], cube_d: float32 [28] (the words of DevPrim::d the
+    two hit tests read); records: uint32 [n, 16] = (raw direction[3], origin[3] as float bits, flags: bit 0 active), 64 to a wave.  Returns (uint32
+    [n, 16]: the float bits of normalized_ranged[3], ray_direction[3], quad hit, quad t, cube hit, cube t, cube po[3], then quad idx, cube idx, 0;
+    the RANGE bits behind the selector)."""
+    L = refs()
+    q, c = np.ascontiguousarray(quad_d, np.float32), np.ascontiguousarray(cube_d, np.float32)
+    assert q.shape == (16,) and c.shape == (28,)
+    rec = np.ascontiguousarray(records, np.uint32).reshape(-1, 16)
+    out = np.zeros((rec.shape[0], 16), np.uint32)
+    bits = C.c_uint32()
+    _check(L.mi355rt_debug_range_wave(int(selector), q.ctypes.data, c.ctypes.data, rec.ctypes.data, rec.shape[0], out.ctypes.data, C.byref(bits), hip_device),
+           "mi355rt_debug_range_wave", L)
+    return out, int(bits.value)
 
 
 def debug_scatter_records(materials, records, hip_device=0):
